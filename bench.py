@@ -6,7 +6,10 @@ catalogue, one GPU.  A "step" is one BaseRunner.fit iteration (forward, BPR loss
 optimizer row update) over one batch of B synthetic (user, pos, neg[K]) tuples whose ids are
 already resident in HBM.  Prints ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--opt SGD|Adam|Adagrad]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--opt SGD|Adam|Adagrad] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (loss, updated parameters; seeded row samples of the large
+tables) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 
 N > 1: one rank per GPU over RCCL.  `python bench.py --gpus N` starts its own N rank processes (rendezvous on
 127.0.0.1); launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it uses the ranks it
@@ -75,7 +78,15 @@ def parse():
                     help="the contract workload only: skip the short legs of the other BASELINE configs that the default run attaches "
                          "as `secondary` (NeuMF at 10 M and 100 M items, SASRec, DeepFM at two batch sizes; N > 1: sharded NeuMF on the "
                          "100 M-item table)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss and the parameters it updated; "
+                         "a fixed, seeded row sample of the tables too large to write whole) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (single GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs: single GPU only (--gpus 1)")
     if args.dropout is None:
         args.dropout = 0.2 if args.workload == "deepfm" else 0.0
     if args.workload == "deepfm":  # configs[4]: the reference's CTR script shape unless overridden
@@ -760,6 +771,55 @@ def launch_check(rank, world, backend):
                           "env": {k: os.environ.get(k) for k in ("WORLD_SIZE", "MASTER_ADDR", "LOCAL_RANK")}}))
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: everything written, in all
+DUMP_WHOLE_BYTES = 4 << 20  # arrays up to this size are written whole; larger tables are row-sampled
+DUMP_SEED = 20240101       # the row sample: the same rows for the same arguments, whatever the build
+
+
+def step_outputs(trainer):
+    """what a caller of the timed step holds after it: the loss it returned and the parameters it updated in place"""
+    from rechorus_amd import engine
+    out = {"loss": trainer.loss}
+    if isinstance(trainer, engine.BprmfTrainer):
+        out.update(U=trainer.U, I=trainer.I)
+    elif isinstance(trainer, (engine.NeumfTrainer, engine.SasrecTrainer)):
+        for k, v in trainer.P.items():
+            if k == "layers":
+                for i, lay in enumerate(v):
+                    out.update({f"layers.{i}.{n}": t for n, t in lay.items()})
+            else:
+                out[k] = v
+    elif isinstance(trainer, DeepfmBench):
+        out.update(trainer.model.named_parameters())
+    else:
+        raise SystemExit(f"--dump-outputs: no outputs defined for {type(trainer).__name__}")
+    return out
+
+
+def dump_outputs(outputs, path):
+    """DIR/<name>.npy for every output (float32; float64 stays float64).  Arrays above DUMP_WHOLE_BYTES are sampled along
+    their first dimension: rows drawn once from DUMP_SEED, sorted, the large arrays sharing what the small ones leave of
+    DUMP_BYTES.  -> {name: {"shape": written, "of": full shape, "rows": "all" | "sampled"}}"""
+    arrays = {k: t.detach() for k, t in outputs.items()}
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    big = sorted(k for k, t in arrays.items() if size(t) > DUMP_WHOLE_BYTES)
+    left = DUMP_BYTES - sum(size(t) for k, t in arrays.items() if k not in big)
+    os.makedirs(path, exist_ok=True)
+    manifest = {}
+    for k, t in arrays.items():
+        full = tuple(t.shape)
+        if k in big:
+            row_bytes = size(t) // t.shape[0]
+            n = min(t.shape[0], left // len(big) // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], size=n, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        np.save(os.path.join(path, k + ".npy"), a)
+        manifest[k] = {"shape": list(a.shape), "of": list(full), "rows": "sampled" if k in big else "all"}
+    return manifest
+
+
 def measure(args, rank, world, device, dist):
     """one workload on the ranks of this job: warm-up, the timed steps between barriers, then (outside the timed region) the
     live roofline phases and the CPU baseline -> the JSON object of the line"""
@@ -849,6 +909,8 @@ def measure(args, rank, world, device, dist):
     loss = float(trainer.loss.item())
     if not np.isfinite(loss):
         raise SystemExit(f"non-finite loss {loss}")
+    # before anything below steps the trainer again (the roofline phases train on)
+    dumped = dump_outputs(step_outputs(trainer), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     if args.workload == "deepfm":
         args.items, args.users, args.num_neg = DEEPFM_VOCAB["item_id"], DEEPFM_VOCAB["user_id"], 0
@@ -894,6 +956,8 @@ def measure(args, rank, world, device, dist):
         },
         "final_loss": loss,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "sample_seed": DUMP_SEED}
 
     if rank == 0 and not args.no_roofline and hasattr(trainer, "profile_step"):
         # per-phase hipEvent timing on the launch stream, measured live (profiling steps are outside the timed region
