@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void full_rank_kernel(
 
 // rank = 1 (the target, column 0 of the reference's candidate list) + catalogue count - clicked items
 // that scored >= target (masked to -inf by BaseRunner.predict :243-250); the target's own catalogue
-// column was already skipped by full_rank_kernel
+// column was already skipped by full_rank_kernel.  A NaN target score gives rank 0, as (pred >= NaN).sum() does
 template <int D>
 __global__ __launch_bounds__(kBlock) void full_rank_finish_kernel(
     const float* __restrict__ Uvec, const float* __restrict__ I, const float* __restrict__ tscore,
@@ -143,10 +143,10 @@ __global__ __launch_bounds__(kBlock) void full_rank_finish_kernel(
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (row >= N) return;  // wave-uniform
+  const float t = tscore[row];
   int sub = 0;
   if (clicked_ptr) {
     const int64_t u = users[row];
-    const float t = tscore[row];
     const int64_t tgt_item = targets[row];
     int64_t prev = -1;
     for (int64_t j = clicked_ptr[u] + lane; j < clicked_ptr[u + 1]; j += 64) {
@@ -159,7 +159,8 @@ __global__ __launch_bounds__(kBlock) void full_rank_finish_kernel(
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) sub += __shfl_xor(sub, off, 64);
-  if (lane == 0) rank[row] = 1 + rank[row] - sub;
+  // a NaN target compares false with everything, itself included: the reference's rank is 0 (and so is rc_target_rank's)
+  if (lane == 0) rank[row] = (t != t) ? 0 : 1 + rank[row] - sub;
 }
 
 }  // namespace rc
@@ -169,15 +170,21 @@ __global__ __launch_bounds__(kBlock) void full_rank_finish_kernel(
 // 74-133,135-168).  A row holds its positives in columns [0, pos_num) and its negatives in [max_pos, max_pos + neg_num); the
 // reference masks everything else to -inf, subtracts 1e-6 from the positive columns (so a positive that ties with a negative
 // ranks below it, :89-96), argsorts -score with a stable merge sort, truncates the ranked 0/1 labels to pos + neg entries and
-// forms the metrics in float64.  Only the positions of the POSITIVES in that order matter:
-//   r_i   = #{valid j : key_j > key_i} + #{valid j < i : key_j == key_i}          (key = (double) score - 1e-6 [column < max_pos])
-//   HR@k  = [min_i r_i < k];   DCG@k = sum_{r_i < k} 1 / log2(r_i + 2);   IDCG@k = sum_{t < min(p, k)} 1 / log2(t + 2)
-//   AP@k  = sum_{r_i < k} #{i' : r_i' <= r_i} / (r_i + 1)  /  clip(p, 1, k)           (p = number of valid positives)
+// forms the metrics in float64.  Only the positions of the POSITIVES in that order matter.  With key = (double) score - 1e-6
+// [column < max_pos] for a valid column and -inf for every other column (read as -inf, never from memory), the sort puts NaN
+// keys last, in column order, behind every non-NaN key (the masked columns included):
+//   r_i   = #{j : key_j > key_i} + #{j < i : key_j == key_i}                        (key_i not NaN; NaN key_j never counts)
+//   r_i   = #{j : key_j not NaN} + #{j < i : key_j NaN}                             (key_i NaN)
+// A positive with r_i >= p + q falls off the truncated label list: it counts in none of the metrics.  Over the m positives
+// with r_i < p + q:
+//   HR@k  = [min_i r_i < k];   DCG@k = sum_{r_i < k} 1 / log2(r_i + 2);   IDCG@k = sum_{t < min(m, k)} 1 / log2(t + 2)
+//   AP@k  = sum_{r_i < k} #{i' : r_i' <= r_i} / (r_i + 1)  /  clip(m, 1, k)
 // One wave per row: keys of the row in LDS, a positive's rank by a strided count + wave sum, the per-k sums in float64.
 namespace rc {
 
 constexpr int kListMetricsMaxK = 16;
-constexpr int kListMetricsMaxN = 2048;   // columns per row the LDS staging holds (4 waves x 2048 doubles + ranks = 80 KB)
+// columns per row the LDS staging holds: 4 waves x (n doubles + 2 max_pos ints), at most 4 x 2048 x (8 + 8) B = 128 KB (max_pos = n)
+constexpr int kListMetricsMaxN = 2048;
 
 struct ListMetricArgs {
   const float* pred;        // [N, n]
@@ -218,25 +225,30 @@ __global__ __launch_bounds__(kBlock) void list_metrics_kernel(ListMetricArgs a) 
     key[c] = valid ? (double)x[c] - (c < a.max_pos ? 1e-6 : 0.0) : -__builtin_inf();
   }
   __builtin_amdgcn_wave_barrier();   // (ds operations of one wave complete in order)
-  // ranks of the positives among the valid entries
+  // ranks of the positives among all n columns (masked ones are -inf keys)
   for (int i = 0; i < p; ++i) {
     const double ki = key[i];
+    const bool nan_i = ki != ki;
     int c = 0;
     for (int j = lane; j < a.n; j += 64) {
-      const bool valid = j < p || (j >= a.max_pos && j < a.max_pos + q);
       const double kj = key[j];
-      c += (valid && (kj > ki || (kj == ki && j < i))) ? 1 : 0;
+      const bool nan_j = kj != kj;
+      c += (nan_i ? (!nan_j || j < i) : (!nan_j && (kj > ki || (kj == ki && j < i)))) ? 1 : 0;
     }
     c = wave_sum_i32(c);
     if (lane == 0) rnk[i] = c;
   }
   __builtin_amdgcn_wave_barrier();
+  const int whole = p + q;   // the reference's truncation of the ranked labels
+  int m = 0;                 // positives that survive it
   for (int i = lane; i < p; i += 64) {     // positives ranked at or before positive i (itself included)
     int c = 0;
     const int ri = rnk[i];
     for (int t = 0; t < p; ++t) c += rnk[t] <= ri ? 1 : 0;
     cnt[i] = c;
+    m += ri < whole ? 1 : 0;
   }
+  m = wave_sum_i32(m);
   __builtin_amdgcn_wave_barrier();
   double* out = a.out + row * 3 * a.n_k;
   for (int kk = 0; kk < a.n_k; ++kk) {
@@ -245,18 +257,18 @@ __global__ __launch_bounds__(kBlock) void list_metrics_kernel(ListMetricArgs a) 
     int hit = 0;
     for (int i = lane; i < p; i += 64) {
       const int ri = rnk[i];
-      if (ri < k) {
+      if (ri < k && ri < whole) {
         dcg += 1.0 / log2((double)(ri + 2));
         ap += (double)cnt[i] / (double)(ri + 1);
         hit = 1;
       }
     }
-    const int ideal = p < k ? p : k;
+    const int ideal = m < k ? m : k;
     for (int t = lane; t < ideal; t += 64) idcg += 1.0 / log2((double)(t + 2));
     dcg = wave_sum_f64(dcg); ap = wave_sum_f64(ap); idcg = wave_sum_f64(idcg);
     hit = wave_sum_i32(hit);
     if (lane == 0) {
-      const int cap = p < 1 ? 1 : (p > k ? k : p);
+      const int cap = m < 1 ? 1 : (m > k ? k : m);
       out[0 * a.n_k + kk] = dcg / (idcg == 0.0 ? 1.0 : idcg);
       out[1 * a.n_k + kk] = ap / (double)cap;
       out[2 * a.n_k + kk] = hit > 0 ? 1.0 : 0.0;

@@ -224,6 +224,51 @@ def test_list_metrics_on_the_device_ties_empty_groups_and_wide_lists(cuda):
     assert not engine.list_metrics_supported(4096, 20, 3) and not engine.list_metrics_supported(40, 20, 17)
 
 
+def test_list_metrics_on_the_device_with_nan_and_minus_inf_scores(cuda):
+    """NaN and -inf in VALID positive and negative slots, against the mirror's numpy evaluate_method at 1e-12: the reference's stable
+    sort of -score puts NaN last (behind the masked columns, which it sorts as -inf), so a NaN positive can rank at or beyond
+    pos + neg and drop out of the truncated labels -- out of DCG, HR, MAP and the ideal DCG alike.  A valid -inf ties with the
+    masked columns; the column order decides, as in the stable sort.  Garbage (NaN, inf) in the unused columns is never read."""
+    from helpers.ImpressionRunner import ImpressionRunner
+    rng = np.random.default_rng(11)
+    vals = np.array([np.nan, -np.inf, np.inf, -1.0, 0.0, 0.5], dtype=np.float32)
+    for N, mp, mn, topk, with_pos, weights in ((300, 6, 7, [1, 2, 3, 5, 10, 13], True, [.3, .2, .05, .15, .15, .15]),
+                                               (130, 1, 9, [1, 3, 10], False, [.25, .25, .1, .1, .2, .1]),
+                                               (70, 20, 44, [1, 5, 20, 64], True, [.5, .1, 0, .1, .2, .1]),
+                                               (65, 4, 0, [1, 4], True, [.4, .3, 0, .1, .1, .1])):
+        n = mp + mn
+        pred = rng.choice(vals, size=(N, n), p=weights)
+        pos = rng.integers(0, mp + 2, size=N) if with_pos else None
+        neg = rng.integers(0, mn + 2, size=N)
+        pred[0, :] = np.nan                      # every key NaN: column order alone
+        pred[1, :mp] = np.nan
+        pred[1, mp:] = -np.inf                   # NaN positives behind valid -inf negatives and the masked columns
+        pred[2, :] = -np.inf                     # all ties at -inf
+        if with_pos:
+            pos[:3] = mp
+            neg[:3] = mn
+        p_eff = np.minimum(pos, mp) if pos is not None else np.full(N, min(1, mp))
+        col = np.arange(n)[None, :]
+        keep = (col < p_eff[:, None]) | ((col >= mp) & (col < mp + np.minimum(neg, mn)[:, None]))
+        masked = np.where(keep, pred, -np.inf)
+        want = ImpressionRunner.evaluate_method(masked, topk, [], False, neg, mp, pos, ret_all=1)
+        # the case the issue is about must occur: a NaN positive truncated away from a row that has a non-NaN positive too
+        m64 = masked.astype(np.float64)
+        m64[:, :mp] -= 1e-6
+        order = np.argsort(-m64, axis=1, kind="mergesort")
+        place = np.argsort(order, axis=1)
+        length = p_eff + np.minimum(neg, mn)
+        nan_pos = keep & np.isnan(pred) & (col < mp)
+        assert (nan_pos & (place >= length[:, None])).any(axis=1).any() or mn == 0
+        dirty = np.where(keep, pred, rng.choice(np.array([np.nan, np.inf, 1e30], dtype=np.float32), size=(N, n)))
+        per_row, mean = _device_metrics(dirty, pos, neg, mp, topk, cuda)
+        for m, name in enumerate(("NDCG", "MAP", "HR")):
+            for j, k in enumerate(topk):
+                w = want["%s@%d" % (name, k)]
+                assert np.allclose(per_row[:, m, j], w, atol=1e-12, rtol=0), (N, mp, mn, name, k, np.flatnonzero(np.abs(per_row[:, m, j] - w) > 1e-12)[:8])
+                assert abs(mean[m, j] - w.mean()) < 1e-12
+
+
 def test_impression_runner_evaluates_on_the_device(tmp_path, cuda, monkeypatch):
     """ImpressionRunner.evaluate: the predictions stay on the device (no BaseRunner.predict, i.e. no [N, n] D2H copy) and the
     result equals the numpy route on the same predictions, means and per-row values (all=1)"""

@@ -165,6 +165,68 @@ def test_full_catalogue_rank_vs_oracle(d, cuda, eng):
         assert (np.abs(rank0.cpu().numpy() - want0) <= near).all()
 
 
+@pytest.mark.parametrize("d", [32, 64])
+def test_full_catalogue_and_target_rank_with_nan_and_exactly_tied_scores(d, cuda, eng):
+    """--test_all with NaN scores: a NaN in a user's vector or in the target's row makes the target score NaN, and the reference's
+    (pred >= pred[:, 0]).sum() is then 0; an item scoring NaN never counts; items whose rows copy the target's tie with it and
+    count.  Integer-valued embeddings make every score exact in any summation order, so rc_full_catalogue_rank, rc_target_rank on
+    the materialised candidate matrix and the reference formula agree exactly; rank_metrics on those ranks equals the reference's
+    own BaseRunner.evaluate_method (NDCG = inf at rank 0, as there)."""
+    import os
+    import sys
+    from conftest import ROOT
+    plugin = os.path.join(ROOT, "rechorus_amd", "rechorus")
+    if plugin not in sys.path:
+        sys.path.insert(0, plugin)
+    from helpers.BaseRunner import BaseRunner
+    rng = np.random.default_rng(77 + d)
+    n_items, N, n_users = 389, 133, 41
+    I = rng.integers(-2, 3, size=(n_items, d)).astype(np.float32)
+    Uv = rng.integers(-2, 3, size=(N, d)).astype(np.float32)
+    users = rng.integers(0, n_users, size=N)
+    targets = rng.integers(1, n_items, size=N)
+    nan_items = np.array([5, 17, 200, n_items - 1])
+    I[nan_items, rng.integers(0, d, size=nan_items.size)] = np.nan        # these items score NaN for every user
+    targets[[0, 9, 50]] = nan_items[:3]                                    # NaN target from the target's row
+    Uv[[3, 4, 64, N - 1], [0, d // 2, d - 1, 7]] = np.nan                  # NaN target from the user's vector (and all its items)
+    for r in range(10, N, 7):                                              # exact copies of the target's row tie with it
+        I[(targets[r] + 31) % (n_items - 1) + 1] = I[targets[r]]
+    sets, _, _ = make_clicked(n_users, n_items, rng)
+    for r in range(N):
+        sets[users[r]].add(int(targets[r]))
+        if r % 3 == 0:      # clicked NaN items and clicked copies of the target are masked, so they do not count either
+            sets[users[r]].update({int(nan_items[3]), int((targets[r] + 31) % (n_items - 1) + 1)})
+    ptr = np.zeros(n_users + 1, dtype=np.int64)
+    flat = []
+    for u in range(n_users):
+        flat.extend(sorted(sets[u]))
+        ptr[u + 1] = len(flat)
+    flat = np.array(flat, dtype=np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        want = S.full_catalogue_rank(Uv, I, users, targets, sets)          # float64 scores, exact here
+        cand = np.concatenate([targets[:, None], np.broadcast_to(np.arange(1, n_items), (N, n_items - 1))], axis=1)
+        pred = np.einsum("nd,ncd->nc", Uv.astype(np.float64), I[cand].astype(np.float64))
+        for r in range(N):
+            seen = np.array([c for c in sets[users[r]] if 1 <= c < n_items], dtype=np.int64)
+            pred[r, seen] = -np.inf
+        assert np.array_equal((pred >= pred[:, :1]).sum(axis=1), want)
+    assert (want == 0).sum() >= 7 and np.isnan(pred[:, 0]).sum() == (want == 0).sum()
+    rank, tscore = eng.full_catalogue_rank(dev(Uv, cuda), dev(I, cuda), dev(users, cuda), dev(targets, cuda), dev(ptr, cuda), dev(flat, cuda))
+    assert np.array_equal(rank.cpu().numpy().astype(np.int64), want)
+    assert np.array_equal(np.isnan(tscore.cpu().numpy()), np.isnan(pred[:, 0]))
+    rank_t = eng.target_rank(dev(pred.astype(np.float32), cuda))
+    assert np.array_equal(rank_t.cpu().numpy().astype(np.int64), want)
+    topk, metrics = [1, 5, 10, 50], ["HR", "NDCG"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ref = BaseRunner.evaluate_method(pred, topk, metrics)
+    for r in (rank, rank_t):
+        got = eng.rank_metrics(r, topk, metrics)
+        assert got.keys() == ref.keys()
+        for k in got:
+            assert got[k] == ref[k] or abs(got[k] - ref[k]) < 1e-12, (k, got[k], ref[k])
+    assert np.isinf(ref["NDCG@1"])
+
+
 def test_full_catalogue_scores_are_consistent_between_mfma_and_scalar_chain(cuda, eng):
     """items that are exact copies of the target row must tie with it (score >= target) in the MFMA
     kernel: the scalar chain used for target / clicked scores restates the MFMA summation order"""
