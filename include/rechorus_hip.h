@@ -1053,6 +1053,44 @@ int rc_bench_mix(float* table, int d, const int64_t* ids, int64_t n_occ, float w
  * prints it as roofline.box_mfma_tflops beside the datasheet's 157.3 TFLOP/s for the MFMA-bound legs.  sink_dev: 4 device bytes. */
 int rc_bench_mfma(int iters, float* sink_dev, float* tflops_out, rc_stream_t stream);
 
+/* ---- LightGCN graph propagation (models/general/LightGCN.py) ------------------------------------------------------------------
+ * The normalised adjacency D^-1/2 A D^-1/2 of the user-item graph (LightGCN.py:23-53, selfloop_flag=False) as CSR over
+ * N = n_users + n_items nodes, users first, plus a propagation plan built once on the host (rechorus_amd/lgcn.py): work items
+ * (destination row, first edge, edge count, partial slot or -1), longest first; rows longer than the plan's chunk length are
+ * split into chunks whose partials (slots long_part_ptr[j] .. long_part_ptr[j+1] of long row j, in chunk order) are added by a
+ * second pass.  The matrix must be exactly symmetric (the backward pass multiplies by A, not A^T).  Host struct, device arrays.
+ * No float atomics: every sum has a fixed order, results are bitwise reproducible run to run.                                   */
+typedef struct rc_lgcn_graph {
+  int64_t n_users, n_items, nnz;
+  const int64_t* indptr;         /* [N + 1] */
+  const int32_t* indices;        /* [nnz]   */
+  const float* values;           /* [nnz]   */
+  int64_t n_work;
+  const int32_t* work_row;       /* [n_work] */
+  const int64_t* work_beg;       /* [n_work] */
+  const int32_t* work_len;       /* [n_work] */
+  const int32_t* work_part;      /* [n_work], -1: the item is a whole row */
+  int64_t n_long;
+  const int32_t* long_row;       /* [n_long] */
+  const int32_t* long_part_ptr;  /* [n_long + 1] */
+  int64_t n_parts;
+} rc_lgcn_graph;
+/* RC_OK when d % 4 == 0, 4 <= d <= 256, 0 <= n_layers <= 8, N < 2^31 and nnz < 2^31, else RC_ERR_UNSUPPORTED with the reason in
+ * rc_last_error_string() (host logic, no GPU needed); the propagation entry points check the same envelope themselves.           */
+int rc_lgcn_check_shape(int d, int n_layers, int64_t n_nodes, int64_t nnz);
+/* LGCNEncoder.forward's propagation (LightGCN.py:137-151: torch.cat of the two tables, L torch.sparse.mm, stack, mean):
+ * out [N, d] = mean(E_0, A E_0, ..., A^L E_0), E_0 read straight from user_emb [n_users, d] / item_emb [n_items, d].
+ * L products (+ the chunk-combine pass where the plan has long rows); each layer's epilogue keeps the running sum in `out`.
+ * buf_a, buf_b [N, d]: ping-pong layers (buf_a needed from L = 2, buf_b from L = 3); partials [n_parts, d].                   */
+int rc_lgcn_propagate_fwd(const rc_lgcn_graph* g, const float* user_emb, const float* item_emb, int d, int n_layers,
+                          float* buf_a, float* buf_b, float* partials, float* out, rc_stream_t stream);
+/* its autograd (SparseMM / Stack / Mean backward of LightGCN.py:143-151): given the gradients grad_user [n_users, d],
+ * grad_item [n_items, d] of the two halves of `out`, writes dE_0 = sum_{l=0..L} A^l G / (L+1) in Horner form (L products with a
+ * "+ G / (L+1)" epilogue) into grad_user_emb / grad_item_emb.  buf_a needed from L = 1, buf_b from L = 2.                      */
+int rc_lgcn_propagate_bwd(const rc_lgcn_graph* g, const float* grad_user, const float* grad_item, int d, int n_layers,
+                          float* buf_a, float* buf_b, float* partials, float* grad_user_emb, float* grad_item_emb,
+                          rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

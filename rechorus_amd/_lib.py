@@ -57,6 +57,19 @@ class StepTicket(C.Structure):
     ]
 
 
+class LgcnGraph(C.Structure):
+    """struct rc_lgcn_graph: the normalised adjacency (CSR) and its propagation plan; device pointers"""
+    _fields_ = [
+        ("n_users", C.c_int64), ("n_items", C.c_int64), ("nnz", C.c_int64),
+        ("indptr", C.c_void_p), ("indices", C.c_void_p), ("values", C.c_void_p),
+        ("n_work", C.c_int64),
+        ("work_row", C.c_void_p), ("work_beg", C.c_void_p), ("work_len", C.c_void_p), ("work_part", C.c_void_p),
+        ("n_long", C.c_int64),
+        ("long_row", C.c_void_p), ("long_part_ptr", C.c_void_p),
+        ("n_parts", C.c_int64),
+    ]
+
+
 _p = C.c_void_p
 _i = C.c_int
 _u64 = C.c_uint64
@@ -65,6 +78,7 @@ _i64 = C.c_int64
 _f = C.c_float
 _sz = C.c_size_t
 _hp = C.POINTER(OptHyper)
+_gp = C.POINTER(LgcnGraph)
 
 # name -> (restype, argtypes); must list every symbol include/rechorus_hip.h declares
 SIGNATURES = {
@@ -222,6 +236,9 @@ SIGNATURES = {
     "rc_bucket_bitmap_bytes": (_sz, [_i64]),
     "rc_bucket_multi_bitmap": (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
     "rc_bprmf_fwd_bwd_update_bitmap": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _hp, _p, _p, _p, _p, _p]),
+    "rc_lgcn_check_shape": (_i, [_i, _i, _i64, _i64]),
+    "rc_lgcn_propagate_fwd": (_i, [_gp, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "rc_lgcn_propagate_bwd": (_i, [_gp, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

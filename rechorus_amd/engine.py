@@ -2484,3 +2484,52 @@ def owner_backward(I, mI, vI, Uall, t32, rows, g, single, n_tuples, hyper):
               C.byref(hyper) if hyper is not None else None, _ptr(pug, f32, "pug"),
               C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
     return pug
+
+
+# ---- LightGCN graph propagation (models/general/LightGCN.py:137-151) ---------------------------------------------------------
+
+def lgcn_check_shape(d, n_layers, n_nodes=0, nnz=0):
+    """rc_lgcn_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 0 <= n_layers <= 8, N < 2^31, nnz < 2^31; raises ValueError
+    with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_lgcn_check_shape(int(d), int(n_layers), int(n_nodes), int(nnz)) != _lib.RC_OK:
+        raise ValueError("LightGCN on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def _lgcn_check(graph, d, n_layers):
+    lgcn_check_shape(d, n_layers, graph.N, graph.nnz)
+
+
+def lgcn_propagate_fwd(graph, user_emb, item_emb, n_layers, out=None):
+    """mean(E_0, A E_0, ..., A^L E_0) over the graph (rechorus_amd.lgcn.LgcnGraph), E_0 = (user_emb | item_emb) read in place
+    -> out [N, d] (the graph's persistent output buffer when out is the string "persistent", a new tensor when None)"""
+    d = user_emb.shape[1]
+    _lgcn_check(graph, d, n_layers)
+    if user_emb.shape != (graph.n_users, d) or item_emb.shape != (graph.n_items, d):
+        raise ValueError(f"lgcn_propagate_fwd: tables {tuple(user_emb.shape)} / {tuple(item_emb.shape)} do not match the graph "
+                         f"({graph.n_users} users, {graph.n_items} items)")
+    buf_a, buf_b, parts, persistent = graph.buffers(d)
+    if isinstance(out, str) and out == "persistent":
+        out = persistent
+    elif out is None:
+        out = torch.empty((graph.N, d), dtype=torch.float32, device=user_emb.device)
+    _lib.call("rc_lgcn_propagate_fwd", C.byref(graph.struct), _ptr(user_emb, torch.float32, "user_emb"),
+              _ptr(item_emb, torch.float32, "item_emb"), d, int(n_layers), _ptr(buf_a, torch.float32, "buf_a"),
+              _ptr(buf_b, torch.float32, "buf_b"), _ptr(parts, torch.float32, "partials"), _ptr(out, torch.float32, "out"), _stream())
+    return out
+
+
+def lgcn_propagate_bwd(graph, grad_user, grad_item, n_layers):
+    """gradient of lgcn_propagate_fwd: sum_l A^l G / (L+1), split into the two tables -> (grad_user_emb, grad_item_emb)"""
+    d = grad_user.shape[1]
+    _lgcn_check(graph, d, n_layers)
+    if grad_user.shape != (graph.n_users, d) or grad_item.shape != (graph.n_items, d):
+        raise ValueError("lgcn_propagate_bwd: gradient shapes do not match the graph")
+    buf_a, buf_b, parts, _ = graph.buffers(d)
+    gu = torch.empty((graph.n_users, d), dtype=torch.float32, device=grad_user.device)
+    gi = torch.empty((graph.n_items, d), dtype=torch.float32, device=grad_user.device)
+    _lib.call("rc_lgcn_propagate_bwd", C.byref(graph.struct), _ptr(grad_user, torch.float32, "grad_user"),
+              _ptr(grad_item, torch.float32, "grad_item"), d, int(n_layers), _ptr(buf_a, torch.float32, "buf_a"),
+              _ptr(buf_b, torch.float32, "buf_b"), _ptr(parts, torch.float32, "partials"), _ptr(gu, torch.float32, "grad_user_emb"),
+              _ptr(gi, torch.float32, "grad_item_emb"), _stream())
+    return gu, gi

@@ -121,6 +121,43 @@ def bprmf_scores(U, I, uid, iid):
     return _BprmfScoreFn.apply(U, I, uid.contiguous(), iid.contiguous())
 
 
+def table_rows(W, ids):
+    """W[ids] with an autograd that sums the rows' gradients into a dense [n_rows, d] tensor (HipEmbedding's lookup on a table
+    that is not a module's Parameter, e.g. LightGCN's propagated tables)"""
+    return _EmbeddingFn.apply(W, ids.contiguous())
+
+
+class _LgcnPropagateFn(torch.autograd.Function):
+    """LGCNEncoder.forward's propagation (models/general/LightGCN.py:137-151): mean(E_0, A E_0, ..., A^L E_0), E_0 = the two
+    tables; backward sum_l A^l G / (L+1) (A symmetric).  Both directions are rc_lgcn_propagate_fwd/bwd on the graph's plan."""
+
+    @staticmethod
+    def forward(ctx, user_emb, item_emb, graph, n_layers):
+        ctx.graph, ctx.n_layers = graph, n_layers
+        # the graph's persistent output buffer: a captured training step replays on the same memory
+        out = engine.lgcn_propagate_fwd(graph, user_emb.detach(), item_emb.detach(), n_layers, out="persistent")
+        return out[:graph.n_users], out[graph.n_users:]
+
+    @staticmethod
+    def backward(ctx, g_user, g_item):
+        graph = ctx.graph
+        if g_user is None and g_item is None:
+            return None, None, None, None
+        ref = g_user if g_user is not None else g_item
+        dim = ref.shape[1]
+        if g_user is None:
+            g_user = torch.zeros((graph.n_users, dim), dtype=torch.float32, device=ref.device)
+        if g_item is None:
+            g_item = torch.zeros((graph.n_items, dim), dtype=torch.float32, device=ref.device)
+        gu, gi = engine.lgcn_propagate_bwd(graph, g_user.contiguous(), g_item.contiguous(), ctx.n_layers)
+        return gu, gi, None, None
+
+
+def lgcn_propagate(user_emb, item_emb, graph, n_layers):
+    """(propagated user table, propagated item table): the two halves of one [N, d] buffer, each a contiguous view"""
+    return _LgcnPropagateFn.apply(user_emb, item_emb, graph, int(n_layers))
+
+
 class _BprLossFn(torch.autograd.Function):
     """GeneralModel.loss (models/BaseModel.py:182-185), closed-form backward."""
 
