@@ -6,7 +6,7 @@
 // sequence on one workgroup per CU (matrix cores busy 7 % of the time); here every phase is one launch over
 // ~100 K rows, bound by HBM streaming of [R, d] activations (26 MB each at B = 4096, mean length 25).
 //
-// Same arithmetic as sasrec.hip: fp32 v_mfma_f32_32x32x2_f32 for every contraction, LayerNorm with biased
+// Same arithmetic as sasrec.hip: fp32 MFMA (32x32x2, 16x16x4) for every contraction, LayerNorm with biased
 // variance and eps 1e-5, causal mask only, position id = length - index, no attention output projection,
 // dropout 0.  Activations needed by the backward pass (layer input, q, k, v, xhat1, y1, relu hidden, xhat2,
 // the two rstd vectors) are SAVED by the forward pass -- they are its natural intermediates -- instead of being
@@ -82,83 +82,22 @@ __global__ __launch_bounds__(kBlock) void sb_embed_kernel(const float* __restric
   }
 }
 
-// ---- Y_w = epilogue(X . W_w^T)  or  X . W_w  over the row space, W_w resident in LDS ---------------------
+// ---- arguments of the row-space projections (sb_qkv16_kernel, sb_sum3_16_kernel below) ----------------------------
 
+// Y_w = X . W_w^T + b_w
 struct SbLinArgs {
   const float* X;       // [R, D]
   const float* W[3];    // nn.Linear weights [out, in]
   const float* bias[3]; // may be null
   float* Y[3];          // [R, D]
-  const float* res;     // optional: Y += res            (same row space)
-  const float* mask;    // optional: Y = mask > 0 ? Y : 0 (ReLU backward)
+  const float* res;     // res, mask, relu: read by no kernel, they keep the argument layout sb_qkv16_kernel is compiled with
+  const float* mask;
   int relu;
   const int32_t* off;
   int B;
 };
 
-template <int D, int NW, bool TRANS>
-__global__ __launch_bounds__(kBlock) void sb_linear_kernel(SbLinArgs a) {
-  constexpr int SD = D + 1;
-  extern __shared__ float lds[];
-  float* Ws = lds;                    // [NW][D][SD]
-  float* Xs = lds + NW * D * SD;      // [kSbTile][SD]
-  // biases live in LDS too: a global load behind the epilogue's global stores waits for those stores (gfx950 counts
-  // loads and stores in one in-order vmcnt) -- 16 serialised load / store round trips per lane and block otherwise
-  float* Bs = Xs + kSbTile * SD;      // [NW][D]
-  for (int w = 0; w < NW; ++w) {
-    for (int idx = threadIdx.x; idx < D * D; idx += kBlock) Ws[w * D * SD + (idx / D) * SD + idx % D] = a.W[w][idx];
-    for (int idx = threadIdx.x; idx < D; idx += kBlock) Bs[w * D + idx] = a.bias[w] ? a.bias[w][idx] : 0.f;
-  }
-  const int R = a.off[a.B];
-  const int tiles = (R + kSbTile - 1) / kSbTile;
-  // the next tile's rows are requested while the current tile is multiplied: each thread holds its
-  // kSbTile * D / 4 / 256 float4 of the tile in registers between the two barriers
-  constexpr int PF = kSbTile * (D / 4) / kBlock;
-  float4 pf[PF];
-  auto fetch = [&](int tile) {
-    const int r0 = tile * kSbTile;
-    const int m = min(kSbTile, R - r0);
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int idx = threadIdx.x + q * kBlock, i = idx / (D / 4), c = idx % (D / 4);
-      pf[q] = i < m ? reinterpret_cast<const float4*>(a.X)[(size_t)(r0 + i) * (D / 4) + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  if ((int)blockIdx.x < tiles) fetch(blockIdx.x);
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int r0 = tile * kSbTile;
-    const int m = min(kSbTile, R - r0);
-    __syncthreads();  // previous tile's readers are done (and the weights are in place)
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int idx = threadIdx.x + q * kBlock, i = idx / (D / 4), c = idx % (D / 4);
-      float* d = Xs + i * SD + 4 * c;
-      d[0] = pf[q].x; d[1] = pf[q].y; d[2] = pf[q].z; d[3] = pf[q].w;
-    }
-    __syncthreads();
-    if (tile + (int)gridDim.x < tiles) fetch(tile + gridDim.x);
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float* Wl = Ws + w * D * SD;
-      const MatB mb = TRANS ? MatB{Wl, SD, 1} : MatB{Wl, 1, SD};  // dx = dy . W   |   y = x . W^T
-      const float* bias = Bs + w * D;
-      float* Y = a.Y[w];
-      sas_mm(MatA{Xs, SD, 1}, mb, m, D, D, false, [&](int i, int j, float v) {
-        const size_t e = (size_t)(r0 + i) * D + j;
-        v += bias[j];
-        if (a.relu) v = fmaxf(v, 0.f);
-        if (a.mask) v = a.mask[e] > 0.f ? v : 0.f;
-        if (a.res) v += a.res[e];
-        Y[e] = v;
-      });
-    }
-  }
-}
-
-// Y = res + X_0 . W_0 + X_1 . W_1 + X_2 . W_2  (dX of the three projections: dZ1 + dQ Wq + dK Wk + dV Wv) in one
-// pass: the accumulators of a wave's 32x32 output block stay in registers across the three inputs, whose tiles
-// are staged one after the other (next one prefetched) -- instead of three launches that each re-read and
-// re-write the [R, D] running sum.
+// Y = res + X_0 . W_0 + X_1 . W_1 + X_2 . W_2: dX of the three projections, dZ1 + dQ Wq + dK Wk + dV Wv
 struct SbSum3Args {
   const float* X[3];
   const float* W[3];  // [out, in]: the product uses W as is (dx = dy . W)
@@ -168,102 +107,14 @@ struct SbSum3Args {
   int B;
 };
 
-template <int D>
-__global__ __launch_bounds__(kBlock) void sb_linear3_sum_kernel(SbSum3Args a) {
-  constexpr int SD = D + 1, NRB = kSbTile / 32, NCB = D / 32, NQ = NRB * NCB;  // NQ <= 4: one block per wave
-  extern __shared__ float lds[];
-  float* Ws = lds;                // [3][D][SD]
-  float* Xs = lds + 3 * D * SD;   // [kSbTile][SD]
-  for (int w = 0; w < 3; ++w)
-    for (int idx = threadIdx.x; idx < D * D; idx += kBlock) Ws[w * D * SD + (idx / D) * SD + idx % D] = a.W[w][idx];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kh = lane >> 5;
-  const int R = a.off[a.B];
-  const int tiles = (R + kSbTile - 1) / kSbTile;
-  const int my_tiles = (int)blockIdx.x < tiles ? (tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
-  constexpr int PF = kSbTile * (D / 4) / kBlock;
-  float4 pf[PF];
-  auto fetch = [&](int step) {  // step = (tile ordinal, input w)
-    const int tile = blockIdx.x + (step / 3) * gridDim.x, w = step % 3;
-    const int r0 = tile * kSbTile;
-    const int m = min(kSbTile, R - r0);
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int idx = threadIdx.x + q * kBlock, i = idx / (D / 4), c = idx % (D / 4);
-      pf[q] = i < m ? reinterpret_cast<const float4*>(a.X[w])[(size_t)(r0 + i) * (D / 4) + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  if (my_tiles > 0) fetch(0);
-  const int rb = wave % NRB, cb = wave / NRB;
-  sas_f32x16 acc;
-  for (int step = 0; step < 3 * my_tiles; ++step) {
-    const int w = step % 3;
-    if (w == 0)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int idx = threadIdx.x + q * kBlock, i = idx / (D / 4), c = idx % (D / 4);
-      float* d = Xs + i * SD + 4 * c;
-      d[0] = pf[q].x; d[1] = pf[q].y; d[2] = pf[q].z; d[3] = pf[q].w;
-    }
-    __syncthreads();
-    if (step + 1 < 3 * my_tiles) fetch(step + 1);
-    if (wave < NQ) {  // wave-uniform
-      const float* ap = Xs + (rb * 32 + (lane & 31)) * SD + kh;                 // a(i, k) = X[i][k]
-      const float* bp = Ws + w * D * SD + kh * SD + cb * 32 + (lane & 31);      // b(k, j) = W[k][j]
-      // the residual values of this block are requested BEFORE the last product (and all of them before the first
-      // store): res may alias Y, so a load behind a store of the epilogue would wait for that store -- 16 serialised
-      // round trips per lane and tile in round 2's `Y[e] = acc + res[e]` loop
-      float rv[16];
-      if (w == 2) {
-        const int tile = blockIdx.x + (step / 3) * gridDim.x;
-        const int r0 = tile * kSbTile;
-        const int m = min(kSbTile, R - r0);
-        const int j = cb * 32 + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-          rv[r] = i < m ? a.res[(size_t)(r0 + i) * D + j] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int k0 = 0; k0 < D; k0 += 32) {
-        float av[16], bv[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          av[t] = ap[k0 + 2 * t];
-          bv[t] = bp[(k0 + 2 * t) * SD];
-        }
-#pragma unroll
-        for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc, 0, 0, 0);
-      }
-      if (w == 2) {
-        const int tile = blockIdx.x + (step / 3) * gridDim.x;
-        const int r0 = tile * kSbTile;
-        const int m = min(kSbTile, R - r0);
-        const int j = cb * 32 + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-          if (i < m) {
-            const size_t e = (size_t)(r0 + i) * D + j;
-            a.Y[e] = acc[r] + rv[r];
-          }
-        }
-      }
-    }
-  }
-}
-
 // ---- the two projection kernels on 16 x 16 x 4 tiles, operands straight from global memory ----------------------
 // Y^T = W X^T: a lane (i, g) = (lane & 15, lane >> 4) holds its row's columns 16 c + 4 g .. + 3 as ONE float4 per chunk --
 // the B operand of every MFMA of the tile -- and receives Y[row i][16 n + 4 g .. + 3] as the accumulator: one float4
 // store.  The weights wait in LDS in a layout whose ds_read_b128 is the A operand of four MFMAs (row stride D + 4: the
 // sixteen lanes of a group hit sixteen different 4-bank groups).  No row tile in LDS, no barrier after the weights are
 // staged: a wave streams its 16-row tiles on its own, the other waves of its SIMD cover its loads.  Workgroups of up
-// to 16 waves stage the weights once per CU.  (The 32 x 32 x 2 kernels above staged every 64-row tile through LDS with
-// scalar ds_write / ds_read and two barriers: 51 us for the QKV projection of 104 K rows whose MFMA floor is 16 us.)
+// to 16 waves stage the weights once per CU.  (The 32 x 32 x 2 kernels these replaced staged every 64-row tile through LDS
+// with scalar ds_write / ds_read and two barriers: 51 us for the QKV projection of 104 K rows whose MFMA floor is 16 us.)
 constexpr int kSb16MaxWaves = 16;
 
 template <int D>
@@ -412,19 +263,10 @@ __global__ __launch_bounds__(64 * kSb16MaxWaves) void sb_sum3_16_kernel(SbSum3Ar
   }
 }
 
-// RC_SAS_ROWS16=0: the 32 x 32 x 2 projection kernels with LDS row tiles (rounds 1-3), for A/B timing and the equivalence test
-static bool sb_rows16() {
-  const char* v = getenv("RC_SAS_ROWS16");
-  return !(v && v[0] == '0');
-}
 // launch geometry of the 16-row-tile kernels: 16 waves per workgroup, one workgroup per CU once there are tiles for all of them
 static void sb_rows16_geometry(int64_t rmax, int* grid, int* block) {
   const int64_t tiles = (rmax + 15) / 16;
-  int nw = tiles >= 256 * kSb16MaxWaves ? kSb16MaxWaves : 4;
-  if (const char* v = getenv("RC_SB16_WAVES")) {   // experiment switch: 4 / 8 / 16 waves per workgroup
-    const int q = atoi(v);
-    if (q == 4 || q == 8 || q == 16) nw = q;
-  }
+  const int nw = tiles >= 256 * kSb16MaxWaves ? kSb16MaxWaves : 4;
   int64_t gr = (tiles + nw - 1) / nw;
   const int64_t cap = 256 * (int64_t)(kSb16MaxWaves / nw < 3 ? kSb16MaxWaves / nw : 3);
   if (gr > cap) gr = cap;
@@ -432,14 +274,15 @@ static void sb_rows16_geometry(int64_t rmax, int* grid, int* block) {
   *block = 64 * nw;
 }
 
-// ---- LayerNorm over rows: z = A (+ Bv) -> xhat, rstd, y = w * xhat + b ----------------------------------
+// ---- dropout of the residual branches ---------------------------------------------------------------------
 
 // Training-mode dropout of the two residual branches of a TransformerLayer (utils/layers.py:104,110 dropout1 on the
 // attention context, :114,117 dropout2 on the FFN output; both feed `layer_norm(drop(branch) + residual)`): the mask
 // is never stored.  Element (compact row r, feature f) of site s = 2 * layer + {0: dropout1, 1: dropout2} is dropped
 // iff word (f & 3) of Philox4x32-10(key = seed, counter = (r, s * D/4 + (f >> 2))) < thresh; kept values are scaled by
-// 1 / (1 - p).  The LayerNorm kernels regenerate it: forward masks the branch before the residual add, backward
-// emits the masked gradient for the branch next to the unmasked one for the residual path.  seed == nullptr: off.
+// 1 / (1 - p).  The block kernels regenerate it: sb_block16_fwd_kernel masks the branch before the residual add,
+// sb_block_bwd_kernel emits the masked gradient for the branch next to the unmasked one for the residual path.
+// seed == nullptr: off.
 struct SbDrop {
   const uint64_t* seed;   // device memory: a captured step replays with a fresh mask once the host bumps it
   uint32_t thresh;
@@ -455,93 +298,12 @@ __device__ __forceinline__ float4 sb_drop_keep4(const SbDrop& dr, uint64_t seed,
                      wd[2] < dr.thresh ? 0.f : dr.scale, wd[3] < dr.thresh ? 0.f : dr.scale);
 }
 
-template <int D>
-__global__ __launch_bounds__(kBlock) void sb_ln_fwd_kernel(const float* __restrict__ A, const float* __restrict__ Bv,
-                                                           const float* __restrict__ w, const float* __restrict__ bb,
-                                                           const int32_t* __restrict__ off, int B,
-                                                           float* __restrict__ xhat, float* __restrict__ rstd,
-                                                           float* __restrict__ y, SbDrop dr) {
-  constexpr int LPR = D / 4;
-  const int l = threadIdx.x % LPR;
-  const int R = off[B];
-  const float4 wv = reinterpret_cast<const float4*>(w)[l], bv = reinterpret_cast<const float4*>(bb)[l];
-  const uint64_t seed = dr.seed ? *dr.seed : 0;
-  for (int64_t r = (int64_t)blockIdx.x * (kBlock / LPR) + threadIdx.x / LPR; r < R; r += (int64_t)gridDim.x * (kBlock / LPR)) {
-    float4 z = reinterpret_cast<const float4*>(A)[r * LPR + l];
-    if (dr.seed) {
-      const float4 kp = sb_drop_keep4<D>(dr, seed, r, l);
-      z.x *= kp.x; z.y *= kp.y; z.z *= kp.z; z.w *= kp.w;
-    }
-    if (Bv) {
-      const float4 t = reinterpret_cast<const float4*>(Bv)[r * LPR + l];
-      z.x += t.x; z.y += t.y; z.z += t.z; z.w += t.w;
-    }
-    const float mu = row_allreduce_sum<LPR>((z.x + z.y) + (z.z + z.w)) / D;
-    const float cx = z.x - mu, cy = z.y - mu, cz = z.z - mu, cw = z.w - mu;
-    const float var = row_allreduce_sum<LPR>(fmaf(cx, cx, fmaf(cy, cy, fmaf(cz, cz, cw * cw)))) / D;
-    const float rs = 1.0f / sqrtf(var + kLnEps);
-    const float4 xh = make_float4(cx * rs, cy * rs, cz * rs, cw * rs);
-    reinterpret_cast<float4*>(xhat)[r * LPR + l] = xh;
-    if (l == 0) rstd[r] = rs;
-    reinterpret_cast<float4*>(y)[r * LPR + l] =
-        make_float4(fmaf(xh.x, wv.x, bv.x), fmaf(xh.y, wv.y, bv.y), fmaf(xh.z, wv.z, bv.z), fmaf(xh.w, wv.w, bv.w));
-  }
-}
-
-// LayerNorm backward in place: G holds dY on entry, dZ on exit (with dropout: Gdrop = mask * dZ as well);
-// per-workgroup partial d(weight), d(bias) go to
-// gw[blockIdx][:D], gb[blockIdx][:D] (stride = part_stride floats between workgroups)
-template <int D>
-__global__ __launch_bounds__(kBlock) void sb_ln_bwd_kernel(float* __restrict__ G, const float* __restrict__ xhat,
-                                                           const float* __restrict__ rstd, const float* __restrict__ w,
-                                                           const int32_t* __restrict__ off, int B,
-                                                           float* __restrict__ gw, float* __restrict__ gb,
-                                                           size_t part_stride, SbDrop dr, float* __restrict__ Gdrop) {
-  constexpr int LPR = D / 4, GPB = kBlock / LPR;
-  __shared__ float s_red[2][GPB][D + 1];
-  const int l = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-  const int R = off[B];
-  const float4 wv = reinterpret_cast<const float4*>(w)[l];
-  const uint64_t seed = dr.seed ? *dr.seed : 0;
-  float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), ab = aw;
-  for (int64_t r = (int64_t)blockIdx.x * GPB + grp; r < R; r += (int64_t)gridDim.x * GPB) {
-    const float4 g = reinterpret_cast<const float4*>(G)[r * LPR + l];
-    const float4 xh = reinterpret_cast<const float4*>(xhat)[r * LPR + l];
-    aw.x = fmaf(g.x, xh.x, aw.x); aw.y = fmaf(g.y, xh.y, aw.y); aw.z = fmaf(g.z, xh.z, aw.z); aw.w = fmaf(g.w, xh.w, aw.w);
-    ab.x += g.x; ab.y += g.y; ab.z += g.z; ab.w += g.w;
-    const float4 dx = make_float4(g.x * wv.x, g.y * wv.y, g.z * wv.z, g.w * wv.w);
-    const float m1 = row_allreduce_sum<LPR>((dx.x + dx.y) + (dx.z + dx.w)) / D;
-    const float m2 = row_allreduce_sum<LPR>(fmaf(dx.x, xh.x, fmaf(dx.y, xh.y, fmaf(dx.z, xh.z, dx.w * xh.w)))) / D;
-    const float rs = rstd[r];
-    const float4 dz = make_float4(rs * (dx.x - m1 - xh.x * m2), rs * (dx.y - m1 - xh.y * m2), rs * (dx.z - m1 - xh.z * m2),
-                                  rs * (dx.w - m1 - xh.w * m2));
-    reinterpret_cast<float4*>(G)[r * LPR + l] = dz;
-    if (dr.seed) {  // gradient of the dropped branch: the same mask as the forward pass
-      const float4 kp = sb_drop_keep4<D>(dr, seed, r, l);
-      reinterpret_cast<float4*>(Gdrop)[r * LPR + l] = make_float4(dz.x * kp.x, dz.y * kp.y, dz.z * kp.z, dz.w * kp.w);
-    }
-  }
-  float* sw = &s_red[0][grp][4 * l];
-  float* sb = &s_red[1][grp][4 * l];
-  sw[0] = aw.x; sw[1] = aw.y; sw[2] = aw.z; sw[3] = aw.w;
-  sb[0] = ab.x; sb[1] = ab.y; sb[2] = ab.z; sb[3] = ab.w;
-  __syncthreads();
-  for (int k = threadIdx.x; k < 2 * D; k += kBlock) {  // fixed order over the groups
-    const int which = k / D, c = k % D;
-    float t = 0.f;
-    for (int g2 = 0; g2 < GPB; ++g2) t += s_red[which][g2][c];
-    (which == 0 ? gw : gb)[(size_t)blockIdx.x * part_stride + c] = t;
-  }
-}
-
 // ---- the post-attention half of a TransformerLayer in ONE row-space kernel (utils/layers.py:110-118) -------------------
 //   y1 = LayerNorm1(drop1(ctx) + x);  h = relu(y1 W1^T + b1);  t = h W2^T + b2;  xnext = LayerNorm2(drop2(t) + y1)
-// Round 2 ran this as four launches (LayerNorm, two sb_linear, LayerNorm) that handed [R, D] intermediates to each other
-// through HBM: 11 row passes and four fill / drain phases for 16 + 29 + 29 + 16 us at config 3.  Here a 64-row tile stays in
-// LDS from the first LayerNorm to the second: both weight matrices are resident, the row statistics run one lane-group
-// per row on the staged tile, the two products are the same 32x32x2 MFMA tile loops (identical summation order), and
-// only what the backward pass reads later leaves the CU (xhat1, rstd1, y1, h, xhat2, rstd2) beside the layer output.
-// The next tile's ctx / x rows travel while the current tile is multiplied.
+// Round 2 ran this as four launches (LayerNorm, two projections, LayerNorm) that handed [R, D] intermediates to each other
+// through HBM: 11 row passes and four fill / drain phases for 16 + 29 + 29 + 16 us at config 3.  sb_block16_fwd_kernel (below)
+// keeps a row tile on the CU from the first LayerNorm to the second with both weight matrices resident, and only what the
+// backward pass reads later leaves the CU (xhat1, rstd1, y1, h, xhat2, rstd2) beside the layer output.
 struct SbBlockArgs {
   const float* ctx;   // [R, D] attention output
   const float* x;     // [R, D] layer input (residual)
@@ -557,145 +319,6 @@ struct SbBlockArgs {
   const float *Wv = nullptr, *bv = nullptr;
   int H = 0;
 };
-
-template <int D>
-__global__ __launch_bounds__(kBlock) void sb_block_fwd_kernel(SbBlockArgs a) {
-  constexpr int SD = D + 1, LPR = D / 4, GPB = kBlock / LPR, NPASS = kSbTile / GPB;
-  extern __shared__ float lds[];
-  float* W1s = lds;                       // [D][SD]
-  float* W2s = W1s + D * SD;              // [D][SD]
-  float* Ys = W2s + D * SD;               // [kSbTile][SD]: y1, then (in place) the FFN output t
-  float* Hs = Ys + kSbTile * SD;          // [kSbTile][SD]
-  float* Bs = Hs + kSbTile * SD;          // [2][D]: b1, b2 (a global load behind the epilogues' global stores would wait for them)
-  for (int idx = threadIdx.x; idx < D * D; idx += kBlock) {
-    W1s[(idx / D) * SD + idx % D] = a.W1[idx];
-    W2s[(idx / D) * SD + idx % D] = a.W2[idx];
-  }
-  for (int idx = threadIdx.x; idx < D; idx += kBlock) {
-    Bs[idx] = a.b1[idx];
-    Bs[D + idx] = a.b2[idx];
-  }
-  const int l = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-  const int R = a.off[a.B];
-  const int tiles = (R + kSbTile - 1) / kSbTile;
-  const bool drop = a.dr.seed != nullptr;
-  const uint64_t seed = drop ? *a.dr.seed : 0;
-  SbDrop dr1 = a.dr, dr2 = a.dr;
-  dr2.site = a.dr.site + 1u;
-  const float4 w1v = reinterpret_cast<const float4*>(a.ln1w)[l], b1v = reinterpret_cast<const float4*>(a.ln1b)[l];
-  const float4 w2v = reinterpret_cast<const float4*>(a.ln2w)[l], b2v = reinterpret_cast<const float4*>(a.ln2b)[l];
-  float4 pc[NPASS], px[NPASS];
-  auto fetch = [&](int tile) {
-    const int r0 = tile * kSbTile;
-#pragma unroll
-    for (int q = 0; q < NPASS; ++q) {
-      const int r = r0 + q * GPB + grp;
-      if (r < R) {
-        pc[q] = reinterpret_cast<const float4*>(a.ctx)[(size_t)r * LPR + l];
-        px[q] = reinterpret_cast<const float4*>(a.x)[(size_t)r * LPR + l];
-      }
-    }
-  };
-#ifdef RC_X_TIMING
-  uint64_t tstamp[6] = {0, 0, 0, 0, 0, 0};
-  uint64_t t_prev = wall_clock64();
-  const uint64_t t_begin = t_prev;
-  int n_my_tiles = 0;
-#define RC_STAMP(k) do { const uint64_t t_now = wall_clock64(); tstamp[k] += t_now - t_prev; t_prev = t_now; } while (0)
-#else
-#define RC_STAMP(k)
-#endif
-  if ((int)blockIdx.x < tiles) fetch(blockIdx.x);
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int r0 = tile * kSbTile;
-    const int m = min(kSbTile, R - r0);
-    __syncthreads();  // the previous tile's readers of Ys / Hs are done (and the weights are in place)
-    RC_STAMP(0);
-    // ---- LayerNorm1 on the staged rows: one lane-group per row
-#pragma unroll
-    for (int q = 0; q < NPASS; ++q) {
-      const int i = q * GPB + grp;
-      const int64_t r = (int64_t)r0 + i;
-      float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i < m) {
-        z = pc[q];
-        if (drop) {
-          const float4 kp = sb_drop_keep4<D>(dr1, seed, r, l);
-          z.x *= kp.x; z.y *= kp.y; z.z *= kp.z; z.w *= kp.w;
-        }
-        z.x += px[q].x; z.y += px[q].y; z.z += px[q].z; z.w += px[q].w;
-      }
-      const float mu = row_allreduce_sum<LPR>((z.x + z.y) + (z.z + z.w)) / D;
-      const float cx = z.x - mu, cy = z.y - mu, cz = z.z - mu, cw = z.w - mu;
-      const float var = row_allreduce_sum<LPR>(fmaf(cx, cx, fmaf(cy, cy, fmaf(cz, cz, cw * cw)))) / D;
-      const float rs = 1.0f / sqrtf(var + kLnEps);
-      const float4 xh = make_float4(cx * rs, cy * rs, cz * rs, cw * rs);
-      const float4 y = make_float4(fmaf(xh.x, w1v.x, b1v.x), fmaf(xh.y, w1v.y, b1v.y), fmaf(xh.z, w1v.z, b1v.z), fmaf(xh.w, w1v.w, b1v.w));
-      float* d = Ys + i * SD + 4 * l;
-      d[0] = y.x; d[1] = y.y; d[2] = y.z; d[3] = y.w;   // rows past m: finite filler, their outputs are discarded
-      if (i < m) {
-        reinterpret_cast<float4*>(a.xh1)[(size_t)r * LPR + l] = xh;
-        if (l == 0) a.rstd1[r] = rs;
-        reinterpret_cast<float4*>(a.y1)[(size_t)r * LPR + l] = y;
-      }
-    }
-    __syncthreads();
-    RC_STAMP(1);
-    if (tile + (int)gridDim.x < tiles) fetch(tile + gridDim.x);   // travels during the two products
-    // ---- h = relu(y1 W1^T + b1)
-    sas_mm(MatA{Ys, SD, 1}, MatB{W1s, 1, SD}, m, D, D, false, [&](int i, int j, float v) {
-      v = fmaxf(v + Bs[j], 0.f);
-      Hs[i * SD + j] = v;
-      a.h[(size_t)(r0 + i) * D + j] = v;
-    });
-    __syncthreads();
-    RC_STAMP(2);
-    // ---- t = h W2^T + b2 (+ y1: without dropout the residual is added right here), in place over y1
-    sas_mm(MatA{Hs, SD, 1}, MatB{W2s, 1, SD}, m, D, D, false, [&](int i, int j, float v) {
-      v += Bs[D + j];
-      if (!drop) v += Ys[i * SD + j];
-      Ys[i * SD + j] = v;
-    });
-    __syncthreads();
-    RC_STAMP(3);
-    // ---- LayerNorm2
-#pragma unroll
-    for (int q = 0; q < NPASS; ++q) {
-      const int i = q * GPB + grp;
-      const int64_t r = (int64_t)r0 + i;
-      const float* sp = Ys + i * SD + 4 * l;
-      float4 z = make_float4(sp[0], sp[1], sp[2], sp[3]);
-      if (drop && i < m) {  // drop2(t) + y1 (y1 was overwritten in LDS: read it back, L2-hot)
-        const float4 kp = sb_drop_keep4<D>(dr2, seed, r, l);
-        const float4 y = reinterpret_cast<const float4*>(a.y1)[(size_t)r * LPR + l];
-        z.x *= kp.x; z.y *= kp.y; z.z *= kp.z; z.w *= kp.w;     // (the same two roundings as the unfused kernels)
-        z.x += y.x; z.y += y.y; z.z += y.z; z.w += y.w;
-      }
-      const float mu = row_allreduce_sum<LPR>((z.x + z.y) + (z.z + z.w)) / D;
-      const float cx = z.x - mu, cy = z.y - mu, cz = z.z - mu, cw = z.w - mu;
-      const float var = row_allreduce_sum<LPR>(fmaf(cx, cx, fmaf(cy, cy, fmaf(cz, cz, cw * cw)))) / D;
-      const float rs = 1.0f / sqrtf(var + kLnEps);
-      const float4 xh = make_float4(cx * rs, cy * rs, cz * rs, cw * rs);
-      if (i < m) {
-        reinterpret_cast<float4*>(a.xh2)[(size_t)r * LPR + l] = xh;
-        if (l == 0) a.rstd2[r] = rs;
-        reinterpret_cast<float4*>(a.xnext)[(size_t)r * LPR + l] =
-            make_float4(fmaf(xh.x, w2v.x, b2v.x), fmaf(xh.y, w2v.y, b2v.y), fmaf(xh.z, w2v.z, b2v.z), fmaf(xh.w, w2v.w, b2v.w));
-      }
-    }
-    RC_STAMP(4);
-#ifdef RC_X_TIMING
-    ++n_my_tiles;
-#endif
-  }
-#ifdef RC_X_TIMING
-  if ((blockIdx.x == 0 || blockIdx.x == 300) && threadIdx.x == 0)
-    printf("sb_block_fwd wg %d: %d tiles, ticks (100 MHz): wait0 %llu ln1 %llu gemm1 %llu gemm2 %llu ln2 %llu total %llu\n", (int)blockIdx.x,
-           n_my_tiles, (unsigned long long)tstamp[0], (unsigned long long)tstamp[1], (unsigned long long)tstamp[2],
-           (unsigned long long)tstamp[3], (unsigned long long)tstamp[4], (unsigned long long)(wall_clock64() - t_begin));
-#endif
-#undef RC_STAMP
-}
 
 // ---- attention per sequence: ctx = softmax(causal(Q K^T / sqrt(dk))) V, head by head ---------------------
 
@@ -1032,7 +655,7 @@ __global__ __launch_bounds__(256 * WPH) void sb_attn_bwd_wave_kernel(SbAttnArgs 
 #undef RC_ST
 }
 
-// ---- the same block on 16-row tiles without an LDS row tile (the pattern of sb_qkv16_kernel) ---------------------------------
+// ---- the post-attention block on 16-row tiles without an LDS row tile (the pattern of sb_qkv16_kernel) ----------------------
 // In the Y^T = W X^T form a product's accumulator comes out in the very layout the next product wants as its B operand
 // (lane (i, g): row i, columns 16 n + 4 g .. + 3), so LayerNorm1 -> FFN1 -> FFN2 -> LayerNorm2 chain through REGISTERS: a row's
 // statistics are the lane's sixteen values plus two cross-lane steps, the activations never touch LDS, and a wave walks its
@@ -1824,7 +1447,6 @@ __global__ __launch_bounds__(kBlock) void sb_last_add_kernel(const float* __rest
   }
 }
 
-static bool sb_fused_block();
 // RC_SAS_LAST_ROW: 0 = the last layer on all rows like the others; 1 = one query row per sequence over materialised keys /
 // values (sb_attn_last_kernel); unset / 2 = the same without keys and values (sas_last_row.hpp).  (A/B timing, equivalence tests)
 static int sb_last_row_request() {
@@ -1843,7 +1465,7 @@ static int sb_last_row_mode(int n_heads, int B, int L, bool drop) {
     return v ? (int64_t)atoll(v) : (int64_t)32768;
   }();
   const int want = sb_last_row_request();
-  if (want <= 0 || drop || n_heads < 1 || D % n_heads != 0 || L > kLrMaxL || !sb_fused_block() || !sb_rows16()) return 0;
+  if (want <= 0 || drop || n_heads < 1 || D % n_heads != 0 || L > kLrMaxL) return 0;
   const int dk = D / n_heads;
   // the buffers of the K / V-free version live in the saved state's per-layer arrays: H * D + 4 <= L * D and 2 D + H L <= L D
   const bool v2 = (n_heads == 1 || n_heads == 2 || n_heads == 4) && L >= 3 && L >= n_heads + 1 && dk % (D * D / kBlock) == 0;
@@ -1917,20 +1539,6 @@ static int sb_row_grid(int64_t rows, int lpr) {
   return (int)(g < 1 ? 1 : g);
 }
 
-template <int D, int NW, bool TRANS>
-static int sb_linear(const SbLinArgs& a, int64_t rmax, hipStream_t s) {
-  const size_t lds = ((size_t)(NW * D + kSbTile) * (D + 1) + (size_t)NW * D) * sizeof(float);
-  auto kern = sb_linear_kernel<D, NW, TRANS>;
-  RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int64_t tiles = (rmax + kSbTile - 1) / kSbTile;
-  const int per_cu = (int)((160 * 1024) / lds);
-  const int64_t cap = 256 * (int64_t)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
-  if (tiles > cap) tiles = cap;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < 1 ? 1 : tiles)), dim3(kBlock), lds, s, a);
-  RC_LAUNCH_CHECK();
-  return RC_OK;
-}
-
 // attention launches.  Sequences are split on the device into length classes <= 16, <= 32, <= history_max
 // (sas_bucket_n_kernel); a class runs with as many LDS rows as its longest member, so the short histories that
 // dominate real data get many resident workgroups per CU (17 KB forward, 25 KB backward at 16 rows, d = 64).
@@ -1992,7 +1600,7 @@ static int sb_attention(SbAttnArgs a, int32_t* bucket, bool make_buckets, hipStr
     // prefetch of the next sequence's rows: needs the full 64 * 4 * wph threads; PF float4 per thread and buffer
     const int threads_w = 64 * a.n_heads * wph;
     int pfn = 0;
-    if (per_wave && a.n_heads == 4 && getenv("RC_SAS_NO_PREFETCH") == nullptr) {
+    if (per_wave && a.n_heads == 4) {
       pfn = (a.lp * (D / 4) + threads_w - 1) / threads_w;
       pfn = pfn <= 1 ? 1 : (pfn <= 2 ? 2 : (pfn <= 4 ? 4 : 0));
     }
@@ -2010,13 +1618,6 @@ static int sb_attention(SbAttnArgs a, int32_t* bucket, bool make_buckets, hipStr
   }
   return RC_OK;
 }
-
-// RC_SAS_FUSED_BLOCK=0: the post-attention half as four launches (round 2), for A/B timing and the equivalence test
-static bool sb_fused_block() {
-  const char* v = getenv("RC_SAS_FUSED_BLOCK");
-  return !(v && v[0] == '0');
-}
-
 
 // ---- the K / V-free last block (sas_last_row.hpp): launch sequences ----------------------------------------------------------------------
 struct SbLastBufs {   // where its per-sequence arrays live inside the layer's saved state
@@ -2285,7 +1886,7 @@ static int sb_forward(const float* item_emb, const float* pos_emb, const SasLaye
     a.off = w.off; a.B = B;
     a.X = sv.x; a.W[0] = p.Wq; a.W[1] = p.Wk; a.W[2] = p.Wv; a.bias[0] = p.bq; a.bias[1] = p.bk; a.bias[2] = p.bv;
     a.Y[0] = sv.q; a.Y[1] = sv.k; a.Y[2] = sv.v;
-    if (sb_rows16()) {
+    {
       const size_t lds = (size_t)(3 * D * (D + 4) + 3 * D) * sizeof(float);
       auto kern = sb_qkv16_kernel<D, 3>;
       RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2293,8 +1894,6 @@ static int sb_forward(const float* item_emb, const float* pos_emb, const SasLaye
       sb_rows16_geometry((int64_t)rmax, &grid, &block);
       hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)block), lds, s, a);
       RC_LAUNCH_CHECK();
-    } else {
-      RC_TRY((sb_linear<D, 3, false>(a, (int64_t)rmax, s)));
     }
     SbAttnArgs at;
     memset(&at, 0, sizeof(at));
@@ -2302,53 +1901,20 @@ static int sb_forward(const float* item_emb, const float* pos_emb, const SasLaye
     at.n_heads = n_heads;
     RC_TRY((sb_attention<D, false>(at, w.bucket, l == 0, s)));
     dr.site = 2u * (uint32_t)l;      // dropout1 on the attention context (utils/layers.py:110)
-    if (sb_fused_block()) {          // LayerNorm1 -> FFN -> LayerNorm2 in one launch
-      SbBlockArgs bk;
-      bk.ctx = w.t0; bk.x = sv.x; bk.ln1w = p.ln1w; bk.ln1b = p.ln1b; bk.W1 = p.W1; bk.b1 = p.b1; bk.W2 = p.W2; bk.b2 = p.b2;
-      bk.ln2w = p.ln2w; bk.ln2b = p.ln2b; bk.xh1 = sv.xh1; bk.rstd1 = sv.rstd1; bk.y1 = sv.y1; bk.h = sv.h; bk.xh2 = sv.xh2;
-      bk.rstd2 = sv.rstd2; bk.xnext = xnext; bk.off = w.off; bk.B = B; bk.dr = dr;
-      if (sb_rows16()) {   // 16-row tiles, activations chained through registers
-        const size_t lds16 = ((size_t)2 * D * (D + 4) + 6 * (size_t)D) * sizeof(float);
-        auto kern16 = sb_block16_fwd_kernel<D>;
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-        const int64_t tiles16 = ((int64_t)rmax + 15) / 16;
-        // 140 registers per lane: three waves per SIMD.  Four-wave workgroups place one wave on each SIMD, so three of them
-        // share a CU (36 KB of LDS each); an eight-wave workgroup would be alone on its CU with two waves per SIMD
-        int nw = 4;
-        if (const char* v = getenv("RC_SB16_BLOCK_WAVES")) nw = atoi(v) == 8 ? 8 : 4;   // experiment switch
-        int64_t gr = (tiles16 + nw - 1) / nw;
-        const int64_t cap16 = nw == 8 ? 256 : 768;
-        if (gr > cap16) gr = cap16;
-        hipLaunchKernelGGL(kern16, dim3((unsigned)(gr < 1 ? 1 : gr)), dim3(64 * nw), lds16, s, bk);
-        RC_LAUNCH_CHECK();
-        continue;
-      }
-      const size_t lds = ((size_t)(2 * D + 2 * kSbTile) * (D + 1) + 2 * (size_t)D) * sizeof(float);
-      auto kern = sb_block_fwd_kernel<D>;
-      RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      int64_t tiles = ((int64_t)rmax + kSbTile - 1) / kSbTile;
-      const int per_cu = (int)((160 * 1024) / lds);
-      const int64_t cap = 256 * (int64_t)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
-      if (tiles > cap) tiles = cap;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < 1 ? 1 : tiles)), dim3(kBlock), lds, s, bk);
-      RC_LAUNCH_CHECK();
-      continue;
-    }
-    hipLaunchKernelGGL((sb_ln_fwd_kernel<D>), dim3(sb_row_grid((int64_t)rmax, LPR)), dim3(kBlock), 0, s, w.t0, sv.x, p.ln1w,
-                       p.ln1b, w.off, B, sv.xh1, sv.rstd1, sv.y1, dr);
-    RC_LAUNCH_CHECK();
-    memset(&a, 0, sizeof(a));
-    a.off = w.off; a.B = B;
-    a.X = sv.y1; a.W[0] = p.W1; a.bias[0] = p.b1; a.Y[0] = sv.h; a.relu = 1;
-    RC_TRY((sb_linear<D, 1, false>(a, (int64_t)rmax, s)));
-    // without dropout the residual y1 is added by the projection's epilogue; with dropout2 (utils/layers.py:117) the
-    // LayerNorm kernel masks the FFN output first and adds the residual itself
-    a.X = sv.h; a.W[0] = p.W2; a.bias[0] = p.b2; a.Y[0] = w.t0; a.relu = 0; a.res = drop ? nullptr : sv.y1;
-    RC_TRY((sb_linear<D, 1, false>(a, (int64_t)rmax, s)));
-    dr.site = 2u * (uint32_t)l + 1u;
-    hipLaunchKernelGGL((sb_ln_fwd_kernel<D>), dim3(sb_row_grid((int64_t)rmax, LPR)), dim3(kBlock), 0, s, w.t0,
-                       drop ? static_cast<const float*>(sv.y1) : static_cast<const float*>(nullptr), p.ln2w, p.ln2b, w.off, B,
-                       sv.xh2, sv.rstd2, xnext, dr);
+    // LayerNorm1 -> FFN -> LayerNorm2 in one launch: 16-row tiles, activations chained through registers
+    SbBlockArgs bk;
+    bk.ctx = w.t0; bk.x = sv.x; bk.ln1w = p.ln1w; bk.ln1b = p.ln1b; bk.W1 = p.W1; bk.b1 = p.b1; bk.W2 = p.W2; bk.b2 = p.b2;
+    bk.ln2w = p.ln2w; bk.ln2b = p.ln2b; bk.xh1 = sv.xh1; bk.rstd1 = sv.rstd1; bk.y1 = sv.y1; bk.h = sv.h; bk.xh2 = sv.xh2;
+    bk.rstd2 = sv.rstd2; bk.xnext = xnext; bk.off = w.off; bk.B = B; bk.dr = dr;
+    const size_t lds16 = ((size_t)2 * D * (D + 4) + 6 * (size_t)D) * sizeof(float);
+    auto kern16 = sb_block16_fwd_kernel<D>;
+    RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+    const int64_t tiles16 = ((int64_t)rmax + 15) / 16;
+    // 140 registers per lane: three waves per SIMD.  Four-wave workgroups place one wave on each SIMD, so three of them
+    // share a CU (36 KB of LDS each); an eight-wave workgroup would be alone on its CU with two waves per SIMD
+    int64_t gr = (tiles16 + 3) / 4;
+    if (gr > 768) gr = 768;
+    hipLaunchKernelGGL(kern16, dim3((unsigned)(gr < 1 ? 1 : gr)), dim3(256), lds16, s, bk);
     RC_LAUNCH_CHECK();
   }
   const float* xout = state + (size_t)n_layers * sb_layer_floats(rmax, D);
@@ -2395,7 +1961,6 @@ static int sb_backward(const SasLayer* layer, int n_layers, int n_heads, const i
     hipLaunchKernelGGL((sb_seed_kernel<D>), dim3(sb_row_grid((int64_t)rmax, LPR)), dim3(kBlock), 0, s, dhv, lengths, w.off, B, L, G);
     RC_LAUNCH_CHECK();
   }
-  const int ln_grid = sb_row_grid((int64_t)rmax, LPR) < kSbPartWg ? sb_row_grid((int64_t)rmax, LPR) : kSbPartWg;
   for (int l = n_layers - 1; l >= 0; --l) {
     const SasLayer& p = layer[l];
     const SbSaved sv = sb_saved(const_cast<float*>(state), l, rmax, D);
@@ -2473,12 +2038,10 @@ static int sb_backward(const SasLayer* layer, int n_layers, int n_heads, const i
       RC_LAUNCH_CHECK();
       continue;
     }
-    // LayerNorm2
+    // LayerNorm2 backward -> FFN backward (both weight gradients) -> LayerNorm1 backward: one launch
     // (dropout: G = dZ2 feeds the residual path, Gb = mask2 * dZ2 the FFN branch)
     float* Gb = drop ? w.t4 : G;
-    SbWgradArgs g;
-    SbLinArgs a;
-    if (sb_fused_block()) {   // LayerNorm2 backward -> FFN backward (both weight gradients) -> LayerNorm1 backward: one launch
+    {
       SbBlockBwdArgs bb;
       bb.G = G; bb.Gb = Gb; bb.xh2 = sv.xh2; bb.rstd2 = sv.rstd2; bb.h = sv.h; bb.y1 = sv.y1; bb.xh1 = sv.xh1; bb.rstd1 = sv.rstd1;
       bb.ln2w = p.ln2w; bb.W2 = p.W2; bb.W1 = p.W1; bb.ln1w = p.ln1w; bb.part = gp; bb.part_stride = stride; bb.off = w.off; bb.B = B;
@@ -2494,30 +2057,8 @@ static int sb_backward(const SasLayer* layer, int n_layers, int n_heads, const i
       if (tiles > cap) tiles = cap;
       hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < 1 ? 1 : tiles)), dim3(kBlock), lds, s, bb);
       RC_LAUNCH_CHECK();
-    } else {
-    dr.site = 2u * (uint32_t)l + 1u;
-    hipLaunchKernelGGL((sb_ln_bwd_kernel<D>), dim3(ln_grid), dim3(kBlock), 0, s, G, sv.xh2, sv.rstd2, p.ln2w, w.off, B,
-                       gp + Cfg::oln2w, gp + Cfg::oln2b, stride, dr, Gb);
-    RC_LAUNCH_CHECK();
-    // FFN: dW2, db2; dHpre = (dZ2 . W2) * relu'(h); dW1, db1; dY1 = dZ2 + dHpre . W1
-    memset(&g, 0, sizeof(g));
-    g.off = w.off; g.B = B; g.part_stride = stride;
-    g.dY[0] = Gb; g.X = sv.h; g.gW[0] = gp + Cfg::oW2; g.gb[0] = gp + Cfg::ob2;
-    RC_TRY((sb_wgrad<D, 1>(g, (int64_t)rmax, s)));
-    memset(&a, 0, sizeof(a));
-    a.off = w.off; a.B = B;
-    a.X = Gb; a.W[0] = p.W2; a.Y[0] = w.t1; a.mask = sv.h;
-    RC_TRY((sb_linear<D, 1, true>(a, (int64_t)rmax, s)));
-    g.dY[0] = w.t1; g.X = sv.y1; g.gW[0] = gp + Cfg::oW1; g.gb[0] = gp + Cfg::ob1;
-    RC_TRY((sb_wgrad<D, 1>(g, (int64_t)rmax, s)));
-    a.X = w.t1; a.W[0] = p.W1; a.Y[0] = G; a.mask = nullptr; a.res = G;
-    RC_TRY((sb_linear<D, 1, true>(a, (int64_t)rmax, s)));
-    // LayerNorm1: G = dZ1 = dCtx = the residual branch of dX
-    dr.site = 2u * (uint32_t)l;
-    hipLaunchKernelGGL((sb_ln_bwd_kernel<D>), dim3(ln_grid), dim3(kBlock), 0, s, G, sv.xh1, sv.rstd1, p.ln1w, w.off, B,
-                       gp + Cfg::oln1w, gp + Cfg::oln1b, stride, dr, Gb);
-    RC_LAUNCH_CHECK();
     }
+    SbWgradArgs g;
     memset(&g, 0, sizeof(g));
     g.off = w.off; g.B = B; g.part_stride = stride;
     // attention
@@ -2535,24 +2076,12 @@ static int sb_backward(const SasLayer* layer, int n_layers, int n_heads, const i
       SbSum3Args q;
       q.X[0] = w.t1; q.X[1] = w.t2; q.X[2] = w.t3; q.W[0] = p.Wq; q.W[1] = p.Wk; q.W[2] = p.Wv;
       q.res = G; q.Y = G; q.off = w.off; q.B = B;
-      if (sb_rows16()) {
-        const size_t lds16 = (size_t)(3 * D * (D + 4)) * sizeof(float);
-        auto kern16 = sb_sum3_16_kernel<D, 3>;
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-        int grid, block;
-        sb_rows16_geometry((int64_t)rmax, &grid, &block);
-        hipLaunchKernelGGL(kern16, dim3((unsigned)grid), dim3((unsigned)block), lds16, s, q);
-        RC_LAUNCH_CHECK();
-        continue;
-      }
-      const size_t lds = (size_t)(3 * D + kSbTile) * (D + 1) * sizeof(float);
-      auto kern = sb_linear3_sum_kernel<D>;
-      RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      int64_t tiles = ((int64_t)rmax + kSbTile - 1) / kSbTile;
-      const int per_cu = (int)((160 * 1024) / lds);
-      const int64_t cap = 256 * (int64_t)(per_cu < 1 ? 1 : per_cu);
-      if (tiles > cap) tiles = cap;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < 1 ? 1 : tiles)), dim3(kBlock), lds, s, q);
+      const size_t lds16 = (size_t)(3 * D * (D + 4)) * sizeof(float);
+      auto kern16 = sb_sum3_16_kernel<D, 3>;
+      RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+      int grid, block;
+      sb_rows16_geometry((int64_t)rmax, &grid, &block);
+      hipLaunchKernelGGL(kern16, dim3((unsigned)grid), dim3((unsigned)block), lds16, s, q);
       RC_LAUNCH_CHECK();
     }
   }

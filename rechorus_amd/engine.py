@@ -455,31 +455,23 @@ def segmented_pair_supported(d):
 _EDB_PLAN_MIN = int(os.environ.get("RC_EDB_PLAN_MIN", "8192"))
 _EDB_SMALL = os.environ.get("RC_EDB_SMALL", "1") != "0"   # embedding_dense_backward of a small id list: rc_small_row_sums
 _EDB_SMALL_MAX = int(os.environ.get("RC_EDB_SMALL_MAX", "8192"))
-# A/B switches: RC_TABLE_UPDATE=sort puts every trainer's table update behind the radix sort, =plan behind the bucket plan.
-# Default: NeuMF on the plan (hashed buckets: 0.33 M lookups over 10 M - 100 M rows); SASRec behind the sort -- 0.6 M
-# occurrences over 8.7 K rows are all hot rows, where the sort-driven update measured faster (table_update 0.27 ms against
-# 0.44 ms through the narrow-bucket plan, profiles/r03d_bench_sasrec*.json)
+# A/B switch: RC_TABLE_UPDATE=sort puts NeuMF's table update behind the radix sort instead of the bucket plan (hashed buckets:
+# 0.33 M lookups over 10 M - 100 M rows).  SasrecTrainer's update is always sort-driven: 0.6 M occurrences over 8.7 K rows are
+# all hot rows, where it measured faster (table_update 0.27 ms against 0.44 ms through the narrow-bucket plan,
+# profiles/r03d_bench_sasrec*.json)
 _USE_PLAN = os.environ.get("RC_TABLE_UPDATE", "auto") != "sort"
 # sorted ids of a table whose rows collect many occurrences each: rc_segmented_update_rows (RC_SEG_ROWS=0: the head-list route)
 _SEG_ROWS = os.environ.get("RC_SEG_ROWS", "1") != "0"
-# SasrecTrainer: id sort beside the encoder, position gradient beside the item update, on a second stream (RC_SAS_OVERLAP=0: one stream)
-_SAS_OVERLAP = os.environ.get("RC_SAS_OVERLAP", "1") != "0"
 _PLAN_CHECK = os.environ.get("RC_PLAN_CHECK", "0") == "1"        # every engine.Plan verifies its status word (host sync; debugging)
 _NEUMF_OVERLAP = os.environ.get("RC_NEUMF_OVERLAP", "1") != "0"   # NeumfTrainer: bucket plan beside the head kernels
 _NEUMF_FUSED = os.environ.get("RC_NEUMF_FUSED", "1") != "0"       # NeumfTrainer: rc_neumf_train_step (A/B against the three-kernel step)
-_SAS_OVERLAP_MIN = int(os.environ.get("RC_SAS_OVERLAP_MIN", "131072"))   # candidate + history occurrences of the batch
+# SasrecTrainer runs its step on two streams (SasrecTrainer._step_item_stream) from this many candidate + history occurrences
+# of the batch on
+_SAS_OVERLAP_MIN = int(os.environ.get("RC_SAS_OVERLAP_MIN", "131072"))
 _SEG_ROWS_MIN_PER_ROW = int(os.environ.get("RC_SEG_ROWS_MIN_PER_ROW", "8"))
-_SASREC_PLAN = os.environ.get("RC_TABLE_UPDATE", "auto") == "plan"
 # SasrecTrainer on the one-wave-per-row route: row bounds from a counting sort of item_id + history_items (RowsPlan) instead of the
 # radix sort and its tensor glue (RC_SAS_ROWS_PLAN=0: the sorted route, same results bit for bit)
 _SAS_ROWS_PLAN = os.environ.get("RC_SAS_ROWS_PLAN", "1") != "0"
-# the two-stream schedule of SasrecTrainer (SasrecTrainer._step_item_stream): one stream owns everything about the item table -- the
-# plan beside the encoder, then the table update as soon as the history rows' gradient is complete (rc_sasrec_batch_bwd_part) -- while
-# the other finishes the encoder's parameter gradients, the position gradient and the dense step: ONE join at the end of the step.
-# "2" (default): the encoder rides the caller's stream; "3": the item-table work does; "1": the round-5 schedule (plan on the side
-# stream, joined before the table update on the main stream, position gradient on the side).  Same box, config 3, ms per replayed
-# step: "1" 0.240, "2" 0.219, "3" 0.225 (profiles/r09_sasrec_two_stream_schedules.txt)
-_SAS_SCHED = os.environ.get("RC_SAS_SCHED", "2")
 
 
 def unique_ids(ids, n_rows, tag="unique"):
@@ -1426,8 +1418,7 @@ SASREC_BATCH_MIN_ROWS = 4096  # B * history_max from which the batch-level kerne
 def _sasrec_one_row_encoder(d, n_heads, n_layers, L):
     """the batch encoder's K / V-free last-row path (csrc/sas_last_row.hpp; sb_last_row_mode) serves the WHOLE encoder:
     one block, no dropout, head count 1 / 2 / 4, history_max 3 .. 128"""
-    if d is None or int(os.environ.get("RC_SAS_LAST_ROW", "2")) < 2 or os.environ.get("RC_SAS_FUSED_BLOCK") == "0" \
-            or os.environ.get("RC_SAS_ROWS16") == "0":
+    if d is None or int(os.environ.get("RC_SAS_LAST_ROW", "2")) < 2:
         return False
     return (n_layers == 1 and d in (32, 64) and n_heads in (1, 2, 4) and 3 <= L <= 128 and L >= n_heads + 1
             and (d // n_heads) % (d * d // 256) == 0)
@@ -1792,9 +1783,7 @@ class SasrecTrainer:
         if self._step_dev is None:
             return False
         I = self.P["item_emb"]
-        n_occ = iid.numel() + hist.numel()
-        use_plan = _SASREC_PLAN and n_occ >= _EDB_PLAN_MIN and plan_supported(n_occ, 0, I.shape[0], 0)
-        return not use_plan and seg_rows_route(n_occ, I.shape[0], I.shape[1])
+        return seg_rows_route(iid.numel() + hist.numel(), I.shape[0], I.shape[1])
 
     def step(self, hist, lengths, iid):
         if not (self.graph and hist.is_cuda) or getattr(self, "timing", None) is not None \
@@ -1902,55 +1891,46 @@ class SasrecTrainer:
         _, loss_vec, gpred, dhv = bprmf_fwd_bwd(hv, self.P["item_emb"], rows_by[key_rows], iid, want_pred=False)
         return loss_vec, gpred, dhv
 
-    def _step_item_stream(self, hist, lengths, iid, h, h0, step_dev, rows_plan, encoder_first):
+    def _step_item_stream(self, hist, lengths, iid, h, h0, step_dev, rows_plan):
         """The step on two streams, one of which owns everything about the ITEM TABLE: the grouping of the batch's ids beside the
         encoder, then -- as soon as the history rows' gradient is complete (rc_sasrec_batch_bwd_part) -- the table update, while the
         other stream finishes the encoder's parameter gradients, the position gradient and the dense step.  One fork, one
         hand-over (g_hist ready), one join.  (Round 5: the table update ran on the encoder's stream behind a second join, the
         position gradient on the side: two more cross-queue edges of ~11 us each on the critical path of a replayed step.)
-        encoder_first: the encoder rides the caller's stream (in a captured step: the launch stream, the other branch starts behind a
-        cross-queue barrier); else the item-table work does, and the LAST kernels of the step -- the table update's -- are on the
-        launch stream, where the graph ends without waiting for another queue."""
+        The encoder rides the caller's stream (in a captured step: the launch stream, the other branch starts behind a cross-queue
+        barrier), the item-table work the side stream.  The other way round -- the table update's kernels last on the launch stream,
+        where the graph ends without waiting for another queue -- measured 0.225 against 0.219 ms per replayed step at config 3
+        (profiles/r09_sasrec_two_stream_schedules.txt)."""
         P = self.P
         I, Pe, layers = P["item_emb"], P["pos_emb"], P["layers"]
         B, L = hist.shape
         Cn = iid.shape[1]
         d = I.shape[1]
-        cur, other = torch.cuda.current_stream(hist.device), self._side_stream(hist.device)
-        enc, tab = (cur, other) if encoder_first else (other, cur)
-        # the batch is ready; last step's users of the other stream's buffers are done (the step ends with a join)
-        other.wait_event(cur.record_event())
-        box = {}
-
-        def plan():
-            with torch.cuda.stream(tab):
-                box["ids"] = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows") if rows_plan else self._sorted_occurrences(hist, lengths, iid)
-
-        def forward():
-            with torch.cuda.stream(enc), _PhaseTimer(self, "encoder_fwd"):
-                box["hv"], box["x"] = sasrec_fwd(I, Pe, layers, self.n_heads, hist, lengths, save=True, drop_p=self.dropout, seed=self.seed)
-
-        for part in ((forward, plan) if encoder_first else (plan, forward)):   # (capture order: see encoder_first)
-            part()
-        hv = box["hv"]
-        with torch.cuda.stream(enc):
-            with _PhaseTimer(self, "score_loss"):
-                loss_vec, gpred, dhv = self._score_loss(hv, iid, B)
-            with _PhaseTimer(self, "encoder_bwd"):
-                g_hist, dgrads, finish_bwd = sasrec_bwd(layers, self.n_heads, lengths, box["x"], dhv, drop_p=self.dropout, seed=self.seed, split=True)
-            ready = enc.record_event()     # g_hist, gpred, hv: what the table update reads
-            with _PhaseTimer(self, "dense_update"):
-                finish_bwd()               # the encoder's parameter gradients ...
-                Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])     # ... the position table's, and the dense step of both
-                self._dense_step(Gp, dgrads, h, h0, step_dev)
-            # the batch mean of the losses last on this stream: it ends ~20 us before the item-table stream does, and 5 us in front of
-            # the table update were 5 us of the step
-            self.loss = reduce_sum(loss_vec, 1.0 / B)
+        enc = torch.cuda.current_stream(hist.device)
+        tab = self._side_stream(hist.device)
+        # the batch is ready; last step's users of the side stream's buffers are done (the step ends with a join)
+        tab.wait_event(enc.record_event())
+        with _PhaseTimer(self, "encoder_fwd"):
+            hv, xsave = sasrec_fwd(I, Pe, layers, self.n_heads, hist, lengths, save=True, drop_p=self.dropout, seed=self.seed)
+        with torch.cuda.stream(tab):
+            sorted_ids = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows") if rows_plan else self._sorted_occurrences(hist, lengths, iid)
+        with _PhaseTimer(self, "score_loss"):
+            loss_vec, gpred, dhv = self._score_loss(hv, iid, B)
+        with _PhaseTimer(self, "encoder_bwd"):
+            g_hist, dgrads, finish_bwd = sasrec_bwd(layers, self.n_heads, lengths, xsave, dhv, drop_p=self.dropout, seed=self.seed, split=True)
+        ready = enc.record_event()     # g_hist, gpred, hv: what the table update reads
+        with _PhaseTimer(self, "dense_update"):
+            finish_bwd()               # the encoder's parameter gradients ...
+            Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])     # ... the position table's, and the dense step of both
+            self._dense_step(Gp, dgrads, h, h0, step_dev)
+        # the batch mean of the losses last on this stream: it ends ~20 us before the item-table stream does, and 5 us in front of
+        # the table update were 5 us of the step
+        self.loss = reduce_sum(loss_vec, 1.0 / B)
         with torch.cuda.stream(tab):
             tab.wait_event(ready)
             with _PhaseTimer(self, "table_update"):
-                self._item_table_update(box["ids"], rows_plan, hv, gpred, g_hist, h, step_dev, B, Cn)
-        cur.wait_stream(other)             # the step's one join
+                self._item_table_update(sorted_ids, rows_plan, hv, gpred, g_hist, h, step_dev, B, Cn)
+        enc.wait_stream(tab)             # the step's one join
         return self.loss
 
     def _step(self, hist, lengths, iid):
@@ -1967,78 +1947,29 @@ class SasrecTrainer:
         if self._step_dev is not None:
             step_increment(self._step_dev)
         n_occ = B * Cn + hist.numel()
-        use_plan = _SASREC_PLAN and n_occ >= _EDB_PLAN_MIN and plan_supported(n_occ, 0, I.shape[0], 0)
         # Adam under replay: the kernels read the step count from device memory where the route carries it (else this step takes
         # the host's count -- both advance every step -- and is not captured)
         step_dev = self._step_dev if self._dev_step_route(hist, iid) else None
+        # one wave per table row with the rows' bounds from a counting sort of the id tensors themselves (no radix sort, no glue)
+        rows_plan = (_SAS_ROWS_PLAN and hist.is_cuda and seg_rows_route(n_occ, I.shape[0], d)
+                     and rows_plan_supported(I.shape[0], n_occ, d))
         # (small batches are bound by the host's launch rate: the extra stream switches cost more than the overlap returns --
         #  B = 256: 0.39 against 0.30 ms; B = 4096: 0.66 against 0.72 ms)
-        overlap = _SAS_OVERLAP and hist.is_cuda and not use_plan and n_occ >= _SAS_OVERLAP_MIN
-        sorted_ids = sort_done = main = side = None
-        # one wave per table row with the rows' bounds from a counting sort of the id tensors themselves (no radix sort, no glue)
-        rows_plan = (_SAS_ROWS_PLAN and hist.is_cuda and not use_plan and seg_rows_route(n_occ, I.shape[0], d)
-                     and rows_plan_supported(I.shape[0], n_occ, d))
-        if overlap and _SAS_SCHED in ("2", "3"):
-            return self._step_item_stream(hist, lengths, iid, h, h0, step_dev, rows_plan, encoder_first=_SAS_SCHED == "2")
-
-        if overlap:      # RC_SAS_SCHED=1, the round-5 schedule: plan on the side stream, joined before the table update
-            main, side = torch.cuda.current_stream(hist.device), self._side_stream(hist.device)
-            side.wait_stream(main)   # the batch is ready; last step's readers of the side stream's buffers are done
-            with torch.cuda.stream(side):
-                sorted_ids = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows") if rows_plan else self._sorted_occurrences(hist, lengths, iid)
-                sort_done = side.record_event()
+        if hist.is_cuda and n_occ >= _SAS_OVERLAP_MIN:
+            return self._step_item_stream(hist, lengths, iid, h, h0, step_dev, rows_plan)
         with _PhaseTimer(self, "encoder_fwd"):
             hv, xsave = sasrec_fwd(I, Pe, layers, self.n_heads, hist, lengths, save=True, drop_p=self.dropout, seed=self.seed)
         with _PhaseTimer(self, "score_loss"):
             loss_vec, gpred, dhv = self._score_loss(hv, iid, B)
-            if not overlap:
-                self.loss = reduce_sum(loss_vec, 1.0 / B)   # (two streams: the mean is formed on the side stream below)
+            self.loss = reduce_sum(loss_vec, 1.0 / B)
         with _PhaseTimer(self, "encoder_bwd"):
             g_hist, dgrads = sasrec_bwd(layers, self.n_heads, lengths, xsave, dhv, drop_p=self.dropout, seed=self.seed)
-        # item table: candidate occurrences (g * hv, rebuilt on the fly) + history occurrences (g_hist rows)
-        Gp = None
-        if overlap:
-            side.wait_stream(main)   # g_hist is ready
-            with torch.cuda.stream(side):
-                self.loss = reduce_sum(loss_vec, 1.0 / B)   # nothing on the main stream waits for the mean of the loss
-                Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])
-        _upd = _PhaseTimer(self, "table_update")
-        _upd.__enter__()
-        st = self._st(I)
-        if use_plan:
-            # bucket plan of candidate + history ids.  The padding slots of the history windows (id 0, zero gradient rows:
-            # half of B * history_max occurrences of ONE row) are marked "takes no part" (negative id) except the first of
-            # them, which keeps row 0 among the touched rows exactly as before -- a sum of zero rows is zero either way.
-            L = hist.shape[1]
-            pad = torch.arange(L, device=hist.device)[None, :] >= lengths[:, None]
-            hid = torch.where(pad, hist.new_full((), -1), hist).reshape(-1)
-            first_pad = pad.reshape(-1).to(torch.int32).argmax().reshape(1)   # position of the first padding slot (0 if there is none)
-            hid.scatter_(0, first_pad, hist.reshape(-1).gather(0, first_pad))   # (no tensor-indexed assignment: it syncs the host)
-            plan = Plan(torch.cat([iid.reshape(-1), hid]), I.shape[0], tag="sasrec")
-            src = dict(coef=gpred.reshape(-1), src=hv, div=Cn, src2=g_hist.view(-1, d), n_split=B * Cn)
-            if self.rowwise:
-                plan.update("a", I, h, m=st.get("m"), v=st.get("v"), **src)
-            else:
-                G = plan.row_sums("a", torch.zeros_like(I), **src)
-                dense_update(I, G, h, st.get("m"), st.get("v"))
-        else:
-            if overlap:
-                main.wait_event(sort_done)
-            elif rows_plan:
-                sorted_ids = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows")
-            else:
-                sorted_ids = self._sorted_occurrences(hist, lengths, iid)
+        with _PhaseTimer(self, "table_update"):
+            sorted_ids = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows") if rows_plan else self._sorted_occurrences(hist, lengths, iid)
             self._item_table_update(sorted_ids, rows_plan, hv, gpred, g_hist, h, step_dev, B, Cn)
-        _upd.__exit__()
-        # position table (tiny): dense gradient, dense step
-        _dns = _PhaseTimer(self, "dense_update")
-        _dns.__enter__()
-        if overlap:
-            main.wait_stream(side)
-        else:
+        with _PhaseTimer(self, "dense_update"):   # position table (tiny) and the block parameters: dense gradient, dense step
             Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])
-        self._dense_step(Gp, dgrads, h, h0, step_dev)
-        _dns.__exit__()
+            self._dense_step(Gp, dgrads, h, h0, step_dev)
         return self.loss
 
 

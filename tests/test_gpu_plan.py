@@ -581,9 +581,9 @@ def test_neumf_trainer_plan_on_second_stream_equals_one_stream(cuda, eng, monkey
             assert torch.equal(Sa[k][st], Sb[k][st]), (k, st)
 
 
-def test_neumf_and_sasrec_trainers_plan_equals_sort(cuda, eng, monkeypatch):
-    """the trainers' table updates through the bucket plan and behind the radix sort: bit-identical item tables, dense
-    parameters and state after two steps (both sum a row's gradient rows in ascending batch position)"""
+def test_neumf_trainer_plan_equals_sort(cuda, eng, monkeypatch):
+    """NeumfTrainer's table updates through the bucket plan and behind the radix sort: bit-identical item tables, dense
+    parameters and state after one step (both sum a row's gradient rows in ascending batch position)"""
     rng = np.random.default_rng(3)
     g = torch.Generator(device=cuda)
     # NeuMF, row-wise Adam, items sparse enough for the hashed geometry
@@ -624,37 +624,6 @@ def test_neumf_and_sasrec_trainers_plan_equals_sort(cuda, eng, monkeypatch):
         assert torch.equal(Pa[k], Pb[k]), k
         for st in ("m", "v"):
             assert torch.equal(Sa[k][st], Sb[k][st]), (k, st)
-    del Pa, Pb, Sa, Sb
-    # SASRec, row-wise Adam, padded histories
-    n_items, d, L, B, Cn = 9_000, 64, 50, 1024, 100
-    def sasrec(use_plan):
-        monkeypatch.setattr(eng, "_SASREC_PLAN", use_plan)
-        # (the sorted route's head list sums in ascending batch position like the plan; its one-wave-per-row variant for small
-        #  catalogues interleaves four lane-groups -- checked against both in tests/test_gpu_sasrec.py, within rounding)
-        monkeypatch.setattr(eng, "_SEG_ROWS", False)
-        g.manual_seed(2)
-        mk = lambda *sh: torch.empty(sh, device=cuda).normal_(0, 0.05, generator=g)
-        lay = {k: (mk(d, d) if k.startswith("W") else mk(d)) for k in eng.SAS_LAYER_KEYS}
-        lay["ln1w"] += 1.0
-        lay["ln2w"] += 1.0
-        P = {"item_emb": mk(n_items, d), "pos_emb": mk(L + 1, d), "layers": [lay]}
-        tr = eng.SasrecTrainer(P, 4, opt="Adam", lr=1e-2, l2=1e-5, rowwise=True)
-        r = np.random.default_rng(6)
-        for _ in range(2):
-            lengths = torch.from_numpy(r.integers(1, L + 1, size=B)).to(cuda)
-            hist = torch.from_numpy(_zipf(r, n_items, (B, L))).to(cuda)
-            hist = (hist * (torch.arange(L, device=cuda)[None, :] < lengths[:, None])).contiguous()
-            iid = torch.from_numpy(np.concatenate([_zipf(r, n_items, (B, 1)), r.integers(1, n_items, size=(B, Cn - 1))], axis=1)).to(cuda)
-            tr.step(hist, lengths, iid)
-        torch.cuda.synchronize()
-        return P, tr
-    Pa, ta = sasrec(True)
-    Pb, tb = sasrec(False)
-    assert torch.equal(Pa["item_emb"], Pb["item_emb"]) and torch.equal(Pa["pos_emb"], Pb["pos_emb"])
-    for k in eng.SAS_LAYER_KEYS:
-        assert torch.equal(Pa["layers"][0][k], Pb["layers"][0][k]), k
-    sa, sb = ta._st(Pa["item_emb"]), tb._st(Pb["item_emb"])
-    assert torch.equal(sa["m"], sb["m"]) and torch.equal(sa["v"], sb["v"])
 
 
 @pytest.mark.parametrize("hashed", [False, True])

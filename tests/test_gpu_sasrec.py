@@ -458,7 +458,7 @@ def test_rows_plan_equals_the_sorted_rows_route(d, n_rows, B, C, L, opt, cuda, e
 
 
 @pytest.mark.parametrize("opt,rowwise", [("SGD", True), ("Adam", True), ("Adam", False)])
-def test_sasrec_trainer_rows_plan_equals_sorted_route(opt, rowwise, cuda, eng, monkeypatch):
+def test_sasrec_trainer_rows_plan_equals_sorted_route_one_and_two_streams(opt, rowwise, cuda, eng, monkeypatch):
     """SasrecTrainer with the counting-sort row bounds (default) against RC_SAS_ROWS_PLAN=0 (radix sort + glue): three steps leave
     every parameter bit-identical, on one stream and on two"""
     rng = np.random.default_rng(11)
@@ -474,8 +474,7 @@ def test_sasrec_trainer_rows_plan_equals_sorted_route(opt, rowwise, cuda, eng, m
     for overlap in (True, False):
         for plan in (True, False):
             monkeypatch.setattr(eng, "_SAS_ROWS_PLAN", plan)
-            monkeypatch.setattr(eng, "_SAS_OVERLAP", overlap)
-            monkeypatch.setattr(eng, "_SAS_OVERLAP_MIN", 0)
+            monkeypatch.setattr(eng, "_SAS_OVERLAP_MIN", 0 if overlap else B * (C + L) + 1)   # two streams from this many occurrences on
             Pd = to_dev(P, n_layers, cuda)
             tr = eng.SasrecTrainer(Pd, n_heads, opt=opt, lr=1e-3, l2=1e-5, rowwise=rowwise)
             losses = [float(tr.step(*b)[0]) for b in batches]
@@ -488,7 +487,7 @@ def test_sasrec_trainer_rows_plan_equals_sorted_route(opt, rowwise, cuda, eng, m
 
 
 @pytest.mark.parametrize("opt,overlap", [("SGD", True), ("Adagrad", False), ("Adam", True)])
-def test_sasrec_trainer_graph_replay_equals_eager(opt, overlap, cuda, eng, monkeypatch):
+def test_sasrec_trainer_graph_replay_equals_eager_one_or_two_streams(opt, overlap, cuda, eng, monkeypatch):
     """SasrecTrainer(graph=True) replays the step from a hipGraph (both streams captured, the batch copied into static
     buffers): seven steps over different batches -- two eager, the capture, four replays -- leave the loss sequence and every
     parameter bit-identical to the eager trainer.  Adam: the replayed trainer keeps the step count in device memory and forms the
@@ -506,8 +505,7 @@ def test_sasrec_trainer_graph_replay_equals_eager(opt, overlap, cuda, eng, monke
         hist = rng.integers(1, n_items, size=(B, L)).astype(np.int64) * (np.arange(L)[None, :] < lengths[:, None])
         iid = rng.integers(1, n_items, size=(B, C)).astype(np.int64)
         batches.append(tuple(torch.from_numpy(x).to(cuda) for x in (hist, lengths, iid)))
-    monkeypatch.setattr(eng, "_SAS_OVERLAP", overlap)
-    monkeypatch.setattr(eng, "_SAS_OVERLAP_MIN", 0)
+    monkeypatch.setattr(eng, "_SAS_OVERLAP_MIN", 0 if overlap else B * (C + L) + 1)   # two streams from this many occurrences on
     out = {}
     for graph in (False, True):
         Pd = to_dev(P, n_layers, cuda)
@@ -575,10 +573,10 @@ def test_sasrec_trainer_graph_adam_counts_replayed_steps_on_the_host_too(cuda, e
 
 
 @pytest.mark.parametrize("rowwise", [False, True])
-def test_sasrec_trainer_two_streams_equal_one_stream(rowwise, cuda, eng, monkeypatch):
+def test_sasrec_trainer_two_stream_step_equals_one_stream_step(rowwise, cuda, eng, monkeypatch):
     """SasrecTrainer sorts the batch's ids beside the encoder and forms the position-table gradient beside the item-table
     update on a second stream; the kernels and their inputs are the same, so three steps leave every parameter bit-identical
-    to the one-stream order (RC_SAS_OVERLAP=0)"""
+    to the one-stream order (RC_SAS_OVERLAP_MIN above the batch's occurrences)"""
     rng = np.random.default_rng(5)
     B, L, d, n_layers, n_heads, C, n_items = 600, 50, 64, 2, 4, 20, 400
     P = _random_sasrec(rng, n_items, d, n_layers, L)
@@ -590,8 +588,7 @@ def test_sasrec_trainer_two_streams_equal_one_stream(rowwise, cuda, eng, monkeyp
         batches.append(tuple(torch.from_numpy(x).to(cuda) for x in (hist, lengths, iid)))
     out = {}
     for mode in (True, False):
-        monkeypatch.setattr(eng, "_SAS_OVERLAP", mode)
-        monkeypatch.setattr(eng, "_SAS_OVERLAP_MIN", 0)
+        monkeypatch.setattr(eng, "_SAS_OVERLAP_MIN", 0 if mode else B * (C + L) + 1)   # two streams from this many occurrences on
         Pd = to_dev(P, n_layers, cuda)
         tr = eng.SasrecTrainer(Pd, n_heads, opt="Adam", lr=1e-3, l2=1e-5, rowwise=rowwise)
         losses = [float(tr.step(*b)[0]) for b in batches]
@@ -623,39 +620,47 @@ def test_sasrec_trainer_two_streams_equal_one_stream(rowwise, cuda, eng, monkeyp
 
 
 @pytest.mark.parametrize("d,n_layers,n_heads,L,B", [(64, 2, 4, 50, 1400), (64, 1, 2, 20, 90), (32, 2, 2, 50, 1400), (32, 1, 1, 7, 3)])
-def test_sasrec_16_row_projection_kernels_equal_lds_tile_kernels(d, n_layers, n_heads, L, B, cuda, eng, monkeypatch):
+def test_sasrec_16_row_projection_kernels_vs_oracle(d, n_layers, n_heads, L, B, cuda, eng, monkeypatch):
     """the QKV projection and the dX = dZ + dQ Wq + dK Wk + dV Wv sum on 16 x 16 x 4 tiles with operands straight from global
-    memory (sb_qkv16_kernel / sb_sum3_16_kernel) against the LDS-tile 32 x 32 x 2 kernels (RC_SAS_ROWS16=0); 16-wave workgroups
-    (B * history_max >= 65,536 rows) and 4-wave ones, ragged last tiles, empty histories"""
+    memory (sb_qkv16_kernel / sb_sum3_16_kernel) against the numpy oracle: hv, every parameter gradient and the position-table
+    gradient formed from the history gradient; 16-wave workgroups (B * history_max >= 65,536 rows) and 4-wave ones, ragged
+    last tiles, empty histories (zero rows); a second run is bit-identical"""
+    from oracle import sasrec_oracle as SO
     monkeypatch.setenv("RC_SAS_LAST_ROW", "0")   # (as above: the all-rows kernels under test)
     rng = np.random.default_rng(77 * d + B)
-    n_items = 300
+    n_items, C = 300, 3
     P = _random_sasrec(rng, n_items, d, n_layers, L)
     lengths = rng.integers(0, L + 1, size=B).astype(np.int64)
-    lengths[0] = L
+    lengths[:2] = (L, 0)
     hist = rng.integers(1, n_items, size=(B, L)).astype(np.int64) * (np.arange(L)[None, :] < lengths[:, None])
+    iid = rng.integers(1, n_items, size=(B, C)).astype(np.int64)
+    gpred = rng.normal(size=(B, C)).astype(np.float32)
     Pd = to_dev(P, n_layers, cuda)
-    h_d, l_d = torch.from_numpy(hist).to(cuda), torch.from_numpy(lengths).to(cuda)
-    dhv = torch.from_numpy(rng.normal(size=(B, d)).astype(np.float32)).to(cuda)
-    out = {}
-    for mode in ("1", "0", "1"):
-        monkeypatch.setenv("RC_SAS_ROWS16", mode)
+    h_d, l_d, i_d, gp_d = (torch.from_numpy(x).to(cuda) for x in (hist, lengths, iid, gpred))
+    dhv = eng.weighted_row_sum(Pd["item_emb"], i_d, gp_d)
+    runs = []
+    for _ in range(2):
         hv, saved = eng.sasrec_fwd(Pd["item_emb"], Pd["pos_emb"], Pd["layers"], n_heads, h_d, l_d, save=True, impl="batch")
         g_hist, dg = eng.sasrec_bwd(Pd["layers"], n_heads, l_d, saved, dhv)
-        torch.cuda.synchronize()
-        res = (hv.cpu().numpy(), g_hist.cpu().numpy(), [{k: v.cpu().numpy() for k, v in g.items()} for g in dg])
-        if mode in out:
-            assert np.array_equal(res[0], out[mode][0]) and np.array_equal(res[1], out[mode][1])
-        out[mode] = res
+        runs.append((hv, g_hist, dg))
+    (hv, g_hist, dg), (hv_b, g_hist_b, dg_b) = runs
+    assert torch.equal(hv, hv_b) and torch.equal(g_hist, g_hist_b)
+    assert all(torch.equal(dg[l][k], dg_b[l][k]) for l in range(n_layers) for k in LAYER_NAMES)
     what = f"d={d} layers={n_layers} heads={n_heads} L={L} B={B}"
-    assert not np.array_equal(out["1"][1], out["0"][1]), what + ": the switch had no effect"
-    assert_close(out["1"][0], out["0"][0], what=what + " hv", rtol=2e-5, atol_scale=2e-5)
-    assert_close(out["1"][1], out["0"][1], what=what + " g_hist", rtol=5e-5, atol_scale=5e-5)
-    floor = 1e-6 * max(float(np.abs(v).max()) for g in out["0"][2] for v in g.values())
+    _, cache = SO.forward(P, hist, lengths, iid, n_heads, keep=True)
+    assert_close(hv.cpu().numpy(), cache["hv"], what=what + " hv", rtol=2e-5, atol_scale=3e-5)
+    _, G = SO.backward(P, hist, lengths, iid, n_heads, gpred)
+    floor = 1e-6 * max(float(np.abs(v).max()) for v in G.values())
     for l in range(n_layers):
-        for k in LAYER_NAMES:
-            assert_close(out["1"][2][l][k], out["0"][2][l][k], what=f"{what} layer {l} d{k}", rtol=5e-5, atol_scale=1e-4, abs_floor=floor)
-    assert np.all(out["1"][0][lengths == 0] == 0) and np.all(out["1"][1][lengths == 0] == 0)
+        for k, name in LAYER_NAMES.items():
+            assert_close(dg[l][k].cpu().numpy(), G["transformer_block.%d.%s" % (l, name)], what=f"{what} layer {l} d{k}",
+                         rtol=3e-5, atol_scale=1e-4, abs_floor=floor)
+    valid = (h_d > 0).to(torch.int64)
+    position = ((l_d[:, None] - torch.arange(L, device=cuda)[None, :]) * valid).contiguous()
+    GP = eng.embedding_dense_backward(g_hist, position, Pd["pos_emb"].shape[0])
+    assert_close(GP.cpu().numpy(), G["p_embeddings.weight"], what=what + " d pos_emb", rtol=3e-5, atol_scale=1e-4)
+    empty = torch.from_numpy(lengths == 0).to(cuda)
+    assert bool((hv[empty] == 0).all()) and bool((g_hist[empty] == 0).all())
 
 
 # (d, layers, heads, L, B, versions of the last-row path the shape is eligible for)
