@@ -1091,6 +1091,29 @@ int rc_lgcn_propagate_bwd(const rc_lgcn_graph* g, const float* grad_user, const 
                           float* buf_a, float* buf_b, float* partials, float* grad_user_emb, float* grad_item_emb,
                           rc_stream_t stream);
 
+/* ---- DirectAU alignment + uniformity loss (models/general/DirectAU.py:54-88) ----------------------------------------------------
+ * x^ = F.normalize(x) (x / max(|x|, 1e-12) per row), align = mean_b |u^_b - i^_b|^2 (:54-57), unif(X) = log mean_{i<j}
+ * exp(-2 |x^_i - x^_j|^2) (torch.pdist over the batch, :59-62), loss = align + gamma (unif(U) + unif(I)) / 2 (:80-86).
+ * The pairwise pass never stores the B x B matrix: per row it keeps s_i = sum_{j != i} e_ij and M_i = sum_{j != i} e_ij x^_j on
+ * fp32 MFMA, from which the backward pass forms -(4 / S)(s_i x^_i - M_i).  No float atomics: bitwise reproducible.
+ * RC_OK when d % 4 == 0, 4 <= d <= 256 and 1 <= batch <= 2^20, else RC_ERR_UNSUPPORTED with the reason in rc_last_error_string()
+ * (host logic, no GPU needed); the entry points below check the same envelope themselves.                                      */
+int rc_directau_check_shape(int d, int64_t batch);
+/* bytes of the caller workspace (256-byte aligned) for this shape; 0 outside the envelope */
+size_t rc_directau_workspace_bytes(int d, int64_t batch);
+/* forward: rows u = user_tab[uid[b]], i = item_tab[iid[b]] (uid / iid NULL: row b itself, i.e. tables of `batch` gathered rows),
+ * sets = bit mask of the uniformity terms to compute (1: users, 2: items; 3 for the loss, 0 for alignment alone).
+ * out [4] (device): loss, align, unif_user, unif_item (a term not computed reads 0; batch 1: every unif is NaN, as the mean of
+ * torch.pdist's empty result).  prediction [batch] or NULL: <u, i>, the training prediction of DirectAU.py:71.
+ * The workspace keeps what the backward pass reads: do not reuse it for another forward before that.                          */
+int rc_directau_fwd(const float* user_tab, const int64_t* uid, const float* item_tab, const int64_t* iid, int64_t batch, int d,
+                    float gamma, int sets, void* workspace, size_t ws_bytes, float* prediction, float* out, rc_stream_t stream);
+/* backward: grad_out [1] (device) the upstream gradient of the scalar, times coef_align d align + coef_unif_user d unif_user +
+ * coef_unif_item d unif_item (the loss: 1, gamma / 2, gamma / 2), mapped back through F.normalize -> per-occurrence row
+ * gradients grad_user / grad_item [batch, d] (either may be NULL); batch 1 carries the alignment term only, as torch does.     */
+int rc_directau_bwd(const float* grad_out, int64_t batch, int d, float coef_align, float coef_unif_user, float coef_unif_item,
+                    const void* workspace, size_t ws_bytes, float* grad_user, float* grad_item, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

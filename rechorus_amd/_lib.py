@@ -239,6 +239,10 @@ SIGNATURES = {
     "rc_lgcn_check_shape": (_i, [_i, _i, _i64, _i64]),
     "rc_lgcn_propagate_fwd": (_i, [_gp, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "rc_lgcn_propagate_bwd": (_i, [_gp, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "rc_directau_check_shape": (_i, [_i, _i64]),
+    "rc_directau_workspace_bytes": (_sz, [_i, _i64]),
+    "rc_directau_fwd": (_i, [_p, _p, _p, _p, _i64, _i, _f, _i, _p, _sz, _p, _p, _p]),
+    "rc_directau_bwd": (_i, [_p, _i64, _i, _f, _f, _f, _p, _sz, _p, _p, _p]),
 }
 
 _lib = None

@@ -39,6 +39,7 @@ SOURCES = [
     "eval_rank.hip",
     "owner_step.hip",
     "lgcn.hip",
+    "directau.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

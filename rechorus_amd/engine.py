@@ -2464,3 +2464,76 @@ def lgcn_propagate_bwd(graph, grad_user, grad_item, n_layers):
               _ptr(buf_b, torch.float32, "buf_b"), _ptr(parts, torch.float32, "partials"), _ptr(gu, torch.float32, "grad_user_emb"),
               _ptr(gi, torch.float32, "grad_item_emb"), _stream())
     return gu, gi
+
+
+# ---- DirectAU alignment + uniformity loss (models/general/DirectAU.py:54-88) -----------------------------------------------------
+
+def directau_check_shape(d, batch=1):
+    """rc_directau_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 1 <= batch <= 2^20; raises ValueError with the library's
+    reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_directau_check_shape(int(d), int(batch)) != _lib.RC_OK:
+        raise ValueError("DirectAU on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class DirectAUWorkspace:
+    """the scratch of rc_directau_fwd / _bwd, one buffer per (batch, d) that is never freed or moved while the owner lives: a
+    captured training step replays on the same memory.  `generation` counts forwards, so that a backward can tell whether another
+    forward has overwritten what it reads."""
+
+    def __init__(self):
+        self._bufs = {}
+        self.generation = 0
+
+    def get(self, batch, d, device):
+        key = (int(batch), int(d), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_directau_workspace_bytes(int(d), int(batch))
+            buf = self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return buf
+
+
+def _dau_rows(name, t, batch, d):
+    if t.dim() != 2 or t.shape[1] != d or (batch is not None and t.shape[0] != batch):
+        raise ValueError(f"directau: {name} must be [batch, {d}], got {tuple(t.shape)}")
+
+
+def directau_fwd(user_e, item_e, gamma=1.0, sets=3, workspace=None, user_ids=None, item_ids=None, prediction=False):
+    """rc_directau_fwd on rows user_e[user_ids] / item_e[item_ids] (ids None: the [B, d] rows themselves) -> (out [4] = loss, align,
+    unif_user, unif_item; prediction [B, 1] or None; the workspace buffer; its generation).  workspace: a DirectAUWorkspace that
+    persists (a model's, so that a captured step replays on the same memory); None: a fresh one for this call alone"""
+    d = user_e.shape[-1]
+    B = user_ids.numel() if user_ids is not None else user_e.shape[0]
+    directau_check_shape(d, B)
+    _dau_rows("user rows", user_e, None if user_ids is not None else B, d)
+    _dau_rows("item rows", item_e, None if item_ids is not None else B, d)
+    for name, ids in (("user_ids", user_ids), ("item_ids", item_ids)):
+        if ids is not None and ids.numel() != B:
+            raise ValueError(f"directau: {name} must hold {B} ids")
+    ws = workspace if workspace is not None else DirectAUWorkspace()   # None: a private one, alive as long as the caller keeps it
+    buf = ws.get(B, d, user_e.device)
+    ws.generation += 1
+    out = torch.empty(4, dtype=torch.float32, device=user_e.device)
+    pred = torch.empty((B, 1), dtype=torch.float32, device=user_e.device) if prediction else None
+    uid = user_ids.reshape(-1).contiguous() if user_ids is not None else None
+    iid = item_ids.reshape(-1).contiguous() if item_ids is not None else None
+    _lib.call("rc_directau_fwd", _ptr(user_e, torch.float32, "user_e"), _ptr(uid, torch.int64, "user_ids", allow_none=True),
+              _ptr(item_e, torch.float32, "item_e"), _ptr(iid, torch.int64, "item_ids", allow_none=True), B, d, float(gamma),
+              int(sets), C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(pred, torch.float32, "prediction", allow_none=True),
+              _ptr(out, torch.float32, "out"), _stream())
+    return out, pred, buf, ws.generation
+
+
+def directau_bwd(grad_out, batch, d, coef, buf, want_user=True, want_item=True):
+    """rc_directau_bwd: grad_out [] / [1] on the device, coef = (align, unif_user, unif_item) -> (grad_user [B, d] | None,
+    grad_item [B, d] | None), the per-occurrence row gradients"""
+    directau_check_shape(d, batch)
+    dev = buf.device
+    g = grad_out.reshape(1).to(torch.float32).contiguous()
+    gu = torch.empty((batch, d), dtype=torch.float32, device=dev) if want_user else None
+    gi = torch.empty((batch, d), dtype=torch.float32, device=dev) if want_item else None
+    _lib.call("rc_directau_bwd", _ptr(g, torch.float32, "grad_out"), int(batch), int(d), float(coef[0]), float(coef[1]),
+              float(coef[2]), C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(gu, torch.float32, "grad_user", allow_none=True),
+              _ptr(gi, torch.float32, "grad_item", allow_none=True), _stream())
+    return gu, gi

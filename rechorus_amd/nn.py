@@ -158,6 +158,50 @@ def lgcn_propagate(user_emb, item_emb, graph, n_layers):
     return _LgcnPropagateFn.apply(user_emb, item_emb, graph, int(n_layers))
 
 
+class _DirectAUFn(torch.autograd.Function):
+    """DirectAU's loss terms (models/general/DirectAU.py:54-88) on rc_directau_fwd / _bwd.  term "loss": align + gamma (unif(U) +
+    unif(I)) / 2; "align": alignment(x, y); "unif": uniformity(x) (x passed as both inputs, the item half not computed).  Backward:
+    the two [B, d] per-occurrence row gradients."""
+
+    _TERMS = {"loss": (3, 0), "align": (0, 1), "unif": (1, 2)}   # term -> (uniformity sets computed, slot of out[4])
+
+    @staticmethod
+    def forward(ctx, user_e, item_e, gamma, term, workspace):
+        sets, slot = _DirectAUFn._TERMS[term]
+        ws = workspace if workspace is not None else engine.DirectAUWorkspace()
+        out, _, buf, gen = engine.directau_fwd(user_e.detach(), item_e.detach(), gamma, sets=sets, workspace=ws)
+        ctx.buf, ctx.gen, ctx.workspace = buf, gen, ws
+        ctx.batch, ctx.d, ctx.term = user_e.shape[0], user_e.shape[1], term
+        ctx.coef = {"loss": (1.0, gamma / 2.0, gamma / 2.0), "align": (1.0, 0.0, 0.0), "unif": (0.0, 1.0, 0.0)}[term]
+        return out[slot]
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.workspace.generation != ctx.gen:
+            raise RuntimeError("DirectAU loss: another DirectAU forward ran on this workspace before this backward; give each "
+                               "pending loss a workspace of its own (rechorus_amd.engine.DirectAUWorkspace)")
+        unif = ctx.term == "unif"
+        gu, gi = engine.directau_bwd(g, ctx.batch, ctx.d, ctx.coef, ctx.buf, want_user=True, want_item=not unif)
+        return gu, gi, None, None, None
+
+
+def directau_loss(user_e, item_e, gamma, workspace=None):
+    """DirectAU.loss (models/general/DirectAU.py:80-86) on the rows [B, d] of one batch, as ONE autograd node; workspace: the
+    model's engine.DirectAUWorkspace, reused step after step (None: a fresh one for this call)"""
+    return _DirectAUFn.apply(user_e.contiguous(), item_e.contiguous(), float(gamma), "loss", workspace)
+
+
+def alignment(x, y, workspace=None):
+    """DirectAU.alignment (:54-57): mean_b |normalize(x_b) - normalize(y_b)|^2"""
+    return _DirectAUFn.apply(x.contiguous(), y.contiguous(), 0.0, "align", workspace)
+
+
+def uniformity(x, workspace=None):
+    """DirectAU.uniformity (:59-62): log mean_{i<j} exp(-2 |normalize(x_i) - normalize(x_j)|^2), without torch.pdist"""
+    x = x.contiguous()
+    return _DirectAUFn.apply(x, x, 0.0, "unif", workspace)
+
+
 class _BprLossFn(torch.autograd.Function):
     """GeneralModel.loss (models/BaseModel.py:182-185), closed-form backward."""
 

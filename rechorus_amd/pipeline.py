@@ -11,7 +11,7 @@ time-ordered histories (CSR) are uploaded once; per epoch one kernel samples all
 (rc_assemble_candidates, rc_gather_history).
 
 Only datasets whose feed dict is exactly one of the reference's standard ones are eligible (`dataset_kind()`:
-General, Sequential, Context top-k, Context CTR -- the latter two add the user / item / situation feature
+General (with sampled or, DirectAU's, empty training negatives), Sequential, Context top-k, Context CTR -- the latter two add the user / item / situation feature
 columns, gathered on the device from dense per-id tables); a model file that overrides `_get_feed_dict` /
 `collate_batch` keeps the DataLoader path.
 """
@@ -101,8 +101,9 @@ def history_csr(corpus, device, which=None):
 
 
 def dataset_kind(dataset):
-    """'general' | 'sequential' | 'context' | 'ctr' when the dataset produces exactly one of the reference's
-    standard feed dicts (so it can be assembled on the device), else None (DataLoader path)"""
+    """'general' | 'general_unsampled' | 'sequential' | 'context' | 'ctr' when the dataset produces exactly one of the
+    reference's standard feed dicts (so it can be assembled on the device), else None (DataLoader path).  'general_unsampled':
+    the general feed dict whose training negatives are empty lists (DirectAU); dev / test keep the reader's negatives."""
     from models.BaseModel import BaseModel, GeneralModel, SequentialModel  # plugin surface (on sys.path)
     from models.BaseModel import CTRModel
     from models.BaseContextModel import ContextCTRModel, ContextModel
@@ -115,6 +116,8 @@ def dataset_kind(dataset):
     sampled = cls.actions_before_epoch is GeneralModel.Dataset.actions_before_epoch
     if feed is GeneralModel.Dataset._get_feed_dict and sampled:
         return 'general'
+    if feed is GeneralModel.Dataset._get_feed_dict and _empty_train_negatives(cls):
+        return 'general_unsampled'
     if feed is SequentialModel.Dataset._get_feed_dict and sampled:
         return 'sequential'
     if feed is ContextModel.Dataset._get_feed_dict and sampled:
@@ -123,6 +126,13 @@ def dataset_kind(dataset):
     if feed in (ContextCTRModel.Dataset._get_feed_dict, CTRModel.Dataset._get_feed_dict) and unsampled:
         return 'ctr'
     return None
+
+
+def _empty_train_negatives(cls):
+    """the class that defines actions_before_epoch declares that it writes empty negative lists (DirectAU.Dataset): training
+    batches are (user, positive) only.  A subclass that overrides actions_before_epoch again does not inherit the declaration."""
+    owner = next(k for k in cls.__mro__ if 'actions_before_epoch' in k.__dict__)
+    return bool(owner.__dict__.get('empty_train_negatives', False))
 
 
 def _impression_kind(cls, feed):
@@ -222,6 +232,8 @@ class DeviceDataset:
         """all negatives of one epoch, like actions_before_epoch (models/BaseModel.py:206-214)"""
         if self.kind == 'ctr' or self.impression:  # labelled data / impressions bring their own negatives
             return None
+        if self.kind == 'general_unsampled':  # empty negative lists (DirectAU.Dataset.actions_before_epoch): nothing to draw
+            return None
         ptr, flat = clicked_csr(self.dataset.corpus, self.device, 'train')
         self.neg = engine.sample_negatives(self.users, self.num_neg, self.n_items, ptr, flat, seed=seed,
                                            base_index=self._draws, out=self.neg)
@@ -233,7 +245,8 @@ class DeviceDataset:
         B = idx.numel()
         if self.impression:
             return self._impression_feed(idx)
-        if self.kind == 'ctr':  # one labelled (user, item) pair per row (models/BaseModel.py:276-284)
+        if self.kind == 'ctr' or (self.kind == 'general_unsampled' and self.train):
+            # one labelled (user, item) pair per row (models/BaseModel.py:276-284) / a training row without negatives
             user_id, item_id = self.users[idx], self.items[idx, None]
         elif self.test_all:  # candidates = target + every item (models/BaseModel.py:194-195)
             user_id = self.users[idx]

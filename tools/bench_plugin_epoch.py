@@ -1,7 +1,7 @@
 """End-to-end epoch time THROUGH THE PLUGIN SURFACE (Reader -> Dataset -> BaseRunner.fit / evaluate), on a
 synthetic dataset with the row counts of the reference's demo dataset (Grocery_and_Gourmet_Food: 14,681
 users, 8,713 items, ~120 K training rows; docs/demo_scripts_results/README.md publishes 2.5 / 3.4 / 5.5 s
-per epoch for BPRMF / NeuMF / SASRec, 6.1 s for LightGCN, on an unnamed GPU).  Everything is included: negative sampling,
+per epoch for BPRMF / NeuMF / SASRec, 6.1 s for LightGCN, 3.3 s for DirectAU, on an unnamed GPU).  Everything is included: negative sampling,
 batch assembly, forward, loss, backward, optimizer, and the per-epoch dev evaluation."""
 import argparse
 import json
@@ -55,6 +55,7 @@ def main():
         ("NeuMF K=4 B=4096 Adam rowwise", "NeuMF", ["--emb_size", "64", "--layers", "[64]", "--num_neg", "4", "--batch_size", "4096", "--engine", "rowwise"]),
         ("SASRec L=20 H=1 K=1 B=256 Adam (demo flags)", "SASRec", ["--emb_size", "64", "--num_layers", "1", "--num_heads", "1", "--lr", "1e-4", "--l2", "1e-6", "--history_max", "20"]),
         ("LightGCN L=3 K=1 B=256 Adam (demo flags)", "LightGCN", ["--emb_size", "64", "--n_layers", "3", "--lr", "1e-3", "--l2", "1e-8"]),
+        ("DirectAU gamma=0.3 B=256 Adam (demo flags)", "DirectAU", ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-5", "--gamma", "0.3"]),
         ("SASRec L=50 H=4 K=99 B=4096 Adam rowwise", "SASRec", ["--emb_size", "64", "--num_layers", "1", "--num_heads", "4", "--history_max", "50", "--num_neg", "99", "--batch_size", "4096", "--engine", "rowwise"]),
     ]
     make_context_dataset(root, "ctr_like", n_users=3000, n_items=2000, per_user=44, ctr=True, seed=1)  # 120 K train rows
