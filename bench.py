@@ -6,7 +6,12 @@ catalogue, one GPU.  A "step" is one BaseRunner.fit iteration (forward, BPR loss
 optimizer row update) over one batch of B synthetic (user, pos, neg[K]) tuples whose ids are
 already resident in HBM.  Prints ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--opt SGD|Adam|Adagrad] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--opt SGD|Adam|Adagrad] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes its outputs if
+asked and prints the line.  --full adds what takes runs of its own after the timed steps: the live roofline and phase figures,
+the CPU baseline and, for the contract workload, the `secondary` legs of the other BASELINE configs (--no-roofline,
+--no-cpu-baseline and --no-secondary leave parts of that out).
 
 --dump-outputs DIR writes what the last timed step computed (loss, updated parameters; seeded row samples of the large
 tables) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
@@ -50,10 +55,13 @@ def parse():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--l2", type=float, default=0.0)
     ap.add_argument("--pool", type=int, default=8, help="distinct pre-generated batches (cycled)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline / phase figures, the CPU baseline and (the default "
+                         "contract workload) the secondary legs; a plain run prints the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline / phase figures")
     ap.add_argument("--cpu-steps", type=int, default=3,
-                    help="timed fit() iterations of the CPU baseline (after one untimed warm-up iteration)")
+                    help="timed fit() iterations of the CPU baseline (after one untimed warm-up iteration; --full)")
     ap.add_argument("--dropout", type=float, default=None,
                     help="deepfm: dropout of the deep tower (default 0.2 = docs/demo_scripts_results/CTR_MIND.sh:8); neumf: dropout of the "
                          "hidden layer (default 0)")
@@ -75,7 +83,7 @@ def parse():
                     help="N>1: row-sharded tables + owner-computes exchange (default), or independent replicas")
     ap.add_argument("--mlp", default="[512,64]", help="deepfm: hidden layers of the deep tower (CTR_MIND.sh:8)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="the contract workload only: skip the short legs of the other BASELINE configs that the default run attaches "
+                    help="the contract workload only: skip the short legs of the other BASELINE configs that --full attaches "
                          "as `secondary` (NeuMF at 10 M and 100 M items, SASRec, DeepFM at two batch sizes; N > 1: sharded NeuMF on the "
                          "100 M-item table)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -87,6 +95,8 @@ def parse():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_outputs and args.gpus != 1:
         ap.error("--dump-outputs: single GPU only (--gpus 1)")
+    if not args.full:   # a plain run: nothing after the timed steps but the line
+        args.no_roofline = args.no_cpu_baseline = args.no_secondary = True
     if args.dropout is None:
         args.dropout = 0.2 if args.workload == "deepfm" else 0.0
     if args.workload == "deepfm":  # configs[4]: the reference's CTR script shape unless overridden
@@ -654,7 +664,7 @@ def launch_ranks(n, argv=None, capture=False):
 # ---- secondary legs: the other BASELINE configs, short, attached to the contract line -------------------------------------
 
 def secondary_wanted(args):
-    """the default invocation of the contract workload carries the other configs; any explicit workload / shape does not"""
+    """--full on the contract workload carries the other configs; any explicit workload / shape does not"""
     return (not args.no_secondary and args.workload == "bprmf" and os.environ.get("RC_BENCH_LAUNCH_ONLY") != "1"
             and not args.graph and args.parallel == "sharded")
 
@@ -723,7 +733,7 @@ def secondary_single_gpu(args):
         # (cpu_s = what the leg's CPU iterations cost on the pool's boxes; the legs after this one still need ~2 s each)
         with_cpu = cpu_s is not None and left > cpu_s + 2.5 * (len(SECONDARY_LEGS) - len(out))
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", "20", "--warmup", "5"] + extra + \
-              (["--cpu-steps", "2"] if with_cpu else ["--no-cpu-baseline"]) + ["--no-secondary"]
+              (["--cpu-steps", "2"] if with_cpu else ["--no-cpu-baseline"]) + ["--full", "--no-secondary"]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=max(left, 10.0))
             j = _last_json(p.stdout)
@@ -738,7 +748,7 @@ def secondary_single_gpu(args):
 # (RC_BENCH_SECONDARY_ROWS="items,users": smaller tables for this leg -- the tests of the N > 1 code path on one GPU set it)
 _SEC_ITEMS, _SEC_USERS = (os.environ.get("RC_BENCH_SECONDARY_ROWS") or "100000001,10000001").split(",")
 SHARDED_LEG = ["--workload", "neumf", "--items", _SEC_ITEMS, "--users", _SEC_USERS, "--steps", "20", "--warmup", "5",
-               "--no-cpu-baseline", "--no-secondary"]
+               "--full", "--no-cpu-baseline", "--no-secondary"]
 
 
 def secondary_sharded_in_process(args, rank, world, device, dist):
@@ -821,8 +831,8 @@ def dump_outputs(outputs, path):
 
 
 def measure(args, rank, world, device, dist):
-    """one workload on the ranks of this job: warm-up, the timed steps between barriers, then (outside the timed region) the
-    live roofline phases and the CPU baseline -> the JSON object of the line"""
+    """one workload on the ranks of this job: warm-up, the timed steps between barriers, then (--full, outside the timed region)
+    the live roofline phases and the CPU baseline -> the JSON object of the line"""
     from rechorus_amd import engine
 
     batches = make_batches(args, device, seed=99 + rank) if args.workload not in ("sasrec", "deepfm") else None
@@ -1121,7 +1131,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if args.gpus > 1 and world == 1:
         # not started by a launcher: be the launcher.  The contract workload's ranks first; then -- its own rank group, so that a
-        # failure there cannot take the contract line with it -- the config-4 leg, attached as secondary.neumf_100M
+        # failure there cannot take the contract line with it -- with --full the config-4 leg, attached as secondary.neumf_100M
         if not secondary_wanted(args):
             raise SystemExit(launch_ranks(args.gpus)[0])
         rc, text = launch_ranks(args.gpus, sys.argv[1:] + ["--no-secondary"], capture=True)

@@ -68,7 +68,7 @@ def test_world_size_mismatch_is_refused():
 
 
 def test_secondary_leg_rules_and_the_launcher_that_captures_rank_zero(monkeypatch):
-    """host logic of the `secondary` object of the contract line: only the default contract workload carries the other configs;
+    """host logic of the `secondary` object of the contract line: only --full on the default contract workload carries the other configs;
     a leg contributes a summary, never its whole line; the launcher can hand rank 0's output back (it runs a second rank group
     for the sharded NeuMF leg and merges the two lines into ONE)"""
     import importlib.util
@@ -76,10 +76,13 @@ def test_secondary_leg_rules_and_the_launcher_that_captures_rank_zero(monkeypatc
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()      # a plain run: the headline figure only
+    assert not bench.secondary_wanted(a) and a.no_roofline and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
     a = bench.parse()
-    assert bench.secondary_wanted(a)
+    assert bench.secondary_wanted(a) and not a.no_roofline and not a.no_cpu_baseline
     for argv in (["--workload", "neumf"], ["--no-secondary"], ["--parallel", "replicas"], ["--graph"]):
-        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full"] + argv)
         assert not bench.secondary_wanted(bench.parse()), argv
     names = [n for n, _, _ in bench.SECONDARY_LEGS]
     assert names == ["neumf", "sasrec", "deepfm_b1024", "neumf_100M", "deepfm_b131072"]
@@ -95,11 +98,12 @@ def test_secondary_leg_rules_and_the_launcher_that_captures_rank_zero(monkeypatc
     monkeypatch.setattr(sys, "argv", ["bench.py", "--workload", "deepfm"])
     assert bench.parse().dropout == 0.2      # docs/demo_scripts_results/CTR_MIND.sh:8
     for _, extra, _ in bench.SECONDARY_LEGS:   # every leg parses, and none of them recurses
-        monkeypatch.setattr(sys, "argv", ["bench.py"] + extra + ["--no-secondary"])
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + extra + ["--full", "--no-secondary"])
         assert not bench.secondary_wanted(bench.parse())
     monkeypatch.setattr(sys, "argv", ["bench.py"] + bench.SHARDED_LEG)
     leg = bench.parse()
     assert (leg.workload, leg.items, leg.users, leg.emb_size, leg.num_neg, leg.opt) == ("neumf", 100_000_001, 10_000_001, 128, 4, "SGD")
+    assert leg.full and not leg.no_roofline and not bench.secondary_wanted(leg)
     j = {"metric": "m", "value": 2.0, "unit": "u", "ms_per_step": 0.5, "config": {"workload": "w", "n_items": 7}, "cpu_baseline": {"x": 1},
          "roofline": {"frac": 0.3}, "phases_ms": {"a": 1.0}}
     sm = bench._summary(j)

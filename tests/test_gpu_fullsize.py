@@ -240,24 +240,35 @@ def test_step_ahead_at_the_bench_batch_sample_vs_oracle(world, cuda):
 
 
 def test_bench_contract_line(cuda):
-    import os
-    """bench.py prints ONE JSON line with the driver's keys, the roofline object and the CPU baseline"""
+    """bench.py prints ONE JSON line with the contract keys; a plain run stops there, --full adds the roofline object, the CPU
+    baseline and the secondary legs"""
     import json
+    import os
     import subprocess
     import sys
     from conftest import ROOT
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "4096",
-                        "--items", "300001", "--users", "30001", "--cpu-steps", "1"], cwd=ROOT, capture_output=True, text=True,
-                       timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    lines = [l for l in p.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, lines
-    out = json.loads(lines[0])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+
+    def line(*extra):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "4096",
+                            "--items", "300001", "--users", "30001"] + list(extra), cwd=ROOT, capture_output=True, text=True,
+                           timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                  "vs_baseline", "dtype", "data", "config"):
+            assert k in out, k
+        assert out["n_gpus"] == 1 and out["steps"] == 4 and out["warmup"] == 2 and out["higher_is_better"] is True
+        assert out["vs_baseline"] is None and out["dtype"] == "f32" and out["data"] == "synthetic" and "workload" in out["config"]
+        assert out["value"] > 0 and abs(out["ms_per_step"] - 1e3 * 4096 / out["value"]) < 1e-6 * out["ms_per_step"]
+        return out
+
+    plain = line()
+    assert not {"roofline", "phases_ms", "cpu_baseline", "secondary"} & set(plain), sorted(plain)
+    out = line("--full", "--cpu-steps", "1")
+    for k in ("roofline", "cpu_baseline", "secondary"):
         assert k in out, k
-    assert out["n_gpus"] == 1 and out["steps"] == 4 and out["warmup"] == 2 and out["higher_is_better"] is True
-    assert out["vs_baseline"] is None and out["dtype"] == "f32" and out["data"] == "synthetic" and "workload" in out["config"]
     r = out["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert "traffic" in r and r["achieved"] > 0

@@ -208,7 +208,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(launcher, workload, extra, cuda):
     env["RC_BENCH_ONE_DEVICE"] = "1"
     env["RC_BENCH_SECONDARY_ROWS"] = "300001,30001"     # the config-4 leg of the contract workload's line, on small tables here
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dist-backend", "gloo",
-            "--workload", workload, "--no-cpu-baseline"] + extra
+            "--workload", workload, "--full", "--no-cpu-baseline"] + extra
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port())] + tail

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 run() {
   tag=$1; shift
-  env "$@" timeout 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline $BENCH_ARGS 2>/dev/null | python -c "
+  env "$@" timeout 200 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline $BENCH_ARGS 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.readline()); print('$tag', round(j['ms_per_step'],4), {k:round(v,4) for k,v in j['phases_ms'].items()})"
 }

@@ -4,7 +4,7 @@
 # Everything lands in gpurun_out/<tag>/.  Stages (any order, run in the order given):
 #   tests[:<pytest -k expr or file>]   pytest -m gpu (whole suite, or one file / -k expression)
 #   smoke                              __graft_entry__.smoke()
-#   bench[:<name>:<bench.py args>]     a bench line -> <name>.json      (plain `bench` = the driver's default command)
+#   bench[:<name>:<bench.py args>]     a bench line of `bench.py --full <args>` -> <name>.json
 #   ab:<name>:<ENV=V,ENV=V>:<args>     the same bench line with environment switches set (A/B inside one call)
 #   prof:<name>:<bench.py args>        rocprofv3 --kernel-trace --stats of a bench command -> prof_<name>/
 #   profenv:<name>:<ENV=V,..>:<args>   the same with environment switches set
@@ -71,14 +71,14 @@ for st in "$@"; do
       [ -z "$rest" ] && name=bench && args=""
       [ "$args" == "$rest" ] && args=""
       t0=$(date +%s.%N)
-      timeout 900 python bench.py $args > $OUT/$name.json 2> $OUT/$name.err
+      timeout 900 python bench.py --full $args > $OUT/$name.json 2> $OUT/$name.err
       echo "$name: $(python -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" | tee $OUT/$name.wall.txt
       summ $OUT/$name.json
       ;;
     ab)
       name=${rest%%:*}; r2=${rest#*:}; envs=${r2%%:*}; args=${r2#*:}
       [ "$args" == "$r2" ] && args=""
-      ( for kv in ${envs//,/ }; do export "$kv"; done; timeout 600 python bench.py $args > $OUT/$name.json 2> $OUT/$name.err )
+      ( for kv in ${envs//,/ }; do export "$kv"; done; timeout 600 python bench.py --full $args > $OUT/$name.json 2> $OUT/$name.err )
       summ $OUT/$name.json
       ;;
     prof)
