@@ -883,7 +883,7 @@ typedef struct rc_plan_row {
 
 /* 1 when a plan geometry exists: id-range buckets (ceil(range_a / 8192) + ceil(range_b / 8192) <= 4096; chosen when the
  * ids are dense enough, range <= 16 n) or hashed buckets with an LDS hash table per bucket (sparse or wider id spaces:
- * ids < 2^32 - 2, at most 8 M keys per list); else 0 -> use rc_sort_ids.  RC_PLAN_HASHED=0/1 forces a geometry (A/B). */
+ * ids < 2^32 - 2, at most 8 M keys per list); else 0 -> use rc_sort_ids.                                              */
 int rc_bucket_plan_supported(int64_t n_a, int64_t n_b, int64_t range_a, int64_t range_b);
 size_t rc_bucket_plan_workspace_bytes(int64_t n_a, int64_t n_b);
 size_t rc_bucket_plan_flags_bytes(int64_t n_a); /* size of single_a: n_a rounded up to whole 8,192-byte tiles */
@@ -976,8 +976,7 @@ size_t rc_bprmf_step_workspace_bytes(int B, int C, int d);
  * 1 = always the radix-sort pipeline, 2 = bucket plan on the caller's stream only, 3 = bucket plan on two streams
  * whatever the batch size.  1, 2, 3 give bit-identical tables; 0 equals them bit for bit on batches without rows of
  * more than 32 occurrences and to fp32 summation order otherwise (parity tests, A/B timing).  Returns the previous
- * setting; any other `mode` only queries.  Process-wide, initial value 0 (1 / 2 / 3 when the environment has
- * RC_BPRMF_STEP=sort / serial / plan).                                                                      */
+ * setting; any other `mode` only queries.  Process-wide, initial value 0.                                   */
 int rc_bprmf_step_pipeline(int mode);
 
 /* One BaseRunner.fit iteration for BPRMF (helpers/BaseRunner.py:193-206 with

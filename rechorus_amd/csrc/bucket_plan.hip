@@ -38,11 +38,6 @@ int device_cus() {
   return cus;
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
-
 PlanGeom plan_geometry(int64_t n_a, int64_t n_b, int64_t range_a, int64_t range_b, int want_mode) {
   PlanGeom g;
   memset(&g, 0, sizeof(g));
@@ -62,7 +57,7 @@ PlanGeom plan_geometry(int64_t n_a, int64_t n_b, int64_t range_a, int64_t range_
   // item lookups over 10 M - 100 M rows; a rank's lookups in a sharded table) or too wide for one direct level at all.
   const bool direct_ok = buckets(kPlanMaxShift, &na, &nbb) <= kPlanMaxBuckets;
   // want_mode 2: the wide id-range geometry or nothing (bitmap callers)
-  const int force = want_mode == 2 ? 0 : (want_mode >= 0 ? want_mode : env_int("RC_PLAN_HASHED", -1));
+  const int force = want_mode == 2 ? 0 : want_mode;
   const bool hashed = force >= 0 ? (force != 0 || !direct_ok) : (!direct_ok || range_a + range_b > 16 * g.n);
   if (hashed) {
     auto pow2_for = [](int64_t n_keys, int* lg) {
@@ -87,7 +82,7 @@ PlanGeom plan_geometry(int64_t n_a, int64_t n_b, int64_t range_a, int64_t range_
   }
   // dense batches (>= 4 keys per id of the tables): as many buckets as one level allows, i.e. as few ids per bucket as
   // possible -- narrow buckets, finished by ballot ranks
-  if (want_mode != 2 && env_int("RC_PLAN_NARROW", 1) != 0 && g.n >= 4 * (range_a + range_b)) {
+  if (want_mode != 2 && g.n >= 4 * (range_a + range_b)) {
     int sh = 0;
     while (buckets(sh, &na, &nbb) > kPlanMaxBuckets) ++sh;
     if (sh <= kPlanNarrowMaxShift) {
@@ -107,9 +102,7 @@ PlanGeom plan_geometry(int64_t n_a, int64_t n_b, int64_t range_a, int64_t range_
   int64_t want = g.n / 8192;
   if (want < 128) want = 128;
   if (want > 1024) want = 1024;
-  int shift = env_int("RC_PLAN_SHIFT", kPlanMaxShift);
-  if (shift > kPlanMaxShift) shift = kPlanMaxShift;
-  if (shift < kPlanMinShift) shift = kPlanMinShift;
+  int shift = kPlanMaxShift;
   while (shift > kPlanMinShift && buckets(shift, &na, &nbb) < want && buckets(shift - 1, &na, &nbb) <= kPlanMaxBuckets) --shift;
   while (buckets(shift, &na, &nbb) > kPlanMaxBuckets) ++shift;
   buckets(shift, &na, &nbb);

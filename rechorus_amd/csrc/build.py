@@ -1,6 +1,6 @@
 """Build librechorus_hip.so (gfx950) in-tree with hipcc.
 
-Usage:  python -m rechorus_amd.csrc.build [--force] [--no-dpp] [--resource-usage]
+Usage:  python -m rechorus_amd.csrc.build [--force] [--resource-usage]
 
 hipcc cross-compiles for gfx950 without a GPU.  Objects go to rechorus_amd/csrc/build/,
 the library to rechorus_amd/librechorus_hip.so (git-ignored, shipped to the GPU box by
@@ -89,16 +89,14 @@ def _write_info(hipcc, flag_str):
                    "sources": SOURCES}, f, indent=1)
 
 
-def build(force=False, no_dpp=False, resource_usage=False, verbose=True, defines=()):
+def build(force=False, resource_usage=False, verbose=True, defines=()):
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     # -ffp-contract=off: only the fmaf() calls written in the kernels fuse, so every template
     # instantiation of the same expression rounds identically (bit-reproducible across paths)
     flags = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function",
              "-ffp-contract=off"]
-    if no_dpp:
-        flags.append("-DRC_NO_DPP")
-    flags += ["-D" + d for d in defines]
+    flags +=["-D" + d for d in defines]
     if resource_usage:
         flags.append("-Rpass-analysis=kernel-resource-usage")
     tag = os.path.join(OBJ_DIR, ".flags")
@@ -141,8 +139,7 @@ def build(force=False, no_dpp=False, resource_usage=False, verbose=True, defines
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--no-dpp", action="store_true", help="debug: DPP reductions via ds_bpermute")
     ap.add_argument("--resource-usage", action="store_true")
-    ap.add_argument("--define", action="append", default=[], help="extra -D (experiment switches, e.g. RC_NT)")
+    ap.add_argument("--define", action="append", default=[], help="extra -D (experiment switches, e.g. RC_X_TIMING)")
     a = ap.parse_args()
-    build(force=a.force, no_dpp=a.no_dpp, resource_usage=a.resource_usage, defines=a.define)
+    build(force=a.force, resource_usage=a.resource_usage, defines=a.define)

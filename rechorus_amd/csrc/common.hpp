@@ -73,20 +73,9 @@ constexpr int kMaxGridX = 1 << 30;
 //   row_half_mirror = 0x141, row_mirror = 0x140.
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float x) {
-#ifdef RC_NO_DPP
-  // debugging fall-back: same permutations through ds_bpermute
-  const int lane = __lane_id();
-  int src = lane;
-  if (CTRL == 0xB1) src = lane ^ 1;
-  else if (CTRL == 0x4E) src = lane ^ 2;
-  else if (CTRL == 0x141) src = (lane & ~7) | (7 - (lane & 7));
-  else if (CTRL == 0x140) src = (lane & ~15) | (15 - (lane & 15));
-  return __shfl(x, src, 64);
-#else
   int xi = __float_as_int(x);
   int r = __builtin_amdgcn_update_dpp(xi, xi, CTRL, 0xF, 0xF, false);
   return __int_as_float(r);
-#endif
 }
 
 // all-reduce (sum) over the LPR consecutive lanes that share one table row.
@@ -167,15 +156,11 @@ __device__ __forceinline__ float wave_allreduce_max(float x) {
   return x;
 }
 
-// streaming row load: read-once table rows; non-temporal (measured: fused BPRMF kernel 0.739 -> 0.629 ms; -DRC_NO_NT restores plain accesses)
+// streaming row load: read-once table rows; non-temporal (measured: fused BPRMF kernel 0.739 -> 0.629 ms against plain accesses)
 __device__ __forceinline__ float4 load_stream4(const float4* p) {
-#if !defined(RC_NO_NT) && !defined(RC_NO_NT_LOAD)
   typedef float v4f __attribute__((ext_vector_type(4)));
   const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
 }
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) {

@@ -43,14 +43,11 @@ __device__ __forceinline__ float tuple_allreduce_max(float x) {
 // candidate evaluates the loss terms (ceil(C / S) per lane instead of CPL), the gradient scalars g_c
 // return through the same strip and are broadcast-read by the lane-groups for the backward pass.
 // Slot order in the strip: s = grp * CPL + j  <->  candidate c = j * GS + grp.
-#ifndef RC_FUSED_MINW
-#define RC_FUSED_MINW 3
-#endif
 // waves per SIMD the register allocation must allow: the candidate block (CPL float4 = 4 CPL VGPRs) is the
 // floor; the stateful singleton paths keep their per-slot gradient scalars as well
 template <int CPL_, int MODE_>
 constexpr int fused_min_waves() {
-  return (MODE_ == MODE_ADAM || MODE_ == MODE_ADAGRAD) ? (CPL_ >= 20 ? 2 : 3) : (CPL_ >= 26 ? 2 : (CPL_ >= 20 ? RC_FUSED_MINW : 4));
+  return (MODE_ == MODE_ADAM || MODE_ == MODE_ADAGRAD) ? (CPL_ >= 20 ? 2 : 3) : (CPL_ >= 26 ? 2 : (CPL_ >= 20 ? 3 : 4));
 }
 // The body of the fused kernel for workgroup `block` of NT threads (the stand-alone kernel: NT = kBlock and its own
 // workgroup index; the small-batch step, small_step.hip, runs it in the upper part of a merged grid).  ub: optional

@@ -841,18 +841,6 @@ __global__ __launch_bounds__(kBlock) void mlp_reduce_wave_kernel(const float* __
 
 static bool vec4_ok(const MlpOperand& o) { return reinterpret_cast<uintptr_t>(o.p) % 16 == 0 && o.ld % 4 == 0; }
 
-// RC_MLP_BIG=0: 64 x 64 tiles for every product (round 2), for A/B timing
-static bool mlp_big_enabled() {
-  const char* v = getenv("RC_MLP_BIG");
-  return !(v && v[0] == '0');
-}
-
-// RC_MLP_BIG2=0: the first 128 x 128 kernel for every large product (A/B timing)
-static bool mlp_big2_enabled() {
-  const char* v = getenv("RC_MLP_BIG2");
-  return !(v && v[0] == '0');
-}
-
 // dynamic LDS beyond 64 KB needs the attribute, once per (device, kernel variant)
 static int b2_set_lds_limit(const void* kern, int variant, size_t lds) {
   static std::mutex mu;
@@ -872,10 +860,10 @@ static int mlp_launch(const MlpGemm& g, int splits, hipStream_t s, bool want_big
   // 128 x 128 tiles once they fill the chip (>= 2048 of them, 8 per CU: below that the 64 x 64 tiles' finer grain wins -- B = 16,384:
   // 1.05 against 1.14 ms per step) and the product is at least a tile wide
   const int64_t mt = (g.M + kBigBM - 1) / kBigBM, nt = (ncols + kBigBN - 1) / kBigBN;
-  if (mlp_big_enabled() && g.M >= kBigBM && ncols >= kBigBN && (mt * nt * splits >= 2048 || want_big2) && mt < (1 << 24)) {
+  if (g.M >= kBigBM && ncols >= kBigBN && (mt * nt * splits >= 2048 || want_big2) && mt < (1 << 24)) {
     const int64_t bn = g.ones_col >= 0 ? (int64_t)g.ones_col : (int64_t)g.N;
     const bool steps_complete = g.K % kB2K == 0 && (splits == 1 ? g.k_total == g.K : (g.split_stride_k == g.K && g.k_total % kB2K == 0));
-    if (mlp_big2_enabled() && vec4_ok(g.A) && vec4_ok(g.B) && steps_complete && (g.B.k_major || bn % 4 == 0) && g.K >= kB2K &&
+    if (vec4_ok(g.A) && vec4_ok(g.B) && steps_complete && (g.B.k_major || bn % 4 == 0) && g.K >= kB2K &&
         mt * nt * (int64_t)((splits + 7) / 8 * 8) < (1 << 28)) {
       const size_t lds = 4 * (size_t)kB2Tile * sizeof(float);
       void (*kern)(MlpGemm, int, int, int) =
@@ -901,7 +889,7 @@ static int mlp_launch(const MlpGemm& g, int splits, hipStream_t s, bool want_big
 // The weight-gradient product of a large batch on the 128 x 128 tiles (mlp_gemm_big2_kernel, the tiles of a split side by side
 // on one XCD): at most two workgroups per CU -- one round --, a multiple of eight splits.  0 = stays on the 64 x 64 tiles.
 static int mlp_dw_big_splits(int64_t M, int N, int K) {
-  if (!mlp_big_enabled() || !mlp_big2_enabled() || M < 16384 || M % kB2K != 0 || N < 128 || K < 127 || K % 4 != 0 || N % 4 != 0) return 0;
+  if (M < 16384 || M % kB2K != 0 || N < 128 || K < 127 || K % 4 != 0 || N % 4 != 0) return 0;
   const int64_t tiles = ((int64_t)(N + 127) / 128) * ((K + 1 + 127) / 128);
   int64_t s = 512 / tiles / 8 * 8;   // one round of two workgroups per CU, a multiple of eight splits (one XCD each)
   const int64_t max_s = M / 1024;   // at least 32 K steps per split
@@ -927,11 +915,6 @@ static int mlp_splits(int64_t M, int N, int K) {
 // 16 / s steps; the partial products [s][M][N] are summed in split order (no float atomics) by a second launch that also applies
 // bias, ReLU and dropout.  1 = no split (enough tiles, or a short reduction).
 static int mlp_k_splits(int64_t M, int N, int K) {
-  static const int mode = [] {   // RC_MLP_SPLITK=0: no split-K of the forward / dX products (A/B)
-    const char* v = getenv("RC_MLP_SPLITK");
-    return (v && v[0] == '0') ? 0 : 1;
-  }();
-  if (mode == 0) return 1;
   const int64_t tiles = ((M + kMlpBM - 1) / kMlpBM) * ((N + kMlpBN - 1) / kMlpBN);
   if (tiles >= 256 || K < 128) return 1;
   int64_t s = (512 + tiles - 1) / tiles;
@@ -968,19 +951,15 @@ __global__ __launch_bounds__(kBlock) void mlp_split_epilogue_kernel(MlpGemm g, c
   }
 }
 
-// one product C = A . B with its epilogue in `g`, through split-K when `part` (room for mlp_k_splits planes) is given
-// RC_MLP_SMALL=0: the 64 x 64 tiles (+ split-K) for every small product (A/B)
+// the small-tile kernel (mlp_gemm_small_kernel) where the 64 x 64 tiles would leave the chip half empty
 static bool mlp_small_ok(const MlpGemm& g) {
-  static const int mode = [] {
-    const char* v = getenv("RC_MLP_SMALL");
-    return (v && v[0] == '0') ? 0 : 1;
-  }();
-  if (mode == 0 || g.ones_col >= 0 || !g.A.k_major || g.k_total != g.K || g.K % kSmBK != 0 || g.K < 2 * kSmBK) return false;
+  if (g.ones_col >= 0 || !g.A.k_major || g.k_total != g.K || g.K % kSmBK != 0 || g.K < 2 * kSmBK) return false;
   if (!vec4_ok(g.A) || !vec4_ok(g.B) || (!g.B.k_major && g.N % 4 != 0)) return false;
   const int64_t tiles64 = ((g.M + kMlpBM - 1) / kMlpBM) * ((g.N + kMlpBN - 1) / kMlpBN);
   return tiles64 < 512 && g.N >= 16;      // (beyond that the 64 x 64 tiles fill the chip by themselves)
 }
 
+// one product C = A . B with its epilogue in `g`, through split-K when `part` (room for mlp_k_splits planes) is given
 static int mlp_product(MlpGemm g, float* part, hipStream_t s) {
   if (mlp_small_ok(g)) {
     dim3 grid((unsigned)((g.M + kSmBM - 1) / kSmBM), (unsigned)((g.N + kSmBN - 1) / kSmBN), 1);

@@ -501,15 +501,6 @@ __global__ __launch_bounds__(64 * kFwd16Waves) void neumf_fwd16_kernel(NeumfArgs
   }
 }
 
-// RC_NEUMF_FWD16=0: the 64-candidate-tile kernel for the forward pass as well (A/B timing)
-static bool neumf_fwd16_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("RC_NEUMF_FWD16");
-    return !(v && v[0] == '0');
-  }();
-  return on;
-}
-
 template <int D, int L1>
 static int launch_neumf_fwd16(const NeumfArgs& a, hipStream_t s) {
   const size_t lds_bytes = ((size_t)L1 * (2 * D + 4) + L1 + D + L1) * sizeof(float);
@@ -555,19 +546,15 @@ static int neumf_grid(int64_t n, int d, int l1) {
   return (int)(g < 1 ? 1 : g);
 }
 
+// the forward pass without dropout runs on 16-candidate tiles (neumf_fwd16_kernel), everything else on 64-candidate tiles
 template <bool BWD>
 static int dispatch_neumf(const NeumfArgs& a, int d, int l1, int n_wg, hipStream_t s) {
-  if (!BWD && !a.seed_dev && neumf_fwd16_enabled()) {   // forward without dropout: 16-candidate tiles
-#define RC_NF(D_, L_) \
-  if (d == D_ && l1 == L_) return launch_neumf_fwd16<D_, L_>(a, s)
-    RC_NF(32, 32); RC_NF(32, 64); RC_NF(32, 128);
-    RC_NF(64, 32); RC_NF(64, 64); RC_NF(64, 128);
-    RC_NF(128, 32); RC_NF(128, 64);
-#undef RC_NF
+#define RC_NM(D_, L_)                                                         \
+  if (d == D_ && l1 == L_) {                                                  \
+    if (a.seed_dev) return launch_neumf<D_, L_, BWD, true>(a, n_wg, s);      \
+    if constexpr (BWD) return launch_neumf<D_, L_, true, false>(a, n_wg, s); \
+    else return launch_neumf_fwd16<D_, L_>(a, s);                            \
   }
-#define RC_NM(D_, L_) \
-  if (d == D_ && l1 == L_)                                                                 \
-    return a.seed_dev ? launch_neumf<D_, L_, BWD, true>(a, n_wg, s) : launch_neumf<D_, L_, BWD, false>(a, n_wg, s)
   RC_NM(32, 32); RC_NM(32, 64); RC_NM(32, 128);
   RC_NM(64, 32); RC_NM(64, 64); RC_NM(64, 128);
   RC_NM(128, 32); RC_NM(128, 64);

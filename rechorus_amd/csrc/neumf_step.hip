@@ -527,17 +527,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
           for (int e = 0; e < 4; ++e) mx[cc][e] = mn[cc][e];
         const int64_t item_c = it0;
-#ifdef RC_NEUMF_FLAG_LATE     // (experiment switch: the flag requested where it is used, as before)
-        const uint8_t mflag = a.multi ? a.multi[item_c] : (uint8_t)1;
-#else
         const uint8_t mflag = mflag_next;
-#endif
         it0 = it1;
         if (c + 1 < C) {
           load_row_slices<NCU>(mn, a.mf_i + it0 * a.ld_i + 4 * g);
-#ifndef RC_NEUMF_FLAG_LATE
           mflag_next = a.multi ? a.multi[it0] : (uint8_t)1;
-#endif
           it1 = ip[c + 2 < C ? c + 2 : C - 1];
         }
         const float gc = sp[c * 16 + i];
@@ -699,12 +693,7 @@ int device_cus();   // bucket_plan.hip
 
 static int step_grid(int B) {
   const int64_t rounds = ((int64_t)B + 63) / 64;
-  static const int per_cu = [] {
-    const char* v = getenv("RC_NEUMF_STEP_WGS_PER_CU");   // workgroups per CU over the launch (A/B: partial size vs balance)
-    const int k = (v && *v) ? atoi(v) : 1;
-    return k < 1 ? 1 : k;
-  }();
-  int64_t grid = (int64_t)device_cus() * per_cu;
+  int64_t grid = device_cus();
   if (grid > rounds) grid = rounds;
   return (int)(grid < 1 ? 1 : grid);
 }

@@ -179,10 +179,7 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
   constexpr int LPR = D / 4;
   constexpr int GPW = 64 / LPR;   // lane-groups per wave
   constexpr int H = 2;            // rows per lane-group per step
-#ifndef RC_PLAN_IDX_OCC
-#define RC_PLAN_IDX_OCC 4
-#endif
-  constexpr uint32_t kIdxOcc = RC_PLAN_IDX_OCC;   // occurrences per row resolved in the index phase (2: the round-4 kernel, for A/B)
+  constexpr uint32_t kIdxOcc = 4;   // occurrences per row resolved in the index phase
   const PlanSide& sd = a.side[side];
   const PlanGrad& gr = sd.g;
   const int lane = threadIdx.x & 63;
@@ -197,11 +194,6 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
     rc_plan_row e;
     e.row = 0; e.start = 0; e.n = 0; e.reserved = 0;
     if (gi < nr) e = sd.rows[gi];
-#ifdef RC_X_SKIP_PAIR_ROWS
-    // EXPERIMENT ONLY (wrong results): rows with exactly two occurrences are dropped -- the upper bound of what this launch would save
-    // if they were resolved inside the fused kernel (profiles/r09_bprmf_pair_ticket_negative.txt)
-    if (e.n == 2) e.n = 0;
-#endif
     const bool shortrow = e.n >= 1 && e.n <= (uint32_t)kPlanLongSeg;
     // the first FOUR occurrences of the row are resolved here (64 rows' chains together); a row's fifth and later ones walk the
     // chain on their own in the data phase.  (With two, a third occurrence -- 17 % of the multi-occurrence rows of config 2, so
@@ -210,8 +202,8 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
     if (shortrow) {
       o0 = a.occ[e.start];
       if (e.n > 1) o1 = a.occ[e.start + 1];
-      if (kIdxOcc > 2 && e.n > 2) o2 = a.occ[e.start + 2];
-      if (kIdxOcc > 3 && e.n > 3) o3 = a.occ[e.start + 3];
+      if (e.n > 2) o2 = a.occ[e.start + 2];
+      if (e.n > 3) o3 = a.occ[e.start + 3];
     }
     float c0 = 1.0f, c1 = 1.0f, c2 = 1.0f, c3 = 1.0f;
     typedef int64_t src_row_t;     // (32-bit source rows: the same 108 registers)
@@ -225,8 +217,8 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
       };
       resolve(o0, c0, s0);
       if (e.n > 1) resolve(o1, c1, s1);
-      if (kIdxOcc > 2 && e.n > 2) resolve(o2, c2, s2);
-      if (kIdxOcc > 3 && e.n > 3) resolve(o3, c3, s3);
+      if (e.n > 2) resolve(o2, c2, s2);
+      if (e.n > 3) resolve(o3, c3, s3);
     }
     // ---- data phase: GPW * H rows per step
     for (int r0 = 0; r0 < 64; r0 += GPW * H) {
@@ -267,8 +259,8 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
           if (mode_has_v(MODE)) v[h] = load_stream4(reinterpret_cast<const float4*>(sd.t.V) + idx4[h]);
           u0[h] = src4[(size_t)sh0[h] * LPR + l];
           if (eh[h].n > 1) u1[h] = src4[(size_t)sh1[h] * LPR + l];
-          if (kIdxOcc > 2 && eh[h].n > 2) u2[h] = src4[(size_t)sh2[h] * LPR + l];
-          if (kIdxOcc > 3 && eh[h].n > 3) u3[h] = src4[(size_t)sh3[h] * LPR + l];
+          if (eh[h].n > 2) u2[h] = src4[(size_t)sh2[h] * LPR + l];
+          if (eh[h].n > 3) u3[h] = src4[(size_t)sh3[h] * LPR + l];
         }
       }
 #pragma unroll
@@ -284,12 +276,12 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
           t.x *= ch1[h]; t.y *= ch1[h]; t.z *= ch1[h]; t.w *= ch1[h];
           padd4(acc, t);
         }
-        if (kIdxOcc > 2 && eh[h].n > 2) {
+        if (eh[h].n > 2) {
           float4 t = u2[h];
           t.x *= ch2[h]; t.y *= ch2[h]; t.z *= ch2[h]; t.w *= ch2[h];
           padd4(acc, t);
         }
-        if (kIdxOcc > 3 && eh[h].n > 3) {
+        if (eh[h].n > 3) {
           float4 t = u3[h];
           t.x *= ch3[h]; t.y *= ch3[h]; t.z *= ch3[h]; t.w *= ch3[h];
           padd4(acc, t);
@@ -330,16 +322,9 @@ __device__ __forceinline__ void plan_long_only_body(const PlanUpdArgs& a, int si
 template <int D>
 __device__ __forceinline__ void plan_chunk_body(const PlanUpdArgs& a, uint32_t first_block, uint32_t n_blocks, float4* part);
 
-// RC_ROWS_WAVES_MAX (experiment switch): cap the waves per SIMD of the row-update kernel, so that a CU keeps wave slots
-// free for the plan kernels of the NEXT batch that run beside it on the second stream
-#ifdef RC_ROWS_WAVES_MAX
-#define RC_ROWS_OCC __attribute__((amdgpu_waves_per_eu(1, RC_ROWS_WAVES_MAX)))
-#else
-#define RC_ROWS_OCC
-#endif
 template <int D, int MODE>
-__global__ __launch_bounds__(kBlock) RC_ROWS_OCC void plan_rows_kernel(PlanUpdArgs a, uint32_t blocks_main, int update_side,
-                                                                      int plan_other, uint32_t blocks_chunk) {
+__global__ __launch_bounds__(kBlock) void plan_rows_kernel(PlanUpdArgs a, uint32_t blocks_main, int update_side,
+                                                           int plan_other, uint32_t blocks_chunk) {
   __shared__ float4 part[kBlock];   // chunk workgroups only
   const bool plan_long = a.long_planned == 0;
   if (blockIdx.x < blocks_main) {

@@ -228,11 +228,10 @@ __device__ __forceinline__ float4 occ_grad4(const SegArgs& a, int64_t jj, int l)
   return occ_grad4_o<D>(a, a.perm[jj], l);
 }
 
-// ONLY_MULTI: the list holds only heads with >= 2 occurrences (singletons were updated by
-// the fused BPRMF kernel), so the first two gradient rows are always fetched together.
+// One head per lane-group, every head of the list.
 // Dependent-load depth: heads[g] -> {keys[j], keys[j+1], perm[j], perm[j+1]} ->
 // {W row, coef, index} -> {src rows} -> store.
-template <int D, int MODE, bool ONLY_MULTI>
+template <int D, int MODE>
 __global__ __launch_bounds__(kBlock) void seg_update_kernel(SegArgs a) {
   constexpr int LPR = D / 4;
   constexpr int GPB = kBlock / LPR;
@@ -259,7 +258,7 @@ __global__ __launch_bounds__(kBlock) void seg_update_kernel(SegArgs a) {
   }
   const float4 w = load_row4<D, MODE>(a, key, l);
   float4 acc = occ_grad4_o<D>(a, o0, l);
-  if (ONLY_MULTI || multi) {
+  if (multi) {
     const float4 s1 = occ_grad4_o<D>(a, o1, l);
     add4(acc, s1);
     int64_t jj = j + 2;
@@ -279,7 +278,8 @@ __global__ __launch_bounds__(kBlock) void seg_update_kernel(SegArgs a) {
   apply_row4<D, MODE>(a, key, l, w, acc);
 }
 
-// Two heads per lane-group (ONLY_MULTI lists: every head has >= 2 occurrences).  The kernel is bound by
+// Two heads per lane-group (lists without singletons -- those were updated by the fused BPRMF kernel -- so
+// every head has >= 2 occurrences and its first two gradient rows are fetched together).  The kernel is bound by
 // the latency of its dependent gathers (head -> keys/perm -> coef/index -> source row), not by bandwidth:
 // interleaving two independent heads doubles the loads in flight per lane.  Same summation order per row as
 // seg_update_kernel, so results are bit-identical.
@@ -302,10 +302,7 @@ __device__ __forceinline__ bool seg_tail(const SegArgs& a, int64_t j, uint32_t k
   return false;
 }
 
-#ifndef RC_SEG_HPG
-#define RC_SEG_HPG 2
-#endif
-constexpr int kSegHpg = RC_SEG_HPG;  // heads per lane-group
+constexpr int kSegHpg = 2;  // heads per lane-group
 
 template <int D, int MODE>
 __global__ __launch_bounds__(kBlock) void seg_update_multi_x2_kernel(SegArgs a) {
@@ -1250,17 +1247,12 @@ static int launch_seg(const SegArgs& a, hipStream_t s) {
   const int64_t max_heads = a.skip_single ? (a.n_occ + 1) / 2 : a.n_occ;
   const int64_t blocks = (max_heads + GPB - 1) / GPB;
   if (blocks > kMaxGridX) return fail(RC_ERR_UNSUPPORTED, "seg_update: grid too large");
-#ifndef RC_SEG_X1
   if (a.skip_single) {
     const int64_t blocks2 = (max_heads + kSegHpg * GPB - 1) / (kSegHpg * GPB);
     hipLaunchKernelGGL((seg_update_multi_x2_kernel<D, MODE>), dim3((unsigned)blocks2), dim3(kBlock), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((seg_update_kernel<D, MODE>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
   }
-#else
-  if (a.skip_single)
-    hipLaunchKernelGGL((seg_update_kernel<D, MODE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-#endif
-  else
-    hipLaunchKernelGGL((seg_update_kernel<D, MODE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
   RC_LAUNCH_CHECK();
   if (a.n_occ > kLongSeg) {  // otherwise no segment can be long
     hipLaunchKernelGGL(long_plan_kernel, dim3(64), dim3(kBlock), 0, s, a);

@@ -7,8 +7,8 @@
 // Three pipelines (rc_bprmf_step_pipeline):
 //   small batches (<= 32,768 row ids)   two launches: small_step.hip
 //   bucket plan (default otherwise)     partition -> [flags] -> fused kernel || per-bucket pass on a second stream
-//                                       -> row updates; with rc_bprmf_train_step_ahead the front of the NEXT batch runs
-//                                       beside this step's row updates
+//                                       -> row updates; with rc_bprmf_train_step_ahead the whole plan of the NEXT batch
+//                                       runs beside this step on the second stream
 //   sort pipeline (wide id spaces)      joint radix sort -> segment heads -> fused kernel -> segmented updates
 // phase_ms slots (all pipelines): [0] sort / partition (+ flags) [7] segment heads / per-bucket pass when on the caller's
 // stream [2] fused kernel [3] loss mean (0 when folded into the last update launch) [4] item-row update [5] user-row update.
@@ -41,8 +41,8 @@ int small_step_launch(float* U, float* I, float* mU, float* vU, float* mI, float
 // that only the updates need; the fused kernel needs at most the multi-occurrence bitmap.  So the step forks: the fused
 // kernel runs on the caller's stream while plan_launch_back runs on this side stream, and the updates wait for both.
 // One record per device, created on first use (non-blocking stream: the caller's stream may be the legacy null
-// stream); fork / join are event dependencies, so the call stays capturable in a hipGraph.  RC_BPRMF_STEP=serial keeps
-// everything on one stream.  These are resources (a stream, four events), not batch state: what was prepared for which
+// stream); fork / join are event dependencies, so the call stays capturable in a hipGraph.  rc_bprmf_step_pipeline(2)
+// keeps everything on one stream.  These are resources (a stream, four events), not batch state: what was prepared for which
 // batch lives in the CALLER's rc_step_ticket.
 namespace {
 struct StepSide {
@@ -61,50 +61,13 @@ StepSide* step_side(int* device_out = nullptr) {
   StepSide& x = sides[dev];
   if (!x.tried) {
     x.tried = true;
-    // RC_SIDE_PRIO=high: the side stream's workgroups are dispatched ahead of the caller's whenever a CU has room
-    // (the plan kernels are latency-bound index work that has to squeeze in beside bandwidth-bound row kernels)
-    const char* pr = getenv("RC_SIDE_PRIO");
-    bool made = false;
-    if (pr && strcmp(pr, "high") == 0) {
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-        made = hipStreamCreateWithPriority(&x.stream, hipStreamNonBlocking, greatest) == hipSuccess;
-    }
-    x.ok = (made || hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking) == hipSuccess) &&
+    x.ok = hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking) == hipSuccess &&
            hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&x.join, hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&x.fork2, hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&x.front_done, hipEventDisableTiming) == hipSuccess;
   }
   return x.ok ? &x : nullptr;
-}
-// where the look-ahead plan of the next batch is forked off: 1 = at the start of the step (default: the plan's chain of
-// latency-bound kernels stretches about 2.5 x beside the bandwidth-bound row kernels and needs the whole step as its
-// window -- 0.988 -> 0.945 ms/step at config 2, profiles/r03d_ab_overlap.txt), 0 = behind the fused kernel (beside this
-// step's row updates only); RC_AHEAD_FORK=late selects 0
-bool ahead_bitmap_in_bucket() {   // RC_AHEAD_BITMAP=separate: the bitmap kernel of the front for the look-ahead plan as well (A/B)
-  static int on = [] {
-    const char* v = getenv("RC_AHEAD_BITMAP");
-    return (v && strcmp(v, "separate") == 0) ? 0 : 1;
-  }();
-  return on != 0;
-}
-int ahead_fork_mode() {
-  static int mode = [] {
-    const char* v = getenv("RC_AHEAD_FORK");
-    return (v && strcmp(v, "late") == 0) ? 0 : 1;
-  }();
-  return mode;
-}
-// what the look-ahead prepares: 0 = the whole plan (default), 1 = only its front (partition + bitmap: what the fused
-// kernel needs); the per-bucket pass then runs on the side stream beside the fused kernel of the step that uses it
-// (RC_AHEAD_PART=front)
-int ahead_part_mode() {
-  static int mode = [] {
-    const char* v = getenv("RC_AHEAD_PART");
-    return (v && strcmp(v, "front") == 0) ? 1 : 0;
-  }();
-  return mode;
 }
 }  // namespace
 
@@ -213,12 +176,9 @@ PlanArgs slot_plan_args(const StepWs& w, int k, const int64_t* uid, const int64_
 
 // 0 = automatic (two-launch step for small batches; else the bucket plan, its per-bucket pass on a second stream behind
 // the fused kernel), 1 = always the sort pipeline, 2 = bucket plan on ONE stream, 3 = bucket plan on two streams whatever
-// the batch size; initial value from RC_BPRMF_STEP=sort|serial|plan
+// the batch size; 0 until rc_bprmf_step_pipeline sets another
 static int& step_pipeline() {
-  static int mode = [] {
-    const char* v = getenv("RC_BPRMF_STEP");
-    return (v && strcmp(v, "sort") == 0) ? 1 : ((v && strcmp(v, "serial") == 0) ? 2 : ((v && strcmp(v, "plan") == 0) ? 3 : 0));
-  }();
+  static int mode = 0;
   return mode;
 }
 
@@ -274,17 +234,11 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
   // (a hashed plan geometry -- very wide / sparse id spaces -- has no id-indexed bitmap: every row is listed then)
   const bool want_bitmap = rc_bprmf_fused_supported(d, C) != 0 && h->opt == RC_OPT_SGD;   // -> id-range buckets if at all possible
   const PlanGeom geom = plan_geometry(n_i, B, n_items, n_users, want_bitmap ? 0 : -1);
-#if defined(RC_FUSED_UPD_NEVER)
-  const bool fused_upd = false;
-#elif defined(RC_FUSED_UPD_ALWAYS)
-  const bool fused_upd = rc_bprmf_fused_supported(d, C) != 0 && !geom.hashed && !geom.narrow;
-#else
   // (narrow geometry = dense batch, several occurrences per row of the table: hardly any row occurs once, the singleton
   //  fast path has nothing to win there)
   const bool fused_upd = rc_bprmf_fused_supported(d, C) != 0 && h->opt == RC_OPT_SGD && !geom.hashed && !geom.narrow;
-#endif
-  // what a prepared plan contains: 1 = bitmap + multi rows, 2 = every row listed, 3 = only the front of flavour 1
-  const int flavour = fused_upd ? (ahead_part_mode() == 1 ? 3 : 1) : 2;
+  // what a prepared plan contains: 1 = bitmap + multi rows, 2 = every row listed
+  const int flavour = fused_upd ? 1 : 2;
 
   // A plan prepared ahead by an earlier call (rc_step_ticket, caller-owned): usable when it was made for exactly this
   // batch -- the caller's generation id, not a pointer, says so -- workspace, geometry and plan flavour.  In every case
@@ -304,7 +258,7 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
   }
 
   // Pipeline choice: the bucket plan (bucket_plan.hip + plan_update.hip) where the register-resident
-  // fused kernel exists and the joint id space fits one bucket level; otherwise (and with RC_BPRMF_STEP=sort)
+  // fused kernel exists and the joint id space fits one bucket level; otherwise (and in pipeline mode 1)
   // the round-1 pipeline: joint radix sort -> segment heads -> fused -> segmented updates.
   const bool force_sort = step_pipeline() == 1;
   const bool fused_ok = rc_bprmf_fused_supported(d, C) != 0;
@@ -332,32 +286,8 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
       hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
       look_ahead = hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
     }
-    auto launch_ahead = [&]() -> int {
-      PlanArgs pn = slot_plan_args(w, 1 - slot, next_uid, next_iid, n_i, B, n_users, n_items, geom, fused_upd);
-      RC_HIP(hipEventRecord(side->fork2, s));
-      RC_HIP(hipStreamWaitEvent(side->stream, side->fork2, 0));
-      // a plan prepared as a whole: the bucket kernel writes the multi-occurrence bitmap from the counts it holds anyway
-      // (the separate bitmap launch zeroes and counts every bucket a second time: 0.06 ms beside the row kernels)
-      const bool whole = flavour != 3 && fused_upd && !geom.hashed && !geom.narrow && ahead_bitmap_in_bucket();
-      pn.bitmap_in_bucket = whole ? 1 : 0;
-      RC_TRY(plan_launch_front(pn, fused_upd && !whole, side->stream));
-      if (flavour != 3) RC_TRY(plan_launch_back(pn, side->stream));
-      RC_HIP(hipEventRecord(side->front_done, side->stream));
-      ticket->generation = next_generation;
-      ticket->ws = reinterpret_cast<uintptr_t>(ws);
-      ticket->slot = 1 - slot; ticket->device = device; ticket->B = B; ticket->C = C; ticket->d = d;
-      ticket->flavour = flavour; ticket->n_users = n_users; ticket->n_items = n_items;
-      return RC_OK;
-    };
     RC_MARK(0);
-    if (ahead_hit && flavour == 3) {
-      // the front is prepared; the per-bucket pass runs on the side stream beside this step's fused kernel
-      RC_MARK(1);
-      RC_HIP(hipEventRecord(side->fork, s));
-      RC_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-      RC_TRY(plan_launch_back(pa, side->stream));
-      RC_HIP(hipEventRecord(side->join, side->stream));
-    } else if (ahead_hit) {
+    if (ahead_hit) {
       // the plan is complete (prepared beside the previous step): this step starts with its fused kernel
       RC_MARK(1);
     } else if (two_streams) {
@@ -376,7 +306,24 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
       RC_MARK(1);   // after the partition (+ bitmap), before the bucket kernel
       RC_TRY(plan_launch_back(pa, s));
     }
-    if (look_ahead && ahead_fork_mode() == 1) RC_TRY(launch_ahead());
+    // The look-ahead is forked here, in front of the fused kernel: the plan's chain of latency-bound kernels stretches
+    // about 2.5 x beside the bandwidth-bound row kernels and needs the whole step as its window (0.988 -> 0.945 ms/step
+    // at config 2 against a fork behind the fused kernel, profiles/r03d_ab_overlap.txt).
+    if (look_ahead) {
+      PlanArgs pn = slot_plan_args(w, 1 - slot, next_uid, next_iid, n_i, B, n_users, n_items, geom, fused_upd);
+      RC_HIP(hipEventRecord(side->fork2, s));
+      RC_HIP(hipStreamWaitEvent(side->stream, side->fork2, 0));
+      // a plan prepared as a whole: the bucket kernel writes the multi-occurrence bitmap from the counts it holds anyway
+      // (the separate bitmap launch zeroes and counts every bucket a second time: 0.06 ms beside the row kernels)
+      pn.bitmap_in_bucket = fused_upd ? 1 : 0;   // (fused_upd implies an id-range geometry: neither hashed nor narrow)
+      RC_TRY(plan_launch_front(pn, false, side->stream));
+      RC_TRY(plan_launch_back(pn, side->stream));
+      RC_HIP(hipEventRecord(side->front_done, side->stream));
+      ticket->generation = next_generation;
+      ticket->ws = reinterpret_cast<uintptr_t>(ws);
+      ticket->slot = 1 - slot; ticket->device = device; ticket->B = B; ticket->C = C; ticket->d = d;
+      ticket->flavour = flavour; ticket->n_users = n_users; ticket->n_items = n_items;
+    }
     RC_MARK(2);
     RC_MARK(3);
     if (fused_upd)
@@ -384,8 +331,7 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
                                             w.gpred, w.ugrad, stream));
     else
       RC_TRY(rc_bprmf_fwd_bwd(U, I, uid, iid, B, C, d, inv_b, pred, w.loss_vec, w.gpred, w.ugrad, stream));
-    if (two_streams && (!ahead_hit || flavour == 3)) RC_HIP(hipStreamWaitEvent(s, side->join, 0));
-    if (look_ahead && ahead_fork_mode() == 0) RC_TRY(launch_ahead());
+    if (two_streams && !ahead_hit) RC_HIP(hipStreamWaitEvent(s, side->join, 0));
     RC_MARK(4);
     RC_MARK(5);  // (the loss mean is one workgroup of the last update launch)
     RC_TRY(plan_bprmf_step_updates(U, mU, vU, I, mI, vI, d, uid, C, n_i, B, w.gpred, w.ugrad, pa.rows_a, pa.n_rows_a,

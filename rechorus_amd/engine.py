@@ -1170,10 +1170,7 @@ class NeumfTrainer:
         two_streams = _NEUMF_OVERLAP and iid.numel() >= _SAS_OVERLAP_MIN
         main = torch.cuda.current_stream(dev)
         if two_streams and self._side is None:
-            # RC_NEUMF_PLAN_PRIORITY=1: the plan's stream above the others (its small latency-bound kernels then go first where the
-            # update kernels compete for the same CUs)
-            prio = -1 if os.environ.get("RC_NEUMF_PLAN_PRIORITY", "0") == "1" else 0
-            self._side, self._side2 = torch.cuda.Stream(device=dev, priority=prio), torch.cuda.Stream(device=dev)
+            self._side, self._side2 = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
         ahead = getattr(self, "_ahead", None)
         self._ahead = None
         plan = plan_done = marks_done = None

@@ -9,7 +9,7 @@ in device memory (HipOptimizer(capturable=True), rc_dense_update_multi_dev), so 
 across replays.  Eligibility is decided by the runner (helpers/BaseRunner.py): host-free forward
 (no host-side candidate shuffle; torch's dropout replays with a fresh Philox offset), HipOptimizer, CUDA tensors.
 
-ROCm caveat (measured on ROCm 7.0 / MI355X, repro: tools/repro_hipgraph_fault.py): with the runtime's
+ROCm caveat (measured on ROCm 7.0 / MI355X): with the runtime's
 default "AQL packet capture" fast path for graphs, ONE device-to-host copy on the default stream between
 two launches of an instantiated graph (a `.item()` on any tensor, e.g. the epoch loss) makes the next
 launch fault ("Memory access fault by GPU").  DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 selects the runtime's

@@ -1,5 +1,4 @@
-"""rc_bucket_plan alone at the bench shape (run under rocprofv3 --kernel-trace --stats for per-kernel times).
-RC_PLAN_DEBUG=1|2|4 (timing experiments: drop the occ stores / the flag stores / pass 2 of the bucket kernel)."""
+"""rc_bucket_plan alone at the bench shape (run under rocprofv3 --kernel-trace --stats for per-kernel times)."""
 import ctypes as C
 import os
 import sys
