@@ -242,25 +242,20 @@ int rc_bprmf_fwd_bwd(const float* U, const float* I, const int64_t* uid,
 int rc_bprmf_fused_supported(int d, int C);
 
 /* rc_bprmf_fwd_bwd that ALSO applies the optimizer `h` to every item row occurring exactly
- * once in the batch (single[b*C+c] != 0, from rc_segment_heads): such a row is read by no
- * other tuple, its whole gradient g[b,c]*U[uid[b]] is known while the row is still in
+ * once in the batch: such a row is read by no other tuple, its whole gradient g[b,c]*U[uid[b]] is known while the row is still in
  * registers, so it is updated and written back here -- one HBM read and one write per step.
  * Rows with several occurrences are left for rc_segmented_update(RC_SEG_SKIP_SINGLETONS).
- * I (and mI, vI) are updated in place; the arithmetic is the one of rc_segmented_update.   */
+ * I (and mI, vI) are updated in place; the arithmetic is the one of rc_segmented_update.
+ * The singleton information comes in exactly ONE of two forms (the other NULL; both or neither: RC_ERR_INVALID_ARG):
+ *   single  one flag per position, single[b*C+c] != 0 (from rc_segment_heads);
+ *   multi   a bitmap over item ids (rc_bucket_multi_bitmap / the bucket plan of rc_bprmf_train_step): a row is updated
+ *           here iff its bit is 0.  The kernel looks the tuple's candidates up in the bitmap itself (L2-resident), so no
+ *           per-position flag array crosses HBM.                                                                       */
 int rc_bprmf_fwd_bwd_update(const float* U, float* I, float* mI, float* vI,
-                            const int64_t* uid, const int64_t* iid, const uint8_t* single,
+                            const int64_t* uid, const int64_t* iid, const uint8_t* single, const uint32_t* multi,
                             int B, int C, int d, float inv_b, const rc_opt_hyper* h,
                             float* pred, float* loss_vec, float* gpred, float* ugrad,
                             rc_stream_t stream);
-
-/* The same with the singleton information as a bitmap over item ids (rc_bucket_multi_bitmap / the bucket plan of
- * rc_bprmf_train_step): a row is updated here iff its bit is 0.  The kernel looks the tuple's candidates up in the
- * bitmap itself (L2-resident), so no per-position flag array crosses HBM.                                     */
-int rc_bprmf_fwd_bwd_update_bitmap(const float* U, float* I, float* mI, float* vI,
-                                   const int64_t* uid, const int64_t* iid, const uint32_t* multi,
-                                   int B, int C, int d, float inv_b, const rc_opt_hyper* h,
-                                   float* pred, float* loss_vec, float* gpred, float* ugrad,
-                                   rc_stream_t stream);
 
 /* ---- index sort (the atomic-free replacement of embedding_dense_backward's index_add) */
 
@@ -275,7 +270,7 @@ int rc_sort_ids(const int64_t* ids, int64_t n, int64_t n_rows, uint32_t* keys_ou
 /* Two id lists sorted in ONE call as the virtual concatenation [ids_a ; key_offset_b + ids_b]
  * (keys < key_range).  With key_offset_b >= every id of list a, the first n_a sorted positions are
  * list a's segment and the tail is list b's (perm values n_a .. n_a+n_b-1): a BPRMF step sorts its
- * item and user ids together and hands the two slices to rc_segmented_update2(key_base, occ_base). */
+ * item and user ids together and hands the two slices to rc_segmented_update(key_base, occ_base). */
 int rc_sort_ids2(const int64_t* ids_a, int64_t n_a, const int64_t* ids_b, int64_t n_b,
                  int64_t key_offset_b, int64_t key_range, uint32_t* keys_out, uint32_t* perm_out,
                  void* ws, size_t ws_bytes, rc_stream_t stream);
@@ -306,14 +301,20 @@ size_t rc_segmented_workspace_bytes(int64_t n_occ, int d);
  * RC_SEG_SKIP_SINGLETONS is given) -- saves re-deriving it.
  * flags: RC_SEG_SKIP_SINGLETONS leaves rows with exactly one occurrence untouched (they
  * were updated by rc_bprmf_fwd_bwd_update).
- * Src must not alias W.  ws from rc_segmented_workspace_bytes(n_occ, d).              */
+ * Src must not alias W.  ws from rc_segmented_workspace_bytes(n_occ, d).
+ * A SECOND gradient source: occurrences o >= n_split take the plain row
+ * src2[o - n_split, :] instead of coef[o]*Src[srow(o)] (one source: src2 = NULL, n_split = n_occ).  SASRec updates its
+ * item table from the candidates (g[b,c] * encoder output, rebuilt on the fly) and from the history positions
+ * (gradient rows written by the encoder backward) in ONE pass, so the optimizer sees each row once.
+ * key_base / occ_base: keys and perm may be a SLICE of a joint sort (rc_sort_ids2): the table row
+ * is keys[j] - key_base, the occurrence index perm[j] - occ_base (0, 0 for a plain sort).           */
 enum rc_seg_flags { RC_SEG_SKIP_SINGLETONS = 1 };
 int rc_segmented_update(float* W, float* m, float* v, int d, const uint32_t* keys,
-                        const uint32_t* perm, int64_t n_occ, const float* coef,
-                        const float* src, const int64_t* src_index, int div,
-                        const rc_opt_hyper* h, float* dense_grad, const uint32_t* heads,
-                        const uint32_t* n_heads, int flags, void* ws, size_t ws_bytes,
-                        rc_stream_t stream);
+                        const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
+                        const int64_t* src_index, int div, const float* src2, int64_t n_split,
+                        int64_t key_base, int64_t occ_base, const rc_opt_hyper* h,
+                        float* dense_grad, const uint32_t* heads, const uint32_t* n_heads, int flags,
+                        void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* Exact dense optimizer step over all n elements (torch.optim semantics incl. weight
  * decay on every element, helpers/BaseRunner.py:110-114,206).  m/v as above.         */
@@ -323,16 +324,13 @@ int rc_dense_update(float* W, const float* G, float* m, float* v, int64_t n,
 /* The same step over n_tensors tensors in one launch per 36 tensors (a model's whole optimizer.step()):
  * W, G, m, v, n and h are HOST arrays of length n_tensors (m / v may be NULL for SGD; h[t] carries the
  * tensor's lr and weight decay -- 'bias' parameters have l2 = 0, models/BaseModel.py:64-73 -- all h[t].opt
- * equal).  Element arithmetic identical to rc_dense_update.                                              */
+ * equal).  Element arithmetic identical to rc_dense_update.
+ * step_dev != NULL is the hipGraph-capturable form: for Adam the step count t is read from DEVICE memory (step_dev, int64) and
+ * the bias corrections 1 - beta^t are derived in the kernel (h[t].step is ignored), so a captured training step
+ * replays correctly; rc_step_increment bumps the counter on the stream.  step_dev NULL: t = h[t].step.           */
 int rc_dense_update_multi(float* const* W, const float* const* G, float* const* m, float* const* v,
-                          const int64_t* n, const rc_opt_hyper* h, int n_tensors, rc_stream_t stream);
-
-/* hipGraph-capturable variant: for Adam the step count t is read from DEVICE memory (step_dev, int64) and the
- * bias corrections 1 - beta^t are derived in the kernel (h[t].step is ignored), so a captured training step
- * replays correctly; rc_step_increment bumps the counter on the stream.  step_dev NULL = rc_dense_update_multi. */
-int rc_dense_update_multi_dev(float* const* W, const float* const* G, float* const* m, float* const* v,
-                              const int64_t* n, const rc_opt_hyper* h, int n_tensors, const int64_t* step_dev,
-                              rc_stream_t stream);
+                          const int64_t* n, const rc_opt_hyper* h, int n_tensors, const int64_t* step_dev,
+                          rc_stream_t stream);
 int rc_step_increment(int64_t* step_dev, rc_stream_t stream);
 /* the same for two counters in one launch (a tower's dropout seed and Adam's step count of the same training step) */
 int rc_step_increment2(int64_t* a_dev, int64_t* b_dev, rc_stream_t stream);
@@ -341,7 +339,7 @@ int rc_step_increment2(int64_t* a_dev, int64_t* b_dev, rc_stream_t stream);
  * gradient: tensor t is [n[t] / row_w[t], row_w[t]] with one int32 flag per row, and a row whose flag equals (int32) step_dev[0]
  * was looked up by this step's batch (rc_gather_fields_pair_mark); only those rows of G[t] hold (and are read for) a gradient, the
  * rest of G[t] is never read -- so nothing zero-fills it.  touched = 2: every row takes its Adam step, g = G's row where stamped
- * and 0 elsewhere (Adam still decays m, v and steps along m there): bit-identical to rc_dense_update_multi_dev on a zero-filled
+ * and 0 elsewhere (Adam still decays m, v and steps along m there): bit-identical to rc_dense_update_multi (step_dev) on a zero-filled
  * dense gradient.  touched = 0 / 1 are the two halves of that pass -- the unstamped rows with g = 0 (G[t] may be NULL) / the
  * stamped rows from G[t] -- for a caller that wants them on different streams.  flags[t] == NULL makes tensor t a plain tensor
  * (all of it updated from G[t] whatever `touched`).  Adam only; step count in device memory, already incremented for this step.
@@ -356,40 +354,24 @@ int rc_stage_batch(const int64_t* a, int64_t na, const int64_t* b, int64_t nb, c
 
 /* ---- whole BPRMF training step ----------------------------------------------------- */
 
-/* rc_segmented_update with a SECOND gradient source: occurrences o >= n_split take the plain row
- * src2[o - n_split, :] instead of coef[o]*Src[srow(o)].  SASRec updates its item table from the
- * candidates (g[b,c] * encoder output, rebuilt on the fly) and from the history positions
- * (gradient rows written by the encoder backward) in ONE pass, so the optimizer sees each row once.
- * key_base / occ_base: keys and perm may be a SLICE of a joint sort (rc_sort_ids2): the table row
- * is keys[j] - key_base, the occurrence index perm[j] - occ_base (0, 0 for a plain sort).           */
-int rc_segmented_update2(float* W, float* m, float* v, int d, const uint32_t* keys,
-                         const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
-                         const int64_t* src_index, int div, const float* src2, int64_t n_split,
-                         int64_t key_base, int64_t occ_base, const rc_opt_hyper* h,
-                         float* dense_grad, const uint32_t* heads, const uint32_t* n_heads, int flags,
-                         void* ws, size_t ws_bytes, rc_stream_t stream);
-
-/* rc_segmented_update2 for a table of n_rows rows that collect MANY occurrences each -- a small catalogue under a
+/* rc_segmented_update for a table of n_rows rows that collect MANY occurrences each -- a small catalogue under a
  * large batch, the reference's own datasets (8.7 K items against 0.5 M candidate + history occurrences of one SASRec
  * step, models/sequential/SASRec.py:51-86 with helpers/BaseRunner.py:193-206): one pass over the sorted keys (plain
  * rc_sort_ids, keys < n_rows) records each row's [start, end), then ONE wave per table row sums its occurrences
  * (fixed order, no float atomics) and applies `h` / writes dense_grad; rows with more than 192 occurrences take the
  * 256-occurrence chunks of rc_segmented_update.  Gradient sources and outputs as there; d in {16, 32, 64, 128, 256},
- * buffers 16-byte aligned.  Worth it from about eight occurrences per table row.                               */
+ * buffers 16-byte aligned.  Worth it from about eight occurrences per table row.
+ * step_dev != NULL: Adam's step count t is read from device memory when the kernels run (step_dev[0] >= 1; h->step is not used; the
+ * bias corrections 1 - beta^t are formed in the kernel with fill-in-double arithmetic like the host's): the launch can be
+ * captured in a hipGraph and replayed while rc_step_increment advances the counter, as rc_dense_update_multi does for
+ * the dense parameters (torch.optim.Adam(capturable=True) semantics, helpers/BaseRunner.py:110-114,206).  step_dev NULL: the
+ * step count is h->step.  SGD / Adagrad: step_dev has no effect.                                                               */
 size_t rc_segmented_rows_workspace_bytes(int64_t n_rows, int64_t n_occ, int d);
 int rc_segmented_update_rows(float* W, float* m, float* v, int d, int64_t n_rows, const uint32_t* keys,
                              const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
                              const int64_t* src_index, int div, const float* src2, int64_t n_split,
-                             const rc_opt_hyper* h, float* dense_grad, void* ws, size_t ws_bytes, rc_stream_t stream);
-/* The same with Adam's step count t read from device memory when the kernels run (step_dev[0] >= 1; h->step is not used; the
- * bias corrections 1 - beta^t are formed in the kernel with fill-in-double arithmetic like the host's): the launch can be
- * captured in a hipGraph and replayed while rc_step_increment advances the counter, as rc_dense_update_multi_dev does for
- * the dense parameters (torch.optim.Adam(capturable=True) semantics, helpers/BaseRunner.py:110-114,206).  SGD / Adagrad: as above. */
-int rc_segmented_update_rows_dev(float* W, float* m, float* v, int d, int64_t n_rows, const uint32_t* keys,
-                                 const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
-                                 const int64_t* src_index, int div, const float* src2, int64_t n_split,
-                                 const rc_opt_hyper* h, const int64_t* step_dev, float* dense_grad, void* ws, size_t ws_bytes,
-                                 rc_stream_t stream);
+                             const rc_opt_hyper* h, const int64_t* step_dev, float* dense_grad, void* ws, size_t ws_bytes,
+                             rc_stream_t stream);
 
 /* rc_segmented_update_rows without the radix sort: the per-row [start, end) and the grouped occurrence list come from a counting
  * sort of the batch's own id tensors, as the reference hands them over (models/sequential/SASRec.py:69-81: feed_dict['item_id']
@@ -399,7 +381,7 @@ int rc_segmented_update_rows_dev(float* W, float* m, float* v, int d, int64_t n_
  * touched rows (its gradient row is zero).  rc_rows_plan_build: three launches (tile histograms in LDS, prefix over the tiles,
  * scatter in occurrence order = the stable sort's order, so that every row sum is bit-identical to the sorted route; the hot
  * rows' chunk list is written on the way), no host synchronisation, capturable.  rc_rows_plan_update: rc_segmented_update_rows
- * on that plan in two launches (n_split = n_a; step_dev as rc_segmented_update_rows_dev, null: h->step).  n_rows <= 12,288;
+ * on that plan in two launches (n_split = n_a; step_dev as rc_segmented_update_rows, null: h->step).  n_rows <= 12,288;
  * ids outside [0, n_rows) take no part and are counted in status[0] (rc_rows_plan_views; the caller zeroes the workspace once).   */
 int rc_rows_plan_supported(int64_t n_rows, int64_t n_occ, int d);
 size_t rc_rows_plan_workspace_bytes(int64_t n_rows, int64_t n_occ, int d);
@@ -520,34 +502,27 @@ int rc_sasrec_bwd(const float* const* layer_params, int n_layers, int n_heads, c
  * his_vector = his[arange(B), lengths - 1]; causal mask): one query row per sequence and -- for 1 / 2 / 4 heads and
  * max(3, heads + 1) <= L <= 64 -- no keys and values at all (score_j = (Wk_h^T q_h) . x_j, ctx_h = Wv_h sum_j p_j x_j: one pass
  * over the layer input rows per direction; with one block the rows come straight from the tables and g_hist is written
- * directly), mirrored in the backward -- same results to fp32 rounding (the products are associated differently).               */
-size_t rc_sasrec_batch_state_floats(int B, int L, int d, int n_layers);
-size_t rc_sasrec_batch_workspace_bytes(int B, int L, int d, int n_layers);
-int rc_sasrec_batch_fwd(const float* item_emb, const float* pos_emb, const float* const* layer_params,
-                        int n_layers, int n_heads, const int64_t* hist, const int64_t* lengths, int B, int L,
-                        int d, float* hv, float* state, void* ws, size_t ws_bytes, rc_stream_t stream);
-int rc_sasrec_batch_bwd(const float* const* layer_params, int n_layers, int n_heads, const int64_t* lengths,
-                        int B, int L, int d, const float* state, const float* dhv, float* g_hist,
-                        float* dense_grads, void* ws, size_t ws_bytes, rc_stream_t stream);
-
-/* Training mode with --dropout p (utils/layers.py:104,110 dropout1 on the attention context, :114,117 dropout2 on the
+ * directly), mirrored in the backward -- same results to fp32 rounding (the products are associated differently).
+ * Training mode with --dropout p (utils/layers.py:104,110 dropout1 on the attention context, :114,117 dropout2 on the
  * FFN output; SASRec.py:47-49 passes the model's --dropout).  The mask is never stored: element (compact row r,
  * feature f) of site s = 2 * layer + {0: dropout1, 1: dropout2} is dropped iff word (f & 3) of
  * Philox4x32-10(key = *seed_dev, counter = (r, s * d/4 + (f >> 2))) < p * 2^32, kept values are scaled by 1/(1-p);
  * r = (sum of min(len, L) over the sequences before b) + position.  The LayerNorm kernels of both passes
  * regenerate it; the caller bumps *seed_dev once per step (rc_step_increment, capturable).  As for NeuMF, parity
  * with the reference is exact given the mask (tests/golden/sasrecdrop_*.npz: the reference in training mode with
- * its nn.Dropout modules swapped for this mask) and distributional in the mask.  p = 0 (seed_dev may be NULL) is
- * rc_sasrec_batch_fwd / rc_sasrec_batch_bwd bit for bit.                                                       */
-int rc_sasrec_batch_fwd_dropout(const float* item_emb, const float* pos_emb, const float* const* layer_params,
-                                int n_layers, int n_heads, const int64_t* hist, const int64_t* lengths, int B,
-                                int L, int d, float drop_p, const uint64_t* seed_dev, float* hv, float* state,
-                                void* ws, size_t ws_bytes, rc_stream_t stream);
-int rc_sasrec_batch_bwd_dropout(const float* const* layer_params, int n_layers, int n_heads,
-                                const int64_t* lengths, int B, int L, int d, float drop_p,
-                                const uint64_t* seed_dev, const float* state, const float* dhv, float* g_hist,
-                                float* dense_grads, void* ws, size_t ws_bytes, rc_stream_t stream);
-/* rc_sasrec_batch_bwd_dropout in two calls, for a caller that lets the item-table update start (on another stream) as soon as the
+ * its nn.Dropout modules swapped for this mask) and distributional in the mask.  drop_p = 0 (seed_dev may be NULL):
+ * no dropout (evaluation, or --dropout 0).                                                                     */
+size_t rc_sasrec_batch_state_floats(int B, int L, int d, int n_layers);
+size_t rc_sasrec_batch_workspace_bytes(int B, int L, int d, int n_layers);
+int rc_sasrec_batch_fwd(const float* item_emb, const float* pos_emb, const float* const* layer_params,
+                        int n_layers, int n_heads, const int64_t* hist, const int64_t* lengths, int B,
+                        int L, int d, float drop_p, const uint64_t* seed_dev, float* hv, float* state,
+                        void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_sasrec_batch_bwd(const float* const* layer_params, int n_layers, int n_heads,
+                        const int64_t* lengths, int B, int L, int d, float drop_p,
+                        const uint64_t* seed_dev, const float* state, const float* dhv, float* g_hist,
+                        float* dense_grads, void* ws, size_t ws_bytes, rc_stream_t stream);
+/* rc_sasrec_batch_bwd in two calls, for a caller that lets the item-table update start (on another stream) as soon as the
  * history rows' gradient g_hist is complete while the encoder's parameter gradients are still being formed: part 1 = every launch
  * up to and including the one that completes g_hist, part 2 = the rest (dense_grads is complete after part 2; both parts take the
  * same arguments).  rc_sasrec_batch_bwd_splits: 1 where part 2 is not empty (one block on the last-row path), else part 1 is the
@@ -573,7 +548,7 @@ int rc_sasrec_pos_grad(const float* g_hist, const int64_t* lengths, int B, int L
  * and no valid row attends to one).                                                                                              */
 
 /* off[b] = sum_{b' < b} min(lengths[b'], L), b in [0, B]: a valid row's compact index off[b] + i keys the dropout mask like
- * rc_sasrec_batch_fwd_dropout does, and off[b + 1] - off[b] is the sequence's valid row count.                                   */
+ * rc_sasrec_batch_fwd does, and off[b + 1] - off[b] is the sequence's valid row count.                                   */
 int rc_seq_offsets(const int64_t* lengths, int64_t B, int L, int32_t* off, rc_stream_t stream);
 /* SASRec.py:58-66: X[b, i, :] = item_emb[hist[b, i]] + pos_emb[len_b - i] for i < len_b, 0 on the padding.                       */
 int rc_seq_embed_fwd(const float* item_emb, const float* pos_emb, const int64_t* hist, const int64_t* lengths, int64_t B, int L, int d,
@@ -600,7 +575,7 @@ int rc_seq_attention_bwd(const float* Q, const float* K, const float* V, const i
  * rstd [rows] are kept for the backward pass.  off NULL: every row is valid and its compact index is the row number; otherwise rows
  * = B * L and invalid rows give Y = xhat = 0.  drop_p > 0: element (compact row r, feature f) of `site` is dropped iff word (f & 3)
  * of Philox4x32-10(key = *seed_dev, counter = (r, site * d / 4 + (f >> 2))) < drop_p * 2^32, kept values scaled by 1 / (1 - p) --
- * the stream of rc_sasrec_batch_fwd_dropout (site = 2 * layer + {0: dropout1, 1: dropout2}).  Backward: dA = mask * dZ (NULL:
+ * the stream of rc_sasrec_batch_fwd (site = 2 * layer + {0: dropout1, 1: dropout2}).  Backward: dA = mask * dZ (NULL:
  * not wanted), dR = dZ, dw = sum_rows dY * xhat, db = sum_rows dY in a fixed order.  d a multiple of 4 up to 1,024.                */
 int rc_seq_add_layernorm_fwd(const float* A, const float* R, const float* w, const float* b, const int32_t* off, int64_t rows, int L,
                              int d, float drop_p, const uint64_t* seed_dev, uint32_t site, float* Y, float* xhat, float* rstd,
@@ -619,11 +594,19 @@ int rc_neumf_supported(int d, int l1);
 /* pred[b,c] = w_out[:d].(mf_u[u_b]*mf_i[i_bc]) + w_out[d:].relu(W1 [mlp_u[u_b];mlp_i[i_bc]] + b1)
  * (NeuMF.py:61-75; W1 = mlp.0.weight [l1, 2d], b1 = mlp.0.bias, w_out = prediction.weight[0]).
  * Without dropout a wave owns 16 candidates: the mlp rows go from global memory straight into the MFMA operand registers,
- * W1 waits in LDS (52 % of the fp32 MFMA peak, gathers at 5 TB/s at d = 128, hidden 64).                                  */
+ * W1 waits in LDS (52 % of the fp32 MFMA peak, gathers at 5 TB/s at d = 128, hidden 64).
+ * TRAINING mode with dropout drop_p > 0 on the hidden layer (NeuMF.py:58 nn.Dropout after the
+ * ReLU, the reference's demo runs --dropout 0.2): hidden feature f of candidate n = b*C+c is zeroed iff
+ * word (f & 3) of Philox4x32-10(key = *seed_dev, counter = (n, f >> 2)) < p * 2^32, kept values are scaled
+ * by 1/(1-p).  The mask is never stored: the backward regenerates it from the same *seed_dev, which
+ * therefore must not change between the two calls; bump it (rc_step_increment) once per step, also inside a
+ * captured graph.  The stream differs from torch's Philox dropout: parity with the reference is
+ * distributional, parity with oracle/neumf_oracle.py (same counter scheme) is exact in the mask.
+ * drop_p = 0 (seed_dev may then be NULL): no dropout.                                                      */
 int rc_neumf_fwd(const float* mf_u, const float* mf_i, const float* mlp_u, const float* mlp_i,
                  const float* W1, const float* b1, const float* w_out, const int64_t* uid,
-                 const int64_t* iid, int B, int C, int d, int l1, float* pred,
-                 rc_stream_t stream);
+                 const int64_t* iid, int B, int C, int d, int l1, float drop_p,
+                 const uint64_t* seed_dev, float* pred, rc_stream_t stream);
 
 size_t rc_neumf_workspace_bytes(int B, int C, int d, int l1);
 
@@ -634,27 +617,9 @@ size_t rc_neumf_workspace_bytes(int B, int C, int d, int l1);
 int rc_neumf_bwd(const float* mf_u, const float* mf_i, const float* mlp_u, const float* mlp_i,
                  const float* W1, const float* b1, const float* w_out, const int64_t* uid,
                  const int64_t* iid, const float* gpred, int B, int C, int d, int l1,
-                 float* g_mf_u, float* g_mf_i, float* g_mlp_u, float* g_mlp_i, float* dW1,
-                 float* db1, float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream);
-
-/* The same head in TRAINING mode with dropout p on the hidden layer (NeuMF.py:58 nn.Dropout after the
- * ReLU, the reference's demo runs --dropout 0.2): hidden feature f of candidate n = b*C+c is zeroed iff
- * word (f & 3) of Philox4x32-10(key = *seed_dev, counter = (n, f >> 2)) < p * 2^32, kept values are scaled
- * by 1/(1-p).  The mask is never stored: the backward regenerates it from the same *seed_dev, which
- * therefore must not change between the two calls; bump it (rc_step_increment) once per step, also inside a
- * captured graph.  The stream differs from torch's Philox dropout: parity with the reference is
- * distributional, parity with oracle/neumf_oracle.py (same counter scheme) is exact in the mask.
- * p = 0 (seed_dev may then be NULL) is rc_neumf_fwd / rc_neumf_bwd bit for bit.                          */
-int rc_neumf_fwd_dropout(const float* mf_u, const float* mf_i, const float* mlp_u, const float* mlp_i,
-                         const float* W1, const float* b1, const float* w_out, const int64_t* uid,
-                         const int64_t* iid, int B, int C, int d, int l1, float drop_p,
-                         const uint64_t* seed_dev, float* pred, rc_stream_t stream);
-int rc_neumf_bwd_dropout(const float* mf_u, const float* mf_i, const float* mlp_u, const float* mlp_i,
-                         const float* W1, const float* b1, const float* w_out, const int64_t* uid,
-                         const int64_t* iid, const float* gpred, int B, int C, int d, int l1,
-                         float drop_p, const uint64_t* seed_dev, float* g_mf_u, float* g_mf_i,
-                         float* g_mlp_u, float* g_mlp_i, float* dW1, float* db1, float* dw_out,
-                         void* ws, size_t ws_bytes, rc_stream_t stream);
+                 float drop_p, const uint64_t* seed_dev, float* g_mf_u, float* g_mf_i,
+                 float* g_mlp_u, float* g_mlp_i, float* dW1, float* db1, float* dw_out,
+                 void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* ONE BaseRunner.fit iteration of the NeuMF head (helpers/BaseRunner.py:193-206 on models/general/NeuMF.py:56-76 with
  * GeneralModel.loss, models/BaseModel.py:182-185) in one kernel (csrc/neumf_step.hip): forward, BPR loss, backward and the
@@ -673,45 +638,33 @@ int rc_neumf_bwd_dropout(const float* mf_u, const float* mf_i, const float* mlp_
  *   gu_mf, gu_mlp [B, d]      ONE gradient row per tuple for the user tables (plan the user ids per tuple)
  *   dW1, db1, dw_out          dense gradients, per-workgroup partials summed in fixed order; no float atomics anywhere
  * Shapes: rc_neumf_train_step_supported(C, d, l1): d in {32,64,128}, l1 in {16,32,64} (l1 = 16: d >= 64), C >= 2 and the LDS image <= 160 KB
- * (C <= 136 at d = 128, l1 = 64).  Training-mode dropout (the reference's own NeuMF command line runs --dropout 0.2,
- * docs/demo_scripts_results/Topk_Amazon.sh:8; NeuMF.py:58,70): rc_neumf_train_step_dropout below.                          */
+ * (C <= 136 at d = 128, l1 = 64).
+ * Training-mode dropout (the reference's own NeuMF command line runs --dropout 0.2, docs/demo_scripts_results/Topk_Amazon.sh:8):
+ * nn.Dropout(p) on the hidden layer (models/general/NeuMF.py:58, 70) inside the kernel: the mask of
+ * rc_neumf_fwd / rc_neumf_bwd -- feature f of candidate n = b C + c is dropped iff word (f & 3) of
+ * Philox4x32-10(key = *seed_dev, counter = (n, f >> 2)) < p 2^32, kept values scaled by 1 / (1 - p) -- generated in the forward
+ * pass of a candidate and regenerated, not stored, in its backward pass.  *seed_dev is read by the kernel (bump it with
+ * rc_step_increment for a fresh mask per step; capturable).  drop_p = 0 (seed_dev may be NULL): no dropout.
+ * marks_prepared != 0: the marks buffer was filled by rc_neumf_mark_rows for this very batch (below); 0: the call marks and
+ * clears it itself.                                                                                                          */
 int rc_neumf_train_step_supported(int C, int d, int l1);
 size_t rc_neumf_train_step_workspace_bytes(int B, int C, int d, int l1);
 size_t rc_neumf_train_step_marks_bytes(int64_t n_items);
 int rc_neumf_train_step(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
                         float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
                         const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                        void* marks, const rc_opt_hyper* h, float inv_b, float* loss_vec, float* pred,
-                        float* g_mf_i, float* g_mlp_i, float* gu_mf, float* gu_mlp, float* dW1, float* db1,
-                        float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream);
+                        void* marks, int marks_prepared, const rc_opt_hyper* h, float inv_b, float drop_p,
+                        const uint64_t* seed_dev, float* loss_vec, float* pred, float* g_mf_i, float* g_mlp_i,
+                        float* gu_mf, float* gu_mlp, float* dW1, float* db1, float* dw_out, void* ws,
+                        size_t ws_bytes, rc_stream_t stream);
 
 /* The marking passes of rc_neumf_train_step on their own, for callers that know the FOLLOWING batch (BaseRunner.fit does: the
  * reference's DataLoader runs ahead of the loop, helpers/BaseRunner.py:182-186): rc_neumf_mark_rows fills a marks buffer for iid
- * [n = B C] on any stream -- e.g. beside the current step's table updates --, rc_neumf_train_step_marked is rc_neumf_train_step
- * without its two marking launches and without the clearing pass (same arguments, same results bit for bit), and
+ * [n = B C] on any stream -- e.g. beside the current step's table updates --, rc_neumf_train_step with marks_prepared != 0 runs
+ * without its two marking launches and without the clearing pass (same results bit for bit), and
  * rc_neumf_unmark_rows clears the flags again before the buffer is marked for another batch.  Two buffers alternate.          */
 int rc_neumf_mark_rows(const int64_t* iid, int64_t n, int64_t n_items, void* marks, rc_stream_t stream);
 int rc_neumf_unmark_rows(const int64_t* iid, int64_t n, int64_t n_items, void* marks, rc_stream_t stream);
-int rc_neumf_train_step_marked(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
-                               float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
-                               const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                               void* marks, const rc_opt_hyper* h, float inv_b, float* loss_vec, float* pred,
-                               float* g_mf_i, float* g_mlp_i, float* gu_mf, float* gu_mlp, float* dW1, float* db1,
-                               float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream);
-
-/* rc_neumf_train_step with nn.Dropout(p) on the hidden layer (models/general/NeuMF.py:58, 70) inside the kernel: the mask of
- * rc_neumf_fwd_dropout / rc_neumf_bwd_dropout -- feature f of candidate n = b C + c is dropped iff word (f & 3) of
- * Philox4x32-10(key = *seed_dev, counter = (n, f >> 2)) < p 2^32, kept values scaled by 1 / (1 - p) -- generated in the forward
- * pass of a candidate and regenerated, not stored, in its backward pass.  *seed_dev is read by the kernel (bump it with
- * rc_step_increment for a fresh mask per step; capturable).  drop_p = 0: exactly rc_neumf_train_step.  marks_prepared != 0: the
- * marks buffer was filled by rc_neumf_mark_rows for this very batch (as rc_neumf_train_step_marked).                          */
-int rc_neumf_train_step_dropout(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
-                                float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
-                                const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                                void* marks, int marks_prepared, const rc_opt_hyper* h, float inv_b, float drop_p,
-                                const uint64_t* seed_dev, float* loss_vec, float* pred, float* g_mf_i, float* g_mlp_i,
-                                float* gu_mf, float* gu_mlp, float* dW1, float* db1, float* dw_out, void* ws,
-                                size_t ws_bytes, rc_stream_t stream);
 
 /* The same kernel without table updates, on row blocks with a stride: forward, BPR loss and backward of the NeuMF head for
  * callers that own neither the tables nor the optimizer -- the row-sharded step (rechorus_amd/sharded.py, ShardedNeumf), where
@@ -750,24 +703,21 @@ int rc_neumf_zhead_fwd_bwd(const float* mf_u, int64_t ld_u, const float* zu, con
  *   rc_linear_bwd: given the layer's saved OUTPUT Y (its own mask: dZ = dY * (Y > 0 ? 1/(1-p) : 0); NULL for a plain
  *     Linear) -> dX [M, K] (NULL: skip), dW [N, K], db [N] (NULL: skip).  The batch reduction of dW / db is cut into
  *     row ranges whose partial sums are combined in a fixed order (no float atomics).                            */
-int rc_linear_fwd(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
-                  const uint64_t* seed_dev, uint32_t site, float* Y, rc_stream_t stream);
-/* rc_linear_fwd with a workspace: a small batch (fewer than 256 output tiles of 64 x 64) is cut along the reduction -- split-K,
- * the partial products summed in split order by a second launch that applies bias / ReLU / dropout -- so that a
- * 1,024 x 512 x 512 product is 512 workgroups of four K steps instead of 128 of sixteen.  ws NULL: no split.             */
+/* rc_linear_fwd's workspace (ws may be NULL: no split): a small batch (fewer than 256 output tiles of 64 x 64) is cut along the
+ * reduction -- split-K, the partial products summed in split order by a second launch that applies bias / ReLU / dropout -- so that a
+ * 1,024 x 512 x 512 product is 512 workgroups of four K steps instead of 128 of sixteen.                                    */
 size_t rc_linear_fwd_workspace_bytes(int64_t M, int N, int K);
-int rc_linear_fwd_ws(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
-                     const uint64_t* seed_dev, uint32_t site, float* Y, void* ws, size_t ws_bytes, rc_stream_t stream);
-size_t rc_linear_bwd_workspace_bytes(int64_t M, int N, int K);
-int rc_linear_bwd(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K,
-                  float drop_p, float* dX, float* dW, float* db, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_linear_fwd(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
+                  const uint64_t* seed_dev, uint32_t site, float* Y, void* ws, size_t ws_bytes, rc_stream_t stream);
 /* rc_linear_bwd inside a chain of layers (utils/layers.py:201-243 builds Linear -> ReLU -> Dropout groups): with x_act != 0 the
  * input X is the drop(relu(.)) output of the layer below and dX comes out already multiplied by that layer's mask
  * (X > 0 ? 1 / (1 - x_drop_p) : 0) in the product's epilogue; the layer below is then called with Y = NULL (its dY is its dZ).
- * Either of dX / dW (+ db) may be NULL here: the two products of a layer are independent given dZ, and a caller may issue them in
+ * A single layer: x_act = 0, x_drop_p = 0.
+ * Either of dX / dW (+ db) may be NULL: the two products of a layer are independent given dZ, and a caller may issue them in
  * two calls on two streams (the dX chain is the critical path of a small batch; workspaces must then differ). */
-int rc_linear_bwd_chain(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K, float drop_p,
-                        int x_act, float x_drop_p, float* dX, float* dW, float* db, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_linear_bwd_workspace_bytes(int64_t M, int N, int K);
+int rc_linear_bwd(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K, float drop_p,
+                  int x_act, float x_drop_p, float* dX, float* dW, float* db, void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* The TAIL of an MLP tower at a small batch (csrc/tower_tail.hip): the last hidden layer Linear(K -> N2) -> ReLU -> Dropout(p) and
  * the output layer Linear(N2 -> 1) of utils/layers.py:201-243 (MLP_Block: models/context/DeepFM.py:25, WideDeep.py:42-47 at
@@ -775,7 +725,7 @@ int rc_linear_bwd_chain(const float* X, const float* W, const float* Y, const fl
  * fixed-order sum of the per-workgroup partials) instead of eleven GEMM / epilogue launches of 5-15 us each.
  *   rc_tower_tail_fwd: H2 [M, N2] = drop(relu(X [M, K] W2^T + b2)) (the mask of rc_linear_fwd, layer index `site`), z [M] = H2 w3 + b3
  *   rc_tower_tail_bwd: given dz [M] = d loss / d z: dX [M, K] = ((dz w3^T * mask(H2)) W2), multiplied by the mask of the layer below
- *     when x_act != 0 (X > 0 ? 1 / (1 - x_drop_p) : 0, as rc_linear_bwd_chain); dW2 [N2, K], db2 [N2], dw3 [N2], db3 [1].
+ *     when x_act != 0 (X > 0 ? 1 / (1 - x_drop_p) : 0, as rc_linear_bwd); dW2 [N2, K], db2 [N2], dw3 [N2], db3 [1].
  *     dX, db2, db3 may be NULL.  ws: rc_tower_tail_workspace_bytes(M, K, N2).  No float atomics.
  * Shapes: rc_tower_tail_supported: N2 in {16, 32, 64}, K in {64, 128, 256, 512}; X, W2, H2, w3 16-byte aligned.                 */
 int rc_tower_tail_supported(int64_t M, int K, int N2);
@@ -908,7 +858,7 @@ int rc_bucket_plan(const int64_t* ids_a, int64_t n_a, int64_t range_a, const int
 
 /* The singleton information alone, as a bitmap over the ids of ONE list: bit (id & 31) of bitmap[id >> 5] = 1 iff
  * row id occurs at least twice in ids_a[0 .. n_a) (words of id ranges the batch does not touch are left unwritten).
- * This is what the fused BPRMF kernel consumes in the bucket-plan step (rc_bprmf_fwd_bwd_update_bitmap): 1.25 MB for
+ * This is what the fused BPRMF kernel consumes in the bucket-plan step (rc_bprmf_fwd_bwd_update with `multi`): 1.25 MB for
  * a 10 M-row table, L2-resident, written as one coalesced 1 KB run per 8,192-id bucket -- instead of one flag byte per
  * batch position.  bitmap: rc_bucket_bitmap_bytes(range_a) bytes; ws: rc_bucket_plan_workspace_bytes(n_a, 0).      */
 size_t rc_bucket_bitmap_bytes(int64_t range_a);
@@ -918,7 +868,7 @@ int rc_bucket_multi_bitmap(const int64_t* ids_a, int64_t n_a, int64_t range_a, u
 /* Optimizer row update of the rows listed by a plan (csrc/plan_update.hip): per row, the gradient rows of its
  * occurrences are summed in ascending batch position (fixed order, no float atomics), the table row is read once,
  * updated by `h` (row-wise: only listed rows move) and written once; rows with more than 32 occurrences go
- * through 256-occurrence chunks.  Same semantics and arguments as rc_segmented_update2 (which it replaces where a
+ * through 256-occurrence chunks.  Same semantics and arguments as rc_segmented_update (which it replaces where a
  * plan exists): the gradient row of the occurrence at position o = occ[slot] is
  *   o <  n_split:  coef[o] * src[src_index ? src_index[o / div] : o / div]     (coef NULL = 1)
  *   o >= n_split:  src2[o - n_split]
@@ -930,26 +880,20 @@ int rc_plan_update(float* W, float* m, float* v, int d, const rc_plan_row* rows,
                    rc_stream_t stream);
 
 /* Two tables that share their ids (NeuMF's mf / mlp embedding of a side, models/general/NeuMF.py:37-40) updated in
- * ONE pass over the plan: per-occurrence gradient rows src_a / src_b [*, d], the occurrence at position o reads row
- * o - occ_base of both.  Workspace: rc_plan_update_workspace_bytes(n_occ, 2 d).  d in {8, 16, 32, 64, 128}.      */
+ * ONE pass over the plan.  Workspace: rc_plan_update_workspace_bytes(n_occ, 2 d).  d in {8, 16, 32, 64, 128}.
+ * Gradient sources, one of two forms:
+ *   src_b != NULL (src_ld must be 0): per-occurrence gradient rows src_a / src_b [*, d], the occurrence at position o reads row
+ *     o - occ_base of both;
+ *   src_b == NULL: both sources in ONE block: occurrence o reads src_a[o - occ_base, 0 .. d) for table a and
+ *     [d .. 2 d) for table b, rows src_ld floats apart (a multiple of 4, >= 2 d) -- the (d mf | d mlp) rows of
+ *     models/general/NeuMF.py:39-42's two table families as a row-sharded rank receives them, used where they lie.
+ * counters: NULL (the call zeroes its own), or the update's eight ticket counters supplied by the caller (8 uint32 on the device),
+ * ZERO-FILLED where that cost nothing -- with the plan's buffers, beside other work on another stream -- and used by nobody since:
+ * the memset in front of the update, a launch of its own between a step's fused kernel and its table updates, is left out.      */
 int rc_plan_update_pair(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
                         const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                        const float* src_a, const float* src_b, int64_t occ_base, const rc_opt_hyper* h, void* ws,
-                        size_t ws_bytes, rc_stream_t stream);
-/* rc_plan_update_pair with the update's eight ticket counters supplied by the caller (8 uint32 on the device), ZERO-FILLED where
- * that cost nothing -- with the plan's buffers, beside other work on another stream -- and used by nobody since: the memset in
- * front of the update, a launch of its own between a step's fused kernel and its table updates, is left out.                     */
-int rc_plan_update_pair_zeroed(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
-                               const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                               const float* src_a, const float* src_b, int64_t occ_base, const rc_opt_hyper* h,
-                               uint32_t* counters, void* ws, size_t ws_bytes, rc_stream_t stream);
-/* rc_plan_update_pair with both gradient sources in ONE block: occurrence o reads src_block[o - occ_base, 0 .. d) for table a and
- * [d .. 2 d) for table b, rows src_ld floats apart (a multiple of 4, >= 2 d) -- the (d mf | d mlp) rows of models/general/NeuMF.py:39-42's
- * two table families as a row-sharded rank receives them, used where they lie.  counters: as rc_plan_update_pair_zeroed, or NULL.  */
-int rc_plan_update_pair_block(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
-                              const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                              const float* src_block, int64_t src_ld, int64_t occ_base, const rc_opt_hyper* h,
-                              uint32_t* counters, void* ws, size_t ws_bytes, rc_stream_t stream);
+                        const float* src_a, const float* src_b, int64_t src_ld, int64_t occ_base, const rc_opt_hyper* h,
+                        uint32_t* counters, void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* The same walk without an optimizer: out[row, :] = the summed gradient row of every LISTED row (other rows of `out` are
  * left as they are) -- aten::embedding_dense_backward's index_add (helpers/BaseRunner.py:205) as a plan consumer, and the

@@ -49,7 +49,7 @@ def linear_bwd(X, W, cache, dY):
 
 
 def linear_bwd_chain(X, W, dZ, x_mask=None, x_scale=1.0):
-    """rc_linear_bwd_chain in float64: the layer receives dZ (its dY already masked by the layer above's dX product) and hands
+    """rc_linear_bwd in float64: the layer receives dZ (its dY already masked by the layer above's dX product) and hands
     down dX multiplied by the mask of the layer BELOW -- x_mask = (X > 0) of the saved activation X = drop(relu(.)), x_scale =
     1 / (1 - p) of that layer's dropout -- i.e. the dZ of the layer below (utils/layers.py:201-243 chains Linear -> ReLU -> Dropout).
     -> (dX masked [M, K], dW [N, K], db [N])"""

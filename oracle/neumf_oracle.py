@@ -12,7 +12,7 @@ F32 = np.float32
 
 
 def dropout_keep(seed, n_cand, width, p):
-    """keep-and-scale factors [n_cand, width] of rc_neumf_fwd_dropout (include/rechorus_hip.h): feature f of
+    """keep-and-scale factors [n_cand, width] of rc_neumf_fwd (include/rechorus_hip.h): feature f of
     candidate n is dropped iff word (f & 3) of Philox4x32-10(key = seed, counter = (n, f >> 2)) < p * 2^32.
     (nn.Dropout semantics, NeuMF.py:58/70: zero with probability p, scale the rest by 1/(1-p); torch's own
     random stream is not reproduced.)"""

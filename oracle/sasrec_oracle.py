@@ -5,7 +5,7 @@ utils/layers.py TransformerLayer :92-118 and MultiHeadAttention :9-63) and of th
 autograd derives from it, fp32 storage with float64 accumulation inside matmuls (the checker
 should be at least as accurate as the thing checked).  Training-mode dropout (utils/layers.py:104-117)
 enters as explicit keep-and-scale masks (`drop`, from dropout_keep: the counter scheme of
-rc_sasrec_batch_fwd_dropout); None = eval mode / p = 0.
+rc_sasrec_batch_fwd); None = eval mode / p = 0.
 Pinned against the reference itself: tests/golden/sasrec_*.npz, sasrecdrop_*.npz (make_golden_sasrec.py).
 
 Parameter names are the reference's state_dict keys:
@@ -22,7 +22,7 @@ LN_EPS = 1e-5  # nn.LayerNorm default
 
 
 def dropout_keep(seed, lengths, L, d, n_layers_, p):
-    """keep-and-scale factors of rc_sasrec_batch_fwd_dropout (include/rechorus_hip.h) as a list of 2 * n_layers arrays
+    """keep-and-scale factors of rc_sasrec_batch_fwd (include/rechorus_hip.h) as a list of 2 * n_layers arrays
     [B, L, d] (site 2l = dropout1 of layer l, 2l + 1 = dropout2): element (b, i, f) with i < min(len_b, L) lives in
     compact row r = sum_{b' < b} min(len_b', L) + i and is dropped iff word (f & 3) of
     Philox4x32-10(key = seed, counter = (r, site * d/4 + (f >> 2))) < p * 2^32.  Padded positions get 1 (their

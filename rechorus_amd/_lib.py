@@ -135,21 +135,19 @@ SIGNATURES = {
     "rc_reduce_sum": (_i, [_p, _i64, _f, _p, _p]),
     "rc_bprmf_fwd_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
     "rc_bprmf_fused_supported": (_i, [_i, _i]),
-    "rc_bprmf_fwd_bwd_update": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _hp, _p, _p, _p, _p, _p]),
+    "rc_bprmf_fwd_bwd_update": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _hp, _p, _p, _p, _p, _p]),
     "rc_segment_heads": (_i, [_p, _p, _i64, _i, _p, _p, _p, _p]),
     "rc_sort_workspace_bytes": (_sz, [_i64]),
     "rc_sort_ids": (_i, [_p, _i64, _i64, _p, _p, _p, _sz, _p]),
     "rc_segmented_workspace_bytes": (_sz, [_i64, _i]),
-    "rc_segmented_update": (_i, [_p, _p, _p, _i, _p, _p, _i64, _p, _p, _p, _i, _hp, _p, _p, _p, _i, _p, _sz, _p]),
+    "rc_segmented_update": (_i, [_p, _p, _p, _i, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _i64, _i64, _hp, _p, _p,
+                                 _p, _i, _p, _sz, _p]),
     "rc_dense_update": (_i, [_p, _p, _p, _p, _i64, _hp, _p]),
-    "rc_dense_update_multi": (_i, [_p, _p, _p, _p, _p, _p, _i, _p]),
-    "rc_dense_update_multi_dev": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "rc_dense_update_multi": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p]),
     "rc_step_increment": (_i, [_p, _p]),
     "rc_step_increment2": (_i, [_p, _p, _p]),
     "rc_dense_update_rows_dev": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "rc_stage_batch": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p]),
-    "rc_segmented_update2": (_i, [_p, _p, _p, _i, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _i64, _i64, _hp, _p, _p,
-                                  _p, _i, _p, _sz, _p]),
     "rc_ctr_head_fwd_bwd": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "rc_ctr_head_fwd_bwd_sums": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "rc_ctr_head_fwd_full": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
@@ -162,8 +160,7 @@ SIGNATURES = {
     "rc_small_row_sums_pair_numeric": (_i, [_p, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i, _p, _p, _p, _sz, _p]),
     "rc_small_row_sums_planned": (_i, [_i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "rc_segmented_rows_workspace_bytes": (_sz, [_i64, _i64, _i]),
-    "rc_segmented_update_rows": (_i, [_p, _p, _p, _i, _i64, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _hp, _p, _p, _sz, _p]),
-    "rc_segmented_update_rows_dev": (_i, [_p, _p, _p, _i, _i64, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _hp, _p, _p, _p, _sz, _p]),
+    "rc_segmented_update_rows": (_i, [_p, _p, _p, _i, _i64, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _hp, _p, _p, _p, _sz, _p]),
     "rc_rows_plan_supported": (_i, [_i64, _i64, _i]),
     "rc_rows_plan_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "rc_rows_plan_build": (_i, [_p, _i64, _p, _i64, _p, _i, _i64, _i, _p, _sz, _p]),
@@ -180,40 +177,32 @@ SIGNATURES = {
     "rc_sasrec_pos_grad": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "rc_sasrec_batch_state_floats": (_sz, [_i, _i, _i, _i]),
     "rc_sasrec_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "rc_sasrec_batch_fwd": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _sz, _p]),
-    "rc_sasrec_batch_bwd": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
-    "rc_sasrec_batch_fwd_dropout": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
-    "rc_sasrec_batch_bwd_dropout": (_i, [_p, _i, _i, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "rc_sasrec_batch_fwd": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "rc_sasrec_batch_bwd": (_i, [_p, _i, _i, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "rc_sasrec_batch_bwd_part": (_i, [_p, _i, _i, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz, _i, _p]),
     "rc_sasrec_batch_bwd_splits": (_i, [_i, _i, _i, _i, _i, _f]),
     "rc_neumf_supported": (_i, [_i, _i]),
-    "rc_neumf_fwd": (_i, [_p] * 9 + [_i, _i, _i, _i, _p, _p]),
+    "rc_neumf_fwd": (_i, [_p] * 9 + [_i, _i, _i, _i, _f, _p, _p, _p]),
     "rc_neumf_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "rc_neumf_bwd": (_i, [_p] * 10 + [_i, _i, _i, _i] + [_p] * 7 + [_p, _sz, _p]),
+    "rc_neumf_bwd": (_i, [_p] * 10 + [_i, _i, _i, _i, _f, _p] + [_p] * 7 + [_p, _sz, _p]),
     "rc_neumf_train_step_supported": (_i, [_i, _i, _i]),
     "rc_neumf_train_step_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rc_neumf_train_step_marks_bytes": (_sz, [_i64]),
-    "rc_neumf_train_step": (_i, [_p] * 13 + [_i, _i, _i, _i, _i64, _p, _hp, _f] + [_p] * 9 + [_p, _sz, _p]),
+    "rc_neumf_train_step": (_i, [_p] * 13 + [_i, _i, _i, _i, _i64, _p, _i, _hp, _f, _f, _p] + [_p] * 9 + [_p, _sz, _p]),
     "rc_neumf_mark_rows": (_i, [_p, _i64, _i64, _p, _p]),
     "rc_neumf_unmark_rows": (_i, [_p, _i64, _i64, _p, _p]),
-    "rc_neumf_train_step_dropout": (_i, [_p] * 13 + [_i, _i, _i, _i, _i64, _p, _i, _hp, _f, _f, _p] + [_p] * 9 + [_p, _sz, _p]),
-    "rc_neumf_train_step_marked": (_i, [_p] * 13 + [_i, _i, _i, _i, _i64, _p, _hp, _f] + [_p] * 9 + [_p, _sz, _p]),
     "rc_neumf_head_fwd_bwd": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _i64, _p, _p, _i64,
                                    _p, _p, _p, _p, _sz, _p]),
     "rc_bench_mix": (_i, [_p, _i, _p, _i64, _f, _i, _p, C.POINTER(C.c_float), _p]),
     "rc_bench_mfma": (_i, [_i, _p, C.POINTER(C.c_float), _p]),
-    "rc_linear_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _p, C.c_uint32, _p, _p]),
+    "rc_linear_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _p, C.c_uint32, _p, _p, _sz, _p]),
     "rc_linear_fwd_workspace_bytes": (_sz, [_i64, _i, _i]),
-    "rc_linear_fwd_ws": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _p, C.c_uint32, _p, _p, _sz, _p]),
     "rc_linear_bwd_workspace_bytes": (_sz, [_i64, _i, _i]),
-    "rc_linear_bwd": (_i, [_p, _p, _p, _p, _i64, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
-    "rc_linear_bwd_chain": (_i, [_p, _p, _p, _p, _i64, _i, _i, _f, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "rc_linear_bwd": (_i, [_p, _p, _p, _p, _i64, _i, _i, _f, _i, _f, _p, _p, _p, _p, _sz, _p]),
     "rc_tower_tail_supported": (_i, [_i64, _i, _i]),
     "rc_tower_tail_workspace_bytes": (_sz, [_i64, _i, _i]),
     "rc_tower_tail_fwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _f, _p, C.c_uint32, _p, _p, _p]),
     "rc_tower_tail_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _f, _i, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "rc_neumf_fwd_dropout": (_i, [_p] * 9 + [_i, _i, _i, _i, _f, _p, _p, _p]),
-    "rc_neumf_bwd_dropout": (_i, [_p] * 10 + [_i, _i, _i, _i, _f, _p] + [_p] * 7 + [_p, _sz, _p]),
     "rc_bucket_plan_supported": (_i, [_i64, _i64, _i64, _i64]),
     "rc_bucket_plan_workspace_bytes": (_sz, [_i64, _i64]),
     "rc_bucket_plan_flags_bytes": (_sz, [_i64]),
@@ -221,9 +210,7 @@ SIGNATURES = {
     "rc_bucket_plan": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "rc_plan_update_workspace_bytes": (_sz, [_i64, _i]),
     "rc_plan_update": (_i, [_p, _p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _hp, _p, _sz, _p]),
-    "rc_plan_update_pair": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _p, _p, _i64, _hp, _p, _sz, _p]),
-    "rc_plan_update_pair_zeroed": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _p, _p, _i64, _hp, _p, _p, _sz, _p]),
-    "rc_plan_update_pair_block": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _p, _i64, _i64, _hp, _p, _p, _sz, _p]),
+    "rc_plan_update_pair": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _p, _p, _i64, _i64, _hp, _p, _p, _sz, _p]),
     "rc_plan_row_sums": (_i, [_p, _i, _p, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _p, _sz, _p]),
     "rc_plan_distinct": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _p]),
     "rc_bprmf_step_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -235,7 +222,6 @@ SIGNATURES = {
                                        _p, _p, _p, _sz, _p, C.POINTER(C.c_float)]),
     "rc_bucket_bitmap_bytes": (_sz, [_i64]),
     "rc_bucket_multi_bitmap": (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
-    "rc_bprmf_fwd_bwd_update_bitmap": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _hp, _p, _p, _p, _p, _p]),
     "rc_lgcn_check_shape": (_i, [_i, _i, _i64, _i64]),
     "rc_lgcn_propagate_fwd": (_i, [_gp, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "rc_lgcn_propagate_bwd": (_i, [_gp, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),

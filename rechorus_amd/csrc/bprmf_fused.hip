@@ -276,12 +276,14 @@ extern "C" int rc_bprmf_fwd_bwd(const float* U, const float* I, const int64_t* u
   return RC_OK;
 }
 
-static int fwd_bwd_update_impl(const char* who, const float* U, float* I, float* mI, float* vI, const int64_t* uid,
-                               const int64_t* iid, const uint8_t* single, const uint32_t* multi, int B, int C, int d,
-                               float inv_b, const rc_opt_hyper* h, float* pred, float* loss_vec, float* gpred, float* ugrad,
-                               rc_stream_t stream) {
+extern "C" int rc_bprmf_fwd_bwd_update(const float* U, float* I, float* mI, float* vI, const int64_t* uid,
+                                       const int64_t* iid, const uint8_t* single, const uint32_t* multi, int B, int C, int d,
+                                       float inv_b, const rc_opt_hyper* h, float* pred, float* loss_vec, float* gpred, float* ugrad,
+                                       rc_stream_t stream) {
+  static const char* who = "rc_bprmf_fwd_bwd_update";
   if (B == 0) return RC_OK;
-  RC_REQUIRE(U && I && uid && iid && (single || multi) && h && loss_vec && gpred && ugrad, "%s: null pointer", who);
+  RC_REQUIRE((single != nullptr) != (multi != nullptr), "%s: exactly one of single / multi must be given", who);
+  RC_REQUIRE(U && I && uid && iid && h && loss_vec && gpred && ugrad, "%s: null pointer", who);
   RC_REQUIRE(B > 0 && C >= 2 && d >= 1, "%s: bad shape B=%d C=%d d=%d", who, B, C, d);
   if (!register_path_ok(d, C))
     return fail(RC_ERR_UNSUPPORTED,
@@ -303,26 +305,6 @@ static int fwd_bwd_update_impl(const char* who, const float* U, float* I, float*
   const int rc_ = run_fused(f, d, &handled);
   if (!handled) return fail(RC_ERR_UNSUPPORTED, "%s: dispatch failed", who);
   return rc_;
-}
-
-extern "C" int rc_bprmf_fwd_bwd_update(const float* U, float* I, float* mI, float* vI,
-                                       const int64_t* uid, const int64_t* iid,
-                                       const uint8_t* single, int B, int C, int d, float inv_b,
-                                       const rc_opt_hyper* h, float* pred, float* loss_vec,
-                                       float* gpred, float* ugrad, rc_stream_t stream) {
-  if (B != 0) RC_REQUIRE(single, "rc_bprmf_fwd_bwd_update: null pointer");
-  return fwd_bwd_update_impl("rc_bprmf_fwd_bwd_update", U, I, mI, vI, uid, iid, single, nullptr, B, C, d, inv_b, h, pred,
-                             loss_vec, gpred, ugrad, stream);
-}
-
-extern "C" int rc_bprmf_fwd_bwd_update_bitmap(const float* U, float* I, float* mI, float* vI,
-                                              const int64_t* uid, const int64_t* iid,
-                                              const uint32_t* multi, int B, int C, int d, float inv_b,
-                                              const rc_opt_hyper* h, float* pred, float* loss_vec,
-                                              float* gpred, float* ugrad, rc_stream_t stream) {
-  if (B != 0) RC_REQUIRE(multi, "rc_bprmf_fwd_bwd_update_bitmap: null pointer");
-  return fwd_bwd_update_impl("rc_bprmf_fwd_bwd_update_bitmap", U, I, mI, vI, uid, iid, nullptr, multi, B, C, d, inv_b, h, pred,
-                             loss_vec, gpred, ugrad, stream);
 }
 
 namespace rc {

@@ -287,13 +287,8 @@ extern "C" int rc_step_increment2(int64_t* a_dev, int64_t* b_dev, rc_stream_t st
 }
 
 extern "C" int rc_dense_update_multi(float* const* W, const float* const* G, float* const* m, float* const* v,
-                                     const int64_t* n, const rc_opt_hyper* h, int n_tensors, rc_stream_t stream) {
-  return rc_dense_update_multi_dev(W, G, m, v, n, h, n_tensors, nullptr, stream);
-}
-
-extern "C" int rc_dense_update_multi_dev(float* const* W, const float* const* G, float* const* m, float* const* v,
-                                         const int64_t* n, const rc_opt_hyper* h, int n_tensors,
-                                         const int64_t* step_dev, rc_stream_t stream) {
+                                     const int64_t* n, const rc_opt_hyper* h, int n_tensors,
+                                     const int64_t* step_dev, rc_stream_t stream) {
   if (n_tensors == 0) return RC_OK;
   RC_REQUIRE(W && G && n && h && n_tensors > 0, "rc_dense_update_multi: bad arguments");
   hipStream_t s = as_stream(stream);
@@ -317,7 +312,7 @@ extern "C" int rc_dense_update_multi_dev(float* const* W, const float* const* G,
       RC_TRY(fill_opt_scalars(&h[t], &a.o[T], /*dense=*/true));
       a.lr[T] = (float)h[t].lr;
       RC_REQUIRE(step_dev == nullptr || (h[t].beta1 == h[0].beta1 && h[t].beta2 == h[0].beta2),
-                 "rc_dense_update_multi_dev: one (beta1, beta2) per call");
+                 "rc_dense_update_multi: one (beta1, beta2) per call with step_dev");
       a.aligned[T] = al(W[t]) && al(G[t]) && al(mt) && al(vt);
       a.blk0[T] = blocks;
       const int64_t nb = (n[t] + kMultiChunk - 1) / kMultiChunk;

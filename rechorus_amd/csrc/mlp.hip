@@ -1018,25 +1018,11 @@ extern "C" size_t rc_linear_bwd_workspace_bytes(int64_t M, int N, int K) {
   return dz + part + mlp_split_bytes(M, K, N);   // (the dX product: [M, K] out, reduction over N)
 }
 
-static int linear_fwd_impl(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
-                           const uint64_t* seed_dev, uint32_t site, float* Y, void* ws, size_t ws_bytes, rc_stream_t stream);
-
+// ws (rc_linear_fwd_workspace_bytes) may be NULL: with one, small batches are cut along the reduction (split-K)
 extern "C" int rc_linear_fwd(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
-                             const uint64_t* seed_dev, uint32_t site, float* Y, rc_stream_t stream) {
-  return linear_fwd_impl(X, W, b, M, N, K, relu, drop_p, seed_dev, site, Y, nullptr, 0, stream);
-}
-
-// the same with a workspace (rc_linear_fwd_workspace_bytes): small batches are cut along the reduction (split-K)
-extern "C" int rc_linear_fwd_ws(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
-                                const uint64_t* seed_dev, uint32_t site, float* Y, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(ws == nullptr || ws_bytes >= rc_linear_fwd_workspace_bytes(M, N, K), "rc_linear_fwd_ws: workspace %zu < %zu", ws_bytes,
+                             const uint64_t* seed_dev, uint32_t site, float* Y, void* ws, size_t ws_bytes, rc_stream_t stream) {
+  RC_REQUIRE(ws == nullptr || ws_bytes >= rc_linear_fwd_workspace_bytes(M, N, K), "rc_linear_fwd: workspace %zu < %zu", ws_bytes,
              rc_linear_fwd_workspace_bytes(M, N, K));
-  return linear_fwd_impl(X, W, b, M, N, K, relu, drop_p, seed_dev, site, Y, ws, ws_bytes, stream);
-}
-
-static int linear_fwd_impl(const float* X, const float* W, const float* b, int64_t M, int N, int K, int relu, float drop_p,
-                           const uint64_t* seed_dev, uint32_t site, float* Y, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  (void)ws_bytes;
   if (M == 0) return RC_OK;
   RC_REQUIRE(X && W && Y, "rc_linear_fwd: null pointer");
   RC_REQUIRE(M > 0 && N >= 1 && K >= 1 && N < 65536, "rc_linear_fwd: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
@@ -1055,26 +1041,13 @@ static int linear_fwd_impl(const float* X, const float* W, const float* b, int64
   return mlp_product(g, static_cast<float*>(ws), as_stream(stream));
 }
 
-static int linear_bwd_impl(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K, float drop_p,
-                           int x_act, float x_drop_p, float* dX, float* dW, float* db, void* ws, size_t ws_bytes, rc_stream_t stream);
-
-extern "C" int rc_linear_bwd(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K,
-                             float drop_p, float* dX, float* dW, float* db, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return linear_bwd_impl(X, W, Y, dY, M, N, K, drop_p, 0, 0.f, dX, dW, db, ws, ws_bytes, stream);
-}
-
-// rc_linear_bwd inside a chain of layers: with x_act != 0 the input X of this layer is the drop(relu(.)) output of the layer
+// Inside a chain of layers: with x_act != 0 the input X of this layer is the drop(relu(.)) output of the layer
 // below, and dX comes out already multiplied by that layer's mask (X > 0 ? 1 / (1 - x_drop_p) : 0) in the product's epilogue --
 // the layer below is then called with Y = NULL (its dY is its dZ): one pass over [M, K] less per layer boundary.
-extern "C" int rc_linear_bwd_chain(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K,
-                                   float drop_p, int x_act, float x_drop_p, float* dX, float* dW, float* db, void* ws,
-                                   size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(x_drop_p >= 0.f && x_drop_p < 1.f, "rc_linear_bwd_chain: dropout p=%g of the layer below outside [0, 1)", (double)x_drop_p);
-  return linear_bwd_impl(X, W, Y, dY, M, N, K, drop_p, x_act, x_drop_p, dX, dW, db, ws, ws_bytes, stream);
-}
-
-static int linear_bwd_impl(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K, float drop_p,
-                           int x_act, float x_drop_p, float* dX, float* dW, float* db, void* ws, size_t ws_bytes, rc_stream_t stream) {
+extern "C" int rc_linear_bwd(const float* X, const float* W, const float* Y, const float* dY, int64_t M, int N, int K,
+                             float drop_p, int x_act, float x_drop_p, float* dX, float* dW, float* db, void* ws,
+                             size_t ws_bytes, rc_stream_t stream) {
+  RC_REQUIRE(x_drop_p >= 0.f && x_drop_p < 1.f, "rc_linear_bwd: dropout p=%g of the layer below outside [0, 1)", (double)x_drop_p);
   RC_REQUIRE(X && W && dY && (dW || dX), "rc_linear_bwd: null pointer");
   RC_REQUIRE(M >= 0 && N >= 1 && K >= 1, "rc_linear_bwd: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
   hipStream_t s = as_stream(stream);
@@ -1110,7 +1083,7 @@ static int linear_bwd_impl(const float* X, const float* W, const float* Y, const
     float* dx_part = mlp_k_splits(M, K, N) > 1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(part) + align_up((size_t)mlp_dw_parts(M, N, K) * (size_t)N * (size_t)(K + 1) * sizeof(float), 256)) : nullptr;
     RC_TRY(mlp_product(g, dx_part, s));
   }
-  if (dW == nullptr) return RC_OK;   // (rc_linear_bwd_chain: the caller forms the weight gradient in another call, e.g. on another stream)
+  if (dW == nullptr) return RC_OK;   // (the caller forms the weight gradient in another call, e.g. on another stream)
   if (mlp_dw_narrow_ok(M, N, K) && reinterpret_cast<uintptr_t>(X) % 16 == 0) {   // one to four outputs: a weighted column sum
     const int gpb = kBlock / (K / 4);
     int64_t wgs = (M + gpb - 1) / gpb;

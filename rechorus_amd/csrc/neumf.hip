@@ -592,15 +592,8 @@ static int set_dropout(NeumfArgs& a, float drop_p, const uint64_t* seed_dev, con
 extern "C" int rc_neumf_fwd(const float* mf_u, const float* mf_i, const float* mlp_u,
                             const float* mlp_i, const float* W1, const float* b1,
                             const float* w_out, const int64_t* uid, const int64_t* iid, int B,
-                            int C, int d, int l1, float* pred, rc_stream_t stream) {
-  return rc_neumf_fwd_dropout(mf_u, mf_i, mlp_u, mlp_i, W1, b1, w_out, uid, iid, B, C, d, l1, 0.f, nullptr, pred, stream);
-}
-
-extern "C" int rc_neumf_fwd_dropout(const float* mf_u, const float* mf_i, const float* mlp_u,
-                                    const float* mlp_i, const float* W1, const float* b1,
-                                    const float* w_out, const int64_t* uid, const int64_t* iid, int B,
-                                    int C, int d, int l1, float drop_p, const uint64_t* seed_dev,
-                                    float* pred, rc_stream_t stream) {
+                            int C, int d, int l1, float drop_p, const uint64_t* seed_dev,
+                            float* pred, rc_stream_t stream) {
   if (B == 0) return RC_OK;
   RC_REQUIRE(mf_u && mf_i && mlp_u && mlp_i && W1 && b1 && w_out && uid && iid && pred,
              "rc_neumf_fwd: null pointer");
@@ -618,20 +611,10 @@ extern "C" int rc_neumf_fwd_dropout(const float* mf_u, const float* mf_i, const 
 extern "C" int rc_neumf_bwd(const float* mf_u, const float* mf_i, const float* mlp_u,
                             const float* mlp_i, const float* W1, const float* b1,
                             const float* w_out, const int64_t* uid, const int64_t* iid,
-                            const float* gpred, int B, int C, int d, int l1, float* g_mf_u,
-                            float* g_mf_i, float* g_mlp_u, float* g_mlp_i, float* dW1, float* db1,
-                            float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return rc_neumf_bwd_dropout(mf_u, mf_i, mlp_u, mlp_i, W1, b1, w_out, uid, iid, gpred, B, C, d, l1, 0.f, nullptr,
-                              g_mf_u, g_mf_i, g_mlp_u, g_mlp_i, dW1, db1, dw_out, ws, ws_bytes, stream);
-}
-
-extern "C" int rc_neumf_bwd_dropout(const float* mf_u, const float* mf_i, const float* mlp_u,
-                                    const float* mlp_i, const float* W1, const float* b1,
-                                    const float* w_out, const int64_t* uid, const int64_t* iid,
-                                    const float* gpred, int B, int C, int d, int l1, float drop_p,
-                                    const uint64_t* seed_dev, float* g_mf_u, float* g_mf_i, float* g_mlp_u,
-                                    float* g_mlp_i, float* dW1, float* db1, float* dw_out, void* ws,
-                                    size_t ws_bytes, rc_stream_t stream) {
+                            const float* gpred, int B, int C, int d, int l1, float drop_p,
+                            const uint64_t* seed_dev, float* g_mf_u, float* g_mf_i, float* g_mlp_u,
+                            float* g_mlp_i, float* dW1, float* db1, float* dw_out, void* ws,
+                            size_t ws_bytes, rc_stream_t stream) {
   if (B == 0) return RC_OK;
   RC_REQUIRE(mf_u && mf_i && mlp_u && mlp_i && W1 && b1 && w_out && uid && iid && gpred && g_mf_u &&
                  g_mf_i && g_mlp_u && g_mlp_i && dW1 && db1 && dw_out && ws,

@@ -69,7 +69,7 @@ struct NeumfStepArgs {
   float* pwout;
   OptScalars opt;
   // DROP instantiations: training-mode dropout on the hidden layer (NeuMF.py:58/70, nn.Dropout after the ReLU) with the mask of
-  // rc_neumf_fwd_dropout: feature f of candidate n = b C + c is dropped iff word (f & 3) of Philox4x32-10(key = *seed_dev,
+  // rc_neumf_fwd: feature f of candidate n = b C + c is dropped iff word (f & 3) of Philox4x32-10(key = *seed_dev,
   // counter = (n, f >> 2)) < drop_thresh; kept values are scaled by keep_scale.  Pass 2 regenerates pass 1's mask.
   const uint64_t* seed_dev;
   uint32_t drop_thresh;
@@ -738,7 +738,7 @@ extern "C" size_t rc_neumf_train_step_marks_bytes(int64_t n_items) {
 }
 
 // the two marking passes / the clearing pass on their own: a caller that knows the NEXT batch (BaseRunner.fit does) marks it on a
-// second stream while this step's updates run and hands the prepared buffer to rc_neumf_train_step_marked
+// second stream while this step's updates run and hands the prepared buffer to rc_neumf_train_step (marks_prepared = 1)
 extern "C" int rc_neumf_mark_rows(const int64_t* iid, int64_t n, int64_t n_items, void* marks, rc_stream_t stream) {
   if (n == 0) return RC_OK;
   RC_REQUIRE(iid && marks && n > 0 && n < ((int64_t)1 << 32) && n_items >= 1, "rc_neumf_mark_rows: bad arguments");
@@ -760,12 +760,14 @@ extern "C" int rc_neumf_unmark_rows(const int64_t* iid, int64_t n, int64_t n_ite
   return RC_OK;
 }
 
-static int neumf_train_step_impl(bool marked, float drop_p, const uint64_t* seed_dev, float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
-                                 float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
-                                 const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                                 void* marks, const rc_opt_hyper* h, float inv_b, float* loss_vec, float* pred,
-                                 float* g_mf_i, float* g_mlp_i, float* gu_mf, float* gu_mlp, float* dW1, float* db1,
-                                 float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
+extern "C" int rc_neumf_train_step(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
+                                   float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
+                                   const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
+                                   void* marks, int marks_prepared, const rc_opt_hyper* h, float inv_b, float drop_p,
+                                   const uint64_t* seed_dev, float* loss_vec, float* pred, float* g_mf_i, float* g_mlp_i,
+                                   float* gu_mf, float* gu_mlp, float* dW1, float* db1, float* dw_out, void* ws,
+                                   size_t ws_bytes, rc_stream_t stream) {
+  const bool marked = marks_prepared != 0;
   if (B == 0) return RC_OK;
   RC_REQUIRE(mf_u && mf_i && mlp_u && mlp_i && W1 && b1 && w_out && uid && iid && marks && loss_vec && g_mf_i && g_mlp_i && gu_mf &&
                  gu_mlp && dW1 && db1 && dw_out && ws,
@@ -782,7 +784,7 @@ static int neumf_train_step_impl(bool marked, float drop_p, const uint64_t* seed
   if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(RC_ERR_INVALID_ARG, "rc_neumf_train_step: dropout p=%g outside [0, 1)", (double)drop_p);
   if (drop_p > 0.f) {
     if (!seed_dev) return fail(RC_ERR_INVALID_ARG, "rc_neumf_train_step: dropout p=%g needs a device seed", (double)drop_p);
-    a.seed_dev = seed_dev;      // (as rc_neumf_fwd_dropout)
+    a.seed_dev = seed_dev;      // (as rc_neumf_fwd)
     a.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0);
     a.keep_scale = 1.0f / (1.0f - drop_p);
   }
@@ -820,38 +822,6 @@ static int neumf_train_step_impl(bool marked, float drop_p, const uint64_t* seed
   RC_TRY(rc);
   RC_LAUNCH_CHECK();
   return neumf_reduce_partials(a.pW1, a.pb1, a.pwout, dW1, db1, dw_out, cW, cb, co, grid, s);
-}
-
-extern "C" int rc_neumf_train_step(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
-                                   float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
-                                   const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                                   void* marks, const rc_opt_hyper* h, float inv_b, float* loss_vec, float* pred,
-                                   float* g_mf_i, float* g_mlp_i, float* gu_mf, float* gu_mlp, float* dW1, float* db1,
-                                   float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return neumf_train_step_impl(false, 0.f, nullptr, mf_u, mf_i, mlp_u, mlp_i, m_mf_i, v_mf_i, m_mlp_i, v_mlp_i, W1, b1, w_out, uid, iid, B, C, d, l1,
-                               n_items, marks, h, inv_b, loss_vec, pred, g_mf_i, g_mlp_i, gu_mf, gu_mlp, dW1, db1, dw_out, ws, ws_bytes, stream);
-}
-
-extern "C" int rc_neumf_train_step_marked(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
-                                          float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
-                                          const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                                          void* marks, const rc_opt_hyper* h, float inv_b, float* loss_vec, float* pred,
-                                          float* g_mf_i, float* g_mlp_i, float* gu_mf, float* gu_mlp, float* dW1, float* db1,
-                                          float* dw_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return neumf_train_step_impl(true, 0.f, nullptr, mf_u, mf_i, mlp_u, mlp_i, m_mf_i, v_mf_i, m_mlp_i, v_mlp_i, W1, b1, w_out, uid, iid, B, C, d, l1,
-                               n_items, marks, h, inv_b, loss_vec, pred, g_mf_i, g_mlp_i, gu_mf, gu_mlp, dW1, db1, dw_out, ws, ws_bytes, stream);
-}
-
-extern "C" int rc_neumf_train_step_dropout(float* mf_u, float* mf_i, float* mlp_u, float* mlp_i, float* m_mf_i, float* v_mf_i,
-                                           float* m_mlp_i, float* v_mlp_i, const float* W1, const float* b1, const float* w_out,
-                                           const int64_t* uid, const int64_t* iid, int B, int C, int d, int l1, int64_t n_items,
-                                           void* marks, int marks_prepared, const rc_opt_hyper* h, float inv_b, float drop_p,
-                                           const uint64_t* seed_dev, float* loss_vec, float* pred, float* g_mf_i, float* g_mlp_i,
-                                           float* gu_mf, float* gu_mlp, float* dW1, float* db1, float* dw_out, void* ws,
-                                           size_t ws_bytes, rc_stream_t stream) {
-  return neumf_train_step_impl(marks_prepared != 0, drop_p, seed_dev, mf_u, mf_i, mlp_u, mlp_i, m_mf_i, v_mf_i, m_mlp_i, v_mlp_i, W1, b1, w_out,
-                               uid, iid, B, C, d, l1, n_items, marks, h, inv_b, loss_vec, pred, g_mf_i, g_mlp_i, gu_mf, gu_mlp, dW1, db1,
-                               dw_out, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_neumf_head_fwd_bwd(const float* mf_u, const float* mlp_u, int64_t ld_u, const float* mf_i, const float* mlp_i,

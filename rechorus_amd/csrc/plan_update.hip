@@ -616,10 +616,24 @@ extern "C" int rc_plan_update(float* W, float* m, float* v, int d, const rc_plan
   return run_side_update(a, h, d, n_occ, ws, ws_bytes, stream, "rc_plan_update");
 }
 
-static int plan_update_pair_impl(uint32_t* zeroed_counters, int64_t src_ld, float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
+/* src_b != NULL: two contiguous gradient sources [n, d], src_ld = 0.  src_b == NULL: both sources in ONE block: occurrence o reads
+ * src_a[o - occ_base, 0 .. d) for table a and [d .. 2 d) for table b, rows src_ld floats apart (a multiple of 4, >= 2 d) -- the
+ * (d mf | d mlp) rows a row-sharded NeuMF rank receives from the others, used where they lie instead of through two contiguous copies.
+ * counters: NULL (the call zeroes its own), or the update's eight ticket counters (8 uint32, device) supplied by the caller,
+ * ZERO-FILLED where that cost nothing (with the plan's own buffers, beside other work on another stream) and used by nobody since: the
+ * one-launch memset in front of the update -- on the critical path of a step between its fused kernel and its table updates -- is
+ * left out. */
+extern "C" int rc_plan_update_pair(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
                                    const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                                   const float* src_a, const float* src_b, int64_t occ_base, const rc_opt_hyper* h,
-                                   void* ws, size_t ws_bytes, rc_stream_t stream) {
+                                   const float* src_a, const float* src_b, int64_t src_ld, int64_t occ_base, const rc_opt_hyper* h,
+                                   uint32_t* counters, void* ws, size_t ws_bytes, rc_stream_t stream) {
+  if (src_b != nullptr) {
+    RC_REQUIRE(src_ld == 0, "rc_plan_update_pair: src_ld = %lld with two contiguous sources (must be 0 when src_b is given)", (long long)src_ld);
+  } else {
+    RC_REQUIRE(src_a != nullptr && src_ld >= 2 * (int64_t)d && src_ld % 4 == 0 && src_ld / 4 < ((int64_t)1 << 32),
+               "rc_plan_update_pair: src_ld = %lld floats (a multiple of 4, at least 2 d)", (long long)src_ld);
+    src_b = src_a + d;
+  }
   if (n_occ == 0) return RC_OK;
   RC_REQUIRE(W_a && W_b && rows && n_rows && occ && src_a && src_b && h && ws, "rc_plan_update_pair: null pointer");
   RC_REQUIRE(n_occ > 0 && n_occ < ((int64_t)1 << 31) && occ_base >= 0 && occ_base < ((int64_t)1 << 31),
@@ -638,39 +652,7 @@ static int plan_update_pair_impl(uint32_t* zeroed_counters, int64_t src_ld, floa
   a.side[0].rows = rows;
   a.side[0].n_rows = n_rows;
   a.occ = occ;
-  return run_side_update(a, h, 2 * d, n_occ, ws, ws_bytes, stream, "rc_plan_update_pair", zeroed_counters);
-}
-
-extern "C" int rc_plan_update_pair(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
-                                   const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                                   const float* src_a, const float* src_b, int64_t occ_base, const rc_opt_hyper* h,
-                                   void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return plan_update_pair_impl(nullptr, 0, W_a, m_a, v_a, W_b, m_b, v_b, d, rows, n_rows, occ, n_occ, src_a, src_b, occ_base, h, ws, ws_bytes, stream);
-}
-
-/* rc_plan_update_pair with both gradient sources in ONE block: occurrence o reads src_block[o - occ_base, 0 .. d) for table a and
- * [d .. 2 d) for table b, rows src_ld floats apart (a multiple of 4, >= 2 d) -- the (d mf | d mlp) rows a row-sharded NeuMF rank
- * receives from the others, used where they lie instead of through two contiguous copies.  counters: as rc_plan_update_pair_zeroed,
- * or NULL (the call zeroes its own). */
-extern "C" int rc_plan_update_pair_block(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
-                                         const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                                         const float* src_block, int64_t src_ld, int64_t occ_base, const rc_opt_hyper* h,
-                                         uint32_t* counters, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(src_block != nullptr && src_ld >= 2 * (int64_t)d && src_ld % 4 == 0 && src_ld / 4 < ((int64_t)1 << 32),
-             "rc_plan_update_pair_block: src_ld = %lld floats (a multiple of 4, at least 2 d)", (long long)src_ld);
-  return plan_update_pair_impl(counters, src_ld, W_a, m_a, v_a, W_b, m_b, v_b, d, rows, n_rows, occ, n_occ, src_block, src_block + d, occ_base, h, ws,
-                               ws_bytes, stream);
-}
-
-/* rc_plan_update_pair with the update's eight ticket counters supplied by the caller, ZERO-FILLED where that cost nothing (with the
- * plan's own buffers, beside other work on another stream) and used by nobody since: the one-launch memset in front of the update --
- * on the critical path of a step between its fused kernel and its table updates -- is left out.  counters: 8 uint32, device. */
-extern "C" int rc_plan_update_pair_zeroed(float* W_a, float* m_a, float* v_a, float* W_b, float* m_b, float* v_b, int d,
-                                          const rc_plan_row* rows, const uint32_t* n_rows, const uint32_t* occ, int64_t n_occ,
-                                          const float* src_a, const float* src_b, int64_t occ_base, const rc_opt_hyper* h,
-                                          uint32_t* counters, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(counters != nullptr, "rc_plan_update_pair_zeroed: null pointer");
-  return plan_update_pair_impl(counters, 0, W_a, m_a, v_a, W_b, m_b, v_b, d, rows, n_rows, occ, n_occ, src_a, src_b, occ_base, h, ws, ws_bytes, stream);
+  return run_side_update(a, h, 2 * d, n_occ, ws, ws_bytes, stream, "rc_plan_update_pair", counters);
 }
 
 /* out[row, :] = sum over the row's occurrences of their gradient rows, for the rows the plan lists (other rows of `out`

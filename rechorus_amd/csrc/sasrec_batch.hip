@@ -2129,10 +2129,10 @@ static int sb_set_dropout(SbDrop& dr, float drop_p, const uint64_t* seed_dev, co
   return RC_OK;
 }
 
-extern "C" int rc_sasrec_batch_fwd_dropout(const float* item_emb, const float* pos_emb, const float* const* layer_params,
-                                           int n_layers, int n_heads, const int64_t* hist, const int64_t* lengths, int B,
-                                           int L, int d, float drop_p, const uint64_t* seed_dev, float* hv, float* state,
-                                           void* ws, size_t ws_bytes, rc_stream_t stream) {
+extern "C" int rc_sasrec_batch_fwd(const float* item_emb, const float* pos_emb, const float* const* layer_params,
+                                   int n_layers, int n_heads, const int64_t* hist, const int64_t* lengths, int B,
+                                   int L, int d, float drop_p, const uint64_t* seed_dev, float* hv, float* state,
+                                   void* ws, size_t ws_bytes, rc_stream_t stream) {
   if (B == 0) return RC_OK;
   RC_REQUIRE(item_emb && pos_emb && hist && lengths && hv && state && ws, "rc_sasrec_batch_fwd: null pointer");
   if (!rc_sasrec_supported(d, n_layers, n_heads, L))
@@ -2149,17 +2149,10 @@ extern "C" int rc_sasrec_batch_fwd_dropout(const float* item_emb, const float* p
                  : sb_forward<32>(item_emb, pos_emb, layer, n_layers, n_heads, hist, lengths, B, L, hv, state, w, dr, s);
 }
 
-extern "C" int rc_sasrec_batch_fwd(const float* item_emb, const float* pos_emb, const float* const* layer_params,
-                                   int n_layers, int n_heads, const int64_t* hist, const int64_t* lengths, int B, int L,
-                                   int d, float* hv, float* state, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return rc_sasrec_batch_fwd_dropout(item_emb, pos_emb, layer_params, n_layers, n_heads, hist, lengths, B, L, d, 0.f, nullptr,
-                                     hv, state, ws, ws_bytes, stream);
-}
-
-extern "C" int rc_sasrec_batch_bwd_dropout(const float* const* layer_params, int n_layers, int n_heads,
-                                           const int64_t* lengths, int B, int L, int d, float drop_p,
-                                           const uint64_t* seed_dev, const float* state, const float* dhv, float* g_hist,
-                                           float* dense_grads, void* ws, size_t ws_bytes, rc_stream_t stream) {
+extern "C" int rc_sasrec_batch_bwd(const float* const* layer_params, int n_layers, int n_heads,
+                                   const int64_t* lengths, int B, int L, int d, float drop_p,
+                                   const uint64_t* seed_dev, const float* state, const float* dhv, float* g_hist,
+                                   float* dense_grads, void* ws, size_t ws_bytes, rc_stream_t stream) {
   if (B == 0) return RC_OK;
   RC_REQUIRE(lengths && state && dhv && g_hist && dense_grads && ws, "rc_sasrec_batch_bwd: null pointer");
   if (!rc_sasrec_supported(d, n_layers, n_heads, L))
@@ -2202,13 +2195,6 @@ extern "C" int rc_sasrec_batch_bwd_part(const float* const* layer_params, int n_
   hipStream_t s = as_stream(stream);
   return d == 64 ? sb_backward<64>(layer, n_layers, n_heads, lengths, B, L, state, dhv, g_hist, dense_grads, w, dr, s, part)
                  : sb_backward<32>(layer, n_layers, n_heads, lengths, B, L, state, dhv, g_hist, dense_grads, w, dr, s, part);
-}
-
-extern "C" int rc_sasrec_batch_bwd(const float* const* layer_params, int n_layers, int n_heads, const int64_t* lengths,
-                                   int B, int L, int d, const float* state, const float* dhv, float* g_hist,
-                                   float* dense_grads, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return rc_sasrec_batch_bwd_dropout(layer_params, n_layers, n_heads, lengths, B, L, d, 0.f, nullptr, state, dhv, g_hist,
-                                     dense_grads, ws, ws_bytes, stream);
 }
 
 extern "C" size_t rc_sasrec_pos_grad_workspace_bytes(int B, int L, int d) {

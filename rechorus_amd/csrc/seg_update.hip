@@ -68,8 +68,8 @@ struct SegArgs {
   uint32_t* narrow_ws;   // narrow rows, dense gradient: room for the tiles' boundary sums (seg_narrow_tiles_kernel); null = one wave per segment
   int planned;   // rows route: the hot rows are already listed in rows[] / chunks[] (rc_rows_plan_build): no hand-over atomics
   OptScalars o;
-  // capturable mode (hipGraph replay, rc_segmented_update_rows_dev): Adam's step count is read from device memory and the two
-  // bias-correction scalars are derived from it in the kernel (as rc_dense_update_multi_dev does) instead of on the host
+  // capturable mode (hipGraph replay, rc_segmented_update_rows with step_dev): Adam's step count is read from device memory and the two
+  // bias-correction scalars are derived from it in the kernel (as rc_dense_update_multi (step_dev) does) instead of on the host
   const int64_t* step_dev;
   double beta1, beta2, lr;
   // pair mode (rc_segmented_update_pair): two tables of width D/2 that share keys / perm / heads are updated as
@@ -1354,24 +1354,14 @@ extern "C" size_t rc_segmented_workspace_bytes(int64_t n_occ, int d) {
 extern "C" int rc_segmented_update(float* W, float* m, float* v, int d, const uint32_t* keys,
                                    const uint32_t* perm, int64_t n_occ, const float* coef,
                                    const float* src, const int64_t* src_index, int div,
-                                   const rc_opt_hyper* h, float* dense_grad,
+                                   const float* src2, int64_t n_split, int64_t key_base,
+                                   int64_t occ_base, const rc_opt_hyper* h, float* dense_grad,
                                    const uint32_t* heads, const uint32_t* n_heads, int flags,
                                    void* ws, size_t ws_bytes, rc_stream_t stream) {
-  return rc_segmented_update2(W, m, v, d, keys, perm, n_occ, coef, src, src_index, div, nullptr, n_occ, 0, 0,
-                              h, dense_grad, heads, n_heads, flags, ws, ws_bytes, stream);
-}
-
-extern "C" int rc_segmented_update2(float* W, float* m, float* v, int d, const uint32_t* keys,
-                                    const uint32_t* perm, int64_t n_occ, const float* coef,
-                                    const float* src, const int64_t* src_index, int div,
-                                    const float* src2, int64_t n_split, int64_t key_base,
-                                    int64_t occ_base, const rc_opt_hyper* h, float* dense_grad,
-                                    const uint32_t* heads, const uint32_t* n_heads, int flags,
-                                    void* ws, size_t ws_bytes, rc_stream_t stream) {
   if (n_occ == 0) return RC_OK;
-  RC_REQUIRE(n_split >= 0 && n_split <= n_occ, "rc_segmented_update2: n_split out of range");
+  RC_REQUIRE(n_split >= 0 && n_split <= n_occ, "rc_segmented_update: n_split out of range");
   RC_REQUIRE(key_base >= 0 && occ_base >= 0 && key_base < ((int64_t)1 << 32) && occ_base < ((int64_t)1 << 31),
-             "rc_segmented_update2: key_base / occ_base out of range");
+             "rc_segmented_update: key_base / occ_base out of range");
   RC_REQUIRE(keys && perm && src && ws, "rc_segmented_update: null pointer");
   RC_REQUIRE(d >= 1 && div >= 1 && n_occ > 0 && n_occ < ((int64_t)1 << 31),
              "rc_segmented_update: bad shape d=%d div=%d n_occ=%lld", d, div, (long long)n_occ);
@@ -1433,13 +1423,15 @@ extern "C" size_t rc_segmented_rows_workspace_bytes(int64_t n_rows, int64_t n_oc
   return rc_segmented_workspace_bytes(n_occ, d) + align_up((2 * (size_t)n_rows + 64) * sizeof(uint32_t), 256) + 256;
 }
 
-// rc_segmented_update2 for a table of n_rows rows that collect many occurrences each (section 4 above); keys / perm
+// rc_segmented_update for a table of n_rows rows that collect many occurrences each (section 4 above); keys / perm
 // from a plain rc_sort_ids.  Same gradient sources and outputs; d in {16, 32, 64, 128, 256}, 16-byte aligned buffers.
-static int segmented_update_rows(float* W, float* m, float* v, int d, int64_t n_rows, const uint32_t* keys,
-                                 const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
-                                 const int64_t* src_index, int div, const float* src2, int64_t n_split,
-                                 const rc_opt_hyper* h, const int64_t* step_dev, float* dense_grad, void* ws, size_t ws_bytes,
-                                 rc_stream_t stream) {
+// step_dev != NULL: Adam's step count is in device memory (step_dev[0] >= 1 when the kernels run; h->step is not used): the launch
+// can be captured in a hipGraph and replayed while the host advances the counter with rc_step_increment.  Other optimizers: no effect.
+extern "C" int rc_segmented_update_rows(float* W, float* m, float* v, int d, int64_t n_rows, const uint32_t* keys,
+                                        const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
+                                        const int64_t* src_index, int div, const float* src2, int64_t n_split,
+                                        const rc_opt_hyper* h, const int64_t* step_dev, float* dense_grad, void* ws,
+                                        size_t ws_bytes, rc_stream_t stream) {
   if (n_occ == 0) return RC_OK;
   RC_REQUIRE(n_split >= 0 && n_split <= n_occ, "rc_segmented_update_rows: n_split out of range");
   RC_REQUIRE(keys && perm && src && ws, "rc_segmented_update_rows: null pointer");
@@ -1489,27 +1481,6 @@ static int segmented_update_rows(float* W, float* m, float* v, int d, int64_t n_
     case MODE_ADAM: return launch_seg_rows_mode<MODE_ADAM>(a, start, end, (uint32_t)n_rows, s);
     default: return launch_seg_rows_mode<MODE_ADAGRAD>(a, start, end, (uint32_t)n_rows, s);
   }
-}
-
-extern "C" int rc_segmented_update_rows(float* W, float* m, float* v, int d, int64_t n_rows, const uint32_t* keys,
-                                        const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
-                                        const int64_t* src_index, int div, const float* src2, int64_t n_split,
-                                        const rc_opt_hyper* h, float* dense_grad, void* ws, size_t ws_bytes,
-                                        rc_stream_t stream) {
-  return segmented_update_rows(W, m, v, d, n_rows, keys, perm, n_occ, coef, src, src_index, div, src2, n_split, h, nullptr,
-                               dense_grad, ws, ws_bytes, stream);
-}
-
-// The same with Adam's step count in device memory (step_dev[0] >= 1 when the kernels run; h->step is not used): the launch can be
-// captured in a hipGraph and replayed while the host advances the counter with rc_step_increment.  Other optimizers: as above.
-extern "C" int rc_segmented_update_rows_dev(float* W, float* m, float* v, int d, int64_t n_rows, const uint32_t* keys,
-                                            const uint32_t* perm, int64_t n_occ, const float* coef, const float* src,
-                                            const int64_t* src_index, int div, const float* src2, int64_t n_split,
-                                            const rc_opt_hyper* h, const int64_t* step_dev, float* dense_grad, void* ws,
-                                            size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(step_dev != nullptr, "rc_segmented_update_rows_dev: step_dev is null");
-  return segmented_update_rows(W, m, v, d, n_rows, keys, perm, n_occ, coef, src, src_index, div, src2, n_split, h, step_dev,
-                               dense_grad, ws, ws_bytes, stream);
 }
 
 // ---- rows route from a counting sort (section 5) -----------------------------------------------------------------------------
@@ -1613,7 +1584,7 @@ extern "C" int rc_rows_plan_views(void* ws, int64_t n_rows, int64_t n_occ, int d
 }
 
 // rc_segmented_update_rows on a plan of rc_rows_plan_build (same ws, same n_rows / n_occ / d; occurrence o < n_split = position o
-// of ids_a, the others position o - n_split of ids_b): two launches, nothing to zero.  step_dev as rc_segmented_update_rows_dev
+// of ids_a, the others position o - n_split of ids_b): two launches, nothing to zero.  step_dev as rc_segmented_update_rows
 // (null: h->step).
 extern "C" int rc_rows_plan_update(float* W, float* m, float* v, int d, int64_t n_rows, int64_t n_occ, const float* coef,
                                    const float* src, const int64_t* src_index, int div, const float* src2, int64_t n_split,

@@ -13,7 +13,7 @@
 // i < min(len_b, L).  Rows that are not valid hold zeros at every layer boundary and zero gradients (the reference computes
 // garbage there, multiplies it by 0 at the end -- SASRec.py:74 -- and no valid row ever attends to one: padding is on the
 // right and the mask is causal), so GEMMs over all B * L rows add nothing for them.  `off` [B + 1] = exclusive prefix sums of
-// min(len_b, L): the compact row index off[b] + i keys the dropout mask exactly as rc_sasrec_batch_fwd_dropout does
+// min(len_b, L): the compact row index off[b] + i keys the dropout mask exactly as rc_sasrec_batch_fwd does
 // (oracle/sasrec_oracle.dropout_keep), so both encoders draw the same mask from the same seed.
 //
 // One wave per attention row (query row forward / for dQ, key row for dK and dV): scores one lane per key, the weighted sums

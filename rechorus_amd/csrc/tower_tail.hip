@@ -15,7 +15,7 @@
 // rc_linear_fwd: element (m, n) dropped iff word (m & 3) of Philox4x32-10(seed, (m >> 2, site 65536 + n)) < p 2^32 -- the four
 // rows a lane holds share one Philox block), the output layer as a 16-lane DPP sum + a sum over the waves in LDS.
 // Backward: the row block's dZ2 and X go to LDS once; product 1 (reduction over N2) walks 64-column groups, its epilogue
-// applies the mask of the layer below (X is that layer's saved output) -- what rc_linear_bwd_chain does in its dX product;
+// applies the mask of the layer below (X is that layer's saved output) -- what rc_linear_bwd does in its dX product;
 // product 2 (reduction over the 16 rows) accumulates dW2 in registers across the row blocks of the workgroup; per-workgroup
 // partials are summed in fixed order by tower_tail_reduce_kernel.  No float atomics.
 #include "common.hpp"

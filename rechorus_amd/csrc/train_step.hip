@@ -327,8 +327,8 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
     RC_MARK(2);
     RC_MARK(3);
     if (fused_upd)
-      RC_TRY(rc_bprmf_fwd_bwd_update_bitmap(U, I, mI, vI, uid, iid, w.slot[slot].bitmap, B, C, d, inv_b, h, pred, w.loss_vec,
-                                            w.gpred, w.ugrad, stream));
+      RC_TRY(rc_bprmf_fwd_bwd_update(U, I, mI, vI, uid, iid, nullptr, w.slot[slot].bitmap, B, C, d, inv_b, h, pred, w.loss_vec,
+                                     w.gpred, w.ugrad, stream));
     else
       RC_TRY(rc_bprmf_fwd_bwd(U, I, uid, iid, B, C, d, inv_b, pred, w.loss_vec, w.gpred, w.ugrad, stream));
     if (two_streams && !ahead_hit) RC_HIP(hipStreamWaitEvent(s, side->join, 0));
@@ -350,7 +350,7 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
   RC_MARK(2);
   RC_MARK(3);  // (the user ids were sorted with the item ids)
   if (fused_upd)
-    RC_TRY(rc_bprmf_fwd_bwd_update(U, I, mI, vI, uid, iid, w.single, B, C, d, inv_b, h, pred,
+    RC_TRY(rc_bprmf_fwd_bwd_update(U, I, mI, vI, uid, iid, w.single, nullptr, B, C, d, inv_b, h, pred,
                                    w.loss_vec, w.gpred, w.ugrad, stream));
   else
     RC_TRY(rc_bprmf_fwd_bwd(U, I, uid, iid, B, C, d, inv_b, pred, w.loss_vec, w.gpred, w.ugrad,
@@ -359,16 +359,16 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
   RC_TRY(rc_reduce_sum(w.loss_vec, B, inv_b, loss_out, stream));
   RC_MARK(5);
   // item rows: grad_r = sum_{(b,c): iid[b,c]=r} g[b,c] * U[uid[b]]
-  RC_TRY(rc_segmented_update(I, mI, vI, d, w.keys_i, w.perm_i, n_i, w.gpred, U, uid, C, h,
-                             nullptr, fused_upd ? w.heads_i : nullptr,
+  RC_TRY(rc_segmented_update(I, mI, vI, d, w.keys_i, w.perm_i, n_i, w.gpred, U, uid, C, nullptr, n_i,
+                             /*key_base=*/0, /*occ_base=*/0, h, nullptr, fused_upd ? w.heads_i : nullptr,
                              fused_upd ? w.n_heads_i : nullptr,
                              fused_upd ? RC_SEG_SKIP_SINGLETONS : 0, w.seg_ws, w.seg_ws_bytes,
                              stream));
   RC_MARK(6);
   // user rows: grad_r = sum_{b: uid[b]=r} ugrad[b]
-  RC_TRY(rc_segmented_update2(U, mU, vU, d, w.keys_u, w.perm_u, B, nullptr, w.ugrad, nullptr, 1, nullptr, B,
-                              /*key_base=*/n_items, /*occ_base=*/n_i, h, nullptr, nullptr, nullptr, 0,
-                              w.seg_ws, w.seg_ws_bytes, stream));
+  RC_TRY(rc_segmented_update(U, mU, vU, d, w.keys_u, w.perm_u, B, nullptr, w.ugrad, nullptr, 1, nullptr, B,
+                             /*key_base=*/n_items, /*occ_base=*/n_i, h, nullptr, nullptr, nullptr, 0,
+                             w.seg_ws, w.seg_ws_bytes, stream));
   RC_MARK(7);
   }
 #undef RC_MARK

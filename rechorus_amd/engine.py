@@ -301,43 +301,28 @@ class Plan:
         """rc_plan_update_pair on list `side` ('a' | 'b'): two tables sharing the ids, per-occurrence gradient rows.
         ws_tag: suffix of the scratch buffer's cache key -- two updates that run at the same time on two streams need two.
         src_b=None: src_a is ONE block [n, >= 2 d] whose rows hold (gradient of table a | gradient of table b) side by side
-        (rc_plan_update_pair_block: the block is read where it lies, no contiguous halves)"""
+        (the block is read where it lies, no contiguous halves)"""
         d = Wa.shape[1]
+        f32 = torch.float32
         if src_b is None:
             if src_a.dim() != 2 or src_a.stride(1) != 1 or src_a.shape[1] < 2 * d or src_a.stride(0) % 4:
                 raise ValueError("update_pair: a block source is [n, >= 2 d] with unit column stride and a row stride that is a multiple of 4")
-            n = self.n_a + self.n_b
-            rows, cnt, base = self._side(side)
-            ws = workspace(_lib.load().rc_plan_update_workspace_bytes(n, 2 * d), Wa.device, self.tag + ".upd" + ws_tag)
-            f32 = torch.float32
-            p = lambda t: C.c_void_p(t.data_ptr())
-            zc = getattr(self, "upd_counters", None)
-            c = zc.pop(side) if (zc is not None and side in zc) else None
-            if c is not None:
-                c.record_stream(torch.cuda.current_stream(c.device))
-            _lib.call("rc_plan_update_pair_block", _ptr(Wa, f32, "W_a"), _ptr(ma, f32, "m_a", True), _ptr(va, f32, "v_a", True),
-                      _ptr(Wb, f32, "W_b"), _ptr(mb, f32, "m_b", True), _ptr(vb, f32, "v_b", True), d, p(rows), p(cnt), p(self.occ), n,
-                      C.c_void_p(src_a.data_ptr()), int(src_a.stride(0)), base, C.byref(hyper), p(c) if c is not None else None,
-                      p(ws), ws.numel(), _stream())
-            return
+            srcs = (C.c_void_p(src_a.data_ptr()), None, int(src_a.stride(0)))
+        else:
+            srcs = (_ptr(src_a, f32, "src_a"), _ptr(src_b, f32, "src_b"), 0)
         n = self.n_a + self.n_b
         rows, cnt, base = self._side(side)
         ws = workspace(_lib.load().rc_plan_update_workspace_bytes(n, 2 * d), Wa.device, self.tag + ".upd" + ws_tag)
-        f32 = torch.float32
         p = lambda t: C.c_void_p(t.data_ptr())
+        # ticket counters that were zero-filled with the plan (prezero_update_counters: beside other work, on the plan's stream);
+        # one use each -- the memset in front of the update, a launch on the step's critical path, is left out
         zc = getattr(self, "upd_counters", None)
-        if zc is not None and side in zc:
-            # the update's ticket counters were zero-filled with the plan (prezero_update_counters: beside other work, on the plan's
-            # stream); one use each -- the memset in front of the update, a launch on the step's critical path, is left out
-            c = zc.pop(side)
+        c = zc.pop(side) if (zc is not None and side in zc) else None
+        if c is not None:
             c.record_stream(torch.cuda.current_stream(c.device))
-            _lib.call("rc_plan_update_pair_zeroed", _ptr(Wa, f32, "W_a"), _ptr(ma, f32, "m_a", True), _ptr(va, f32, "v_a", True),
-                      _ptr(Wb, f32, "W_b"), _ptr(mb, f32, "m_b", True), _ptr(vb, f32, "v_b", True), d, p(rows), p(cnt), p(self.occ), n,
-                      _ptr(src_a, f32, "src_a"), _ptr(src_b, f32, "src_b"), base, C.byref(hyper), p(c), p(ws), ws.numel(), _stream())
-            return
         _lib.call("rc_plan_update_pair", _ptr(Wa, f32, "W_a"), _ptr(ma, f32, "m_a", True), _ptr(va, f32, "v_a", True),
                   _ptr(Wb, f32, "W_b"), _ptr(mb, f32, "m_b", True), _ptr(vb, f32, "v_b", True), d, p(rows), p(cnt), p(self.occ), n,
-                  _ptr(src_a, f32, "src_a"), _ptr(src_b, f32, "src_b"), base, C.byref(hyper), p(ws), ws.numel(), _stream())
+                  *srcs, base, C.byref(hyper), p(c) if c is not None else None, p(ws), ws.numel(), _stream())
 
     def prezero_update_counters(self):
         """zero-fill the ticket counters of one later update_pair per side NOW, on the current stream (the plan's: beside the work the
@@ -397,10 +382,10 @@ def bprmf_fwd_bwd_update(U, I, uid, iid, single, hyper, mI=None, vI=None, inv_b=
     loss_vec = torch.empty(B, dtype=f32, device=dev)
     gpred = torch.empty((B, Cn), dtype=f32, device=dev)
     ugrad = torch.empty((B, d), dtype=f32, device=dev)
-    _lib.call("rc_bprmf_fwd_bwd_update_bitmap" if multi is not None else "rc_bprmf_fwd_bwd_update", _ptr(U, f32, "U"), _ptr(I, f32, "I"),
+    _lib.call("rc_bprmf_fwd_bwd_update", _ptr(U, f32, "U"), _ptr(I, f32, "I"),
               _ptr(mI, f32, "mI", True), _ptr(vI, f32, "vI", True),
               _ptr(uid, torch.int64, "uid"), _ptr(iid, torch.int64, "iid"),
-              _ptr(multi, torch.int32, "multi") if multi is not None else _ptr(single, torch.uint8, "single"),
+              _ptr(single, torch.uint8, "single", True), _ptr(multi, torch.int32, "multi", True),
               B, Cn, d, float(inv_b), C.byref(hyper),
               _ptr(pred, f32, "pred", True), _ptr(loss_vec, f32, "loss_vec"),
               _ptr(gpred, f32, "gpred"), _ptr(ugrad, f32, "ugrad"), _stream())
@@ -424,7 +409,7 @@ def segmented_update(keys, perm, src, hyper=None, W=None, m=None, v=None, coef=N
               _ptr(v, torch.float32, "v", allow_none=True), d,
               _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
               _ptr(coef, torch.float32, "coef", allow_none=True), _ptr(src, torch.float32, "src"),
-              _ptr(src_index, torch.int64, "src_index", allow_none=True), int(div), hp,
+              _ptr(src_index, torch.int64, "src_index", allow_none=True), int(div), None, n_occ, 0, 0, hp,
               _ptr(dense_grad, torch.float32, "dense_grad", allow_none=True),
               _ptr(heads, torch.int32, "heads", True), _ptr(n_heads, torch.int32, "n_heads", True),
               _lib.RC_SEG_SKIP_SINGLETONS if skip_singletons else 0,
@@ -645,12 +630,9 @@ def dense_update_multi(items, opt, step_dev=None, increment=True):
     Va = (C.c_void_p * T)(*[_ptr(v, f32, "v", True).value for _, _, _, _, v in items])
     na = (C.c_int64 * T)(*[w.numel() for w, _, _, _, _ in items])
     ha = (OptHyper * T)(*[h for _, _, h, _, _ in items])
-    if step_dev is None:
-        _lib.call("rc_dense_update_multi", Wa, Ga, Ma, Va, na, ha, T, _stream())
-        return
-    if increment:
+    if step_dev is not None and increment:
         _lib.call("rc_step_increment", _ptr(step_dev, torch.int64, "step_dev"), _stream())
-    _lib.call("rc_dense_update_multi_dev", Wa, Ga, Ma, Va, na, ha, T, _ptr(step_dev, torch.int64, "step_dev"), _stream())
+    _lib.call("rc_dense_update_multi", Wa, Ga, Ma, Va, na, ha, T, _ptr(step_dev, torch.int64, "step_dev", True), _stream())
 
 
 def dense_update_rows(items, step_dev, touched=2, max_blocks=0):
@@ -866,11 +848,11 @@ def step_increment(counter):
 def neumf_fwd(P, uid, iid, drop_p=0.0, seed=None):
     """P: dict mf_u, mf_i, mlp_u, mlp_i [rows,d], W1 [l1,2d], b1 [l1], w_out [d+l1] -> pred [B,C]
     (models/general/NeuMF.py:61-75).  drop_p > 0: training-mode dropout on the hidden layer, mask drawn from
-    the counter-based stream keyed by seed[0] (rc_neumf_fwd_dropout)."""
+    the counter-based stream keyed by seed[0]."""
     B, Cn = iid.shape
     d, l1 = P["mf_u"].shape[1], P["W1"].shape[0]
     pred = torch.empty((B, Cn), dtype=torch.float32, device=iid.device)
-    _lib.call("rc_neumf_fwd_dropout", *_neumf_ptrs(P), _ptr(uid, torch.int64, "uid"), _ptr(iid, torch.int64, "iid"),
+    _lib.call("rc_neumf_fwd", *_neumf_ptrs(P), _ptr(uid, torch.int64, "uid"), _ptr(iid, torch.int64, "iid"),
               B, Cn, d, l1, *_drop_args(drop_p, seed), _ptr(pred, torch.float32, "pred"), _stream())
     return pred
 
@@ -884,7 +866,7 @@ def neumf_bwd(P, uid, iid, gpred, drop_p=0.0, seed=None):
     rows = {k: torch.empty((B * Cn, d), dtype=f32, device=dev) for k in ("g_mf_u", "g_mf_i", "g_mlp_u", "g_mlp_i")}
     dense = {"W1": torch.empty_like(P["W1"]), "b1": torch.empty_like(P["b1"]), "w_out": torch.empty_like(P["w_out"])}
     ws = workspace(_lib.load().rc_neumf_workspace_bytes(B, Cn, d, l1), dev, "neumf")
-    _lib.call("rc_neumf_bwd_dropout", *_neumf_ptrs(P), _ptr(uid, torch.int64, "uid"), _ptr(iid, torch.int64, "iid"),
+    _lib.call("rc_neumf_bwd", *_neumf_ptrs(P), _ptr(uid, torch.int64, "uid"), _ptr(iid, torch.int64, "iid"),
               _ptr(gpred, f32, "gpred"), B, Cn, d, l1, *_drop_args(drop_p, seed),
               *[_ptr(rows[k], f32, k) for k in ("g_mf_u", "g_mf_i", "g_mlp_u", "g_mlp_i")],
               _ptr(dense["W1"], f32, "dW1"), _ptr(dense["b1"], f32, "db1"), _ptr(dense["w_out"], f32, "dw_out"),
@@ -913,7 +895,7 @@ def neumf_train_step(P, state, uid, iid, hyper, marks, out, inv_b=None, pred=Non
     """rc_neumf_train_step: forward + BPR loss + backward + in-place update of single-occurrence item rows.
     state: {table: {"m": .., "v": ..}} of the optimizer; marks: uint8 buffer of rc_neumf_train_step_marks_bytes(n_items), zeroed
     once (every call leaves it ready for the next; marked=True: prepared by neumf_mark_rows for this very batch, cleared by the caller); out: dict of preallocated buffers loss_vec [B], g_mf_i / g_mlp_i [B C, d], gu_mf / gu_mlp [B, d], W1 / b1 / w_out
-    gradients.  drop_p > 0: training-mode dropout on the hidden layer inside the kernel (rc_neumf_train_step_dropout; `seed` int64 [1]
+    gradients.  drop_p > 0: training-mode dropout on the hidden layer inside the kernel (`seed` int64 [1]
     on the device, the mask stream of neumf_fwd / neumf_bwd).  Returns nothing: the caller finishes the step with the plan's pair
     updates and the dense update."""
     B, Cn = iid.shape
@@ -932,10 +914,7 @@ def neumf_train_step(P, state, uid, iid, hyper, marks, out, inv_b=None, pred=Non
             _ptr(out["gu_mlp"], f32, "gu_mlp"), _ptr(out["W1"], f32, "dW1"), _ptr(out["b1"], f32, "db1"),
             _ptr(out["w_out"], f32, "dw_out"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()]
     inv = float(1.0 / B if inv_b is None else inv_b)
-    if drop_p:
-        _lib.call("rc_neumf_train_step_dropout", *head, 1 if marked else 0, C.byref(hyper), inv, *_drop_args(drop_p, seed), *tail)
-    else:
-        _lib.call("rc_neumf_train_step_marked" if marked else "rc_neumf_train_step", *head, C.byref(hyper), inv, *tail)
+    _lib.call("rc_neumf_train_step", *head, 1 if marked else 0, C.byref(hyper), inv, *_drop_args(drop_p, seed), *tail)
 
 
 def neumf_head_fwd_bwd(urows, irows, W1, b1, w_out, B, Cn, inv_b, want_pred=False):
@@ -1310,7 +1289,7 @@ def linear_fwd(X, W, b=None, relu=False, drop_p=0.0, seed=None, site=0):
     N = W.shape[0]
     Y = torch.empty((M, N), dtype=f32, device=X.device)
     ws = workspace(_lib.load().rc_linear_fwd_workspace_bytes(M, N, K), X.device, "linear_fwd")   # split-K planes of a small batch
-    _lib.call("rc_linear_fwd_ws", _ptr(X, f32, "X"), _ptr(W, f32, "W"), _ptr(b, f32, "b", True), M, N, K, 1 if relu else 0,
+    _lib.call("rc_linear_fwd", _ptr(X, f32, "X"), _ptr(W, f32, "W"), _ptr(b, f32, "b", True), M, N, K, 1 if relu else 0,
               *_drop_args(drop_p, seed), C.c_uint32(int(site)), _ptr(Y, f32, "Y"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
     return Y
 
@@ -1319,7 +1298,7 @@ def linear_bwd(X, W, Y, dY, drop_p=0.0, need_dx=True, need_db=True, x_act=False,
     """backward of linear_fwd -> (dX | None, dW, db | None).  Y: the layer's saved output when it went through
     relu (+ dropout) -- it is its own mask -- or None for a plain Linear (or when dY is already masked, see below).
     x_act: X is the drop(relu(.)) output of the layer below (dropout x_drop_p): dX comes out multiplied by that layer's mask
-    in the product's epilogue (rc_linear_bwd_chain), and the layer below is called with Y=None.
+    in the product's epilogue, and the layer below is called with Y=None.
     need_dw=False: only dX (the weight gradient comes from a second call, e.g. on another stream with its own ws_tag)."""
     f32 = torch.float32
     M, K = X.shape
@@ -1329,7 +1308,7 @@ def linear_bwd(X, W, Y, dY, drop_p=0.0, need_dx=True, need_db=True, x_act=False,
     dW = torch.empty((N, K), dtype=f32, device=dev) if need_dw else None
     db = torch.empty(N, dtype=f32, device=dev) if (need_db and need_dw) else None
     ws = workspace(_lib.load().rc_linear_bwd_workspace_bytes(M, N, K), dev, ws_tag)
-    _lib.call("rc_linear_bwd_chain", _ptr(X, f32, "X"), _ptr(W, f32, "W"), _ptr(Y, f32, "Y", True), _ptr(dY, f32, "dY"), M, N, K,
+    _lib.call("rc_linear_bwd", _ptr(X, f32, "X"), _ptr(W, f32, "W"), _ptr(Y, f32, "Y", True), _ptr(dY, f32, "dY"), M, N, K,
               C.c_float(float(drop_p)), 1 if (x_act and need_dx) else 0, C.c_float(float(x_drop_p)), _ptr(dX, f32, "dX", True),
               _ptr(dW, f32, "dW", True), _ptr(db, f32, "db", True), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
     return dX, dW, db
@@ -1443,7 +1422,7 @@ def sasrec_fwd(item_emb, pos_emb, layers, n_heads, hist, lengths, save=False, im
     impl: 'sequence' (csrc/sasrec.hip, one workgroup per sequence), 'batch' (csrc/sasrec_batch.hip, row-space
     kernels), default by batch size.  drop_p > 0: training-mode dropout of both residual branches of every layer
     (utils/layers.py:104-117), mask from the counter-based stream keyed by seed[0] (int64 [1] on the device); only
-    the batch-level kernels carry it (rc_sasrec_batch_fwd_dropout), so dropout selects them."""
+    the batch-level kernels carry it (rc_sasrec_batch_fwd), so dropout selects them."""
     B, L = hist.shape
     d = item_emb.shape[1]
     dev, f32 = hist.device, torch.float32
@@ -1460,7 +1439,7 @@ def sasrec_fwd(item_emb, pos_emb, layers, n_heads, hist, lengths, save=False, im
         state = (torch.empty(n_state, dtype=f32, device=dev) if save
                  else workspace(4 * n_state, dev, "sasrec_state").view(f32)[:n_state])
         ws = workspace(lib.rc_sasrec_batch_workspace_bytes(B, L, d, len(layers)), dev, "sasrec_batch")
-        _lib.call("rc_sasrec_batch_fwd_dropout", _ptr(item_emb, f32, "item_emb"), _ptr(pos_emb, f32, "pos_emb"),
+        _lib.call("rc_sasrec_batch_fwd", _ptr(item_emb, f32, "item_emb"), _ptr(pos_emb, f32, "pos_emb"),
                   _sas_ptr_table(layers), len(layers), int(n_heads), _ptr(hist, torch.int64, "hist"),
                   _ptr(lengths, torch.int64, "lengths"), B, L, d, *_drop_args(drop_p, seed), _ptr(hv, f32, "hv"),
                   _ptr(state, f32, "state"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
@@ -1507,7 +1486,7 @@ def sasrec_bwd(layers, n_heads, lengths, saved, dhv, drop_p=0.0, seed=None, spli
             _lib.call("rc_sasrec_batch_bwd_part", *args, 1, _stream())
             keep = (layers, lengths, saved, dhv, g_hist, dense, ws)      # alive until part 2 is enqueued
             return g_hist, _sas_dense_views(dense, n_layers, d), (lambda: (_lib.call("rc_sasrec_batch_bwd_part", *args, 2, _stream()), keep)[0])
-        _lib.call("rc_sasrec_batch_bwd_dropout", _sas_ptr_table(layers), n_layers, int(n_heads),
+        _lib.call("rc_sasrec_batch_bwd", _sas_ptr_table(layers), n_layers, int(n_heads),
                   _ptr(lengths, torch.int64, "lengths"), B, L, d, *_drop_args(drop_p, seed), _ptr(saved.data, f32, "state"),
                   _ptr(dhv, f32, "dhv"), _ptr(g_hist, f32, "g_hist"), _ptr(dense, f32, "dense"), C.c_void_p(ws.data_ptr()),
                   ws.numel(), _stream())
@@ -1648,7 +1627,7 @@ def seg_rows_route(n_occ, n_rows, d):
 
 def segmented_update2(keys, perm, src, src2, n_split, hyper=None, W=None, m=None, v=None, coef=None,
                       src_index=None, div=1, dense_grad=None, step_dev=None):
-    """rc_segmented_update2: occurrences >= n_split take plain rows src2[o - n_split].
+    """rc_segmented_update with a second source: occurrences >= n_split take plain rows src2[o - n_split].
     step_dev: int64 device tensor [1] with Adam's step count (hipGraph-capturable; one-wave-per-row route only)"""
     n_occ = keys.numel()
     d = src.shape[-1]
@@ -1658,21 +1637,18 @@ def segmented_update2(keys, perm, src, src2, n_split, hyper=None, W=None, m=None
     if seg_rows_route(n_occ, n_rows, d):
         # every row collects many occurrences (a small catalogue under a large batch): one wave per table row
         ws = workspace(_lib.load().rc_segmented_rows_workspace_bytes(n_rows, n_occ, d), keys.device, "seg_rows")
-        head = (_ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d,
-                n_rows, _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
-                _ptr(coef, f32, "coef", True), _ptr(src, f32, "src"), _ptr(src_index, torch.int64, "src_index", True),
-                int(div), _ptr(src2, f32, "src2"), int(n_split), C.byref(hyper) if hyper is not None else None)
-        tail = (_ptr(dense_grad, f32, "dense_grad", True), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
-        if step_dev is None:
-            _lib.call("rc_segmented_update_rows", *head, *tail)
-        else:
-            _lib.call("rc_segmented_update_rows_dev", *head, _ptr(step_dev, torch.int64, "step_dev"), *tail)
+        _lib.call("rc_segmented_update_rows", _ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d,
+                  n_rows, _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
+                  _ptr(coef, f32, "coef", True), _ptr(src, f32, "src"), _ptr(src_index, torch.int64, "src_index", True),
+                  int(div), _ptr(src2, f32, "src2"), int(n_split), C.byref(hyper) if hyper is not None else None,
+                  _ptr(step_dev, torch.int64, "step_dev", True), _ptr(dense_grad, f32, "dense_grad", True),
+                  C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
         return
     if step_dev is not None:
         raise RuntimeError("segmented_update2(step_dev=...): the device-side step count is carried by the one-wave-per-row "
                            "update only (seg_rows_route: a small catalogue under a large batch)")
     ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, d), keys.device, "seg")
-    _lib.call("rc_segmented_update2", _ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d,
+    _lib.call("rc_segmented_update", _ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d,
               _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
               _ptr(coef, f32, "coef", True), _ptr(src, f32, "src"), _ptr(src_index, torch.int64, "src_index", True),
               int(div), _ptr(src2, f32, "src2"), int(n_split), 0, 0, C.byref(hyper) if hyper is not None else None,

@@ -5,7 +5,7 @@ between them (autograd Functions, module calls, ctypes) costs several times more
 whole step is therefore recorded ONCE per batch shape with HIP stream capture (torch.cuda.CUDAGraph: the
 engine launches on torch's current stream, takes its scratch from caches that are warm by then, never
 synchronises) and replayed with the next batch copied into static input buffers.  Adam's step count lives
-in device memory (HipOptimizer(capturable=True), rc_dense_update_multi_dev), so bias correction advances
+in device memory (HipOptimizer(capturable=True), rc_dense_update_multi (step_dev)), so bias correction advances
 across replays.  Eligibility is decided by the runner (helpers/BaseRunner.py): host-free forward
 (no host-side candidate shuffle; torch's dropout replays with a fresh Philox offset), HipOptimizer, CUDA tensors.
 

@@ -872,7 +872,7 @@ def mlp_plan(modules):
 
 
 class _MlpFn(torch.autograd.Function):
-    """a whole mlp_plan as ONE autograd node: forward = one rc_linear_fwd per layer; backward = rc_linear_bwd_chain per layer,
+    """a whole mlp_plan as ONE autograd node: forward = one rc_linear_fwd per layer; backward = rc_linear_bwd per layer,
     top down, where the dX product of layer i + 1 applies the ReLU / dropout mask of layer i in its epilogue (the saved output of
     layer i is the input of layer i + 1), so no layer but the top one makes a separate masking pass over [M, width]."""
 
@@ -929,7 +929,7 @@ class _MlpFn(torch.autograd.Function):
                                                            x_drop_p=below[1] if x_act else 0.0, need_db2=spec[n - 2][2], need_db3=spec[n - 1][2])
             grads[2 * (n - 2)], grads[2 * (n - 2) + 1], grads[2 * (n - 1)], grads[2 * (n - 1) + 1] = dW2, db2, dW3, db3
             dz, top = dX, n - 3
-        # (the weight-gradient products on a second stream beside the dX chain -- rc_linear_bwd_chain takes dX / dW separately --
+        # (the weight-gradient products on a second stream beside the dX chain -- rc_linear_bwd takes dX / dW separately --
         #  measured SLOWER inside the replayed graph at B = 1,024: 0.389 against 0.377 ms, profiles/r05h_gemm_probe.txt)
         for i in range(top, -1, -1):
             X, W = saved[2 * i], saved[2 * i + 1]

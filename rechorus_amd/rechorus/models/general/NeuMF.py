@@ -3,8 +3,8 @@ Reference: "Neural Collaborative Filtering", Xiangnan He et al., WWW'2017.
 Mirror of the reference's models/general/NeuMF.py (same class / arg / state_dict names):
     python main.py --model_name NeuMF --emb_size 64 --layers '[64]' --lr 5e-4 --l2 1e-7 --dataset 'Grocery_and_Gourmet_Food'
 With one hidden layer and emb_size and layer size in {32, 64, 128}, the whole head (:61-75: four
-gathers, GMF product, MLP, dropout, prediction layer) is the fp32-MFMA kernel pair rc_neumf_fwd(_dropout)
-/ rc_neumf_bwd(_dropout); the dropout mask comes from a counter-based stream keyed by a device-side seed
+gathers, GMF product, MLP, dropout, prediction layer) is the fp32-MFMA kernel pair rc_neumf_fwd
+/ rc_neumf_bwd; the dropout mask comes from a counter-based stream keyed by a device-side seed
 that is bumped every training forward (so a captured step replays with fresh masks).  Any other
 configuration runs the same parameters through HipEmbedding gathers + torch layers.
 """

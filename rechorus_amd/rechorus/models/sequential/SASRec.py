@@ -7,7 +7,7 @@ The encoder of :58-76 (history + position gather, causal self-attention blocks, 
 rc_sasrec_fwd / rc_sasrec_bwd; the candidate scoring of :80-81 is the BPRMF gather-dot kernel with
 the encoder output as the "user" row.  Training with --dropout p runs the batch-level kernels with the
 two nn.Dropout sites of every TransformerLayer (utils/layers.py:104-117) inside them: the mask comes from a
-counter-based stream keyed by a device-side seed (rc_sasrec_batch_fwd_dropout), never from torch's RNG.
+counter-based stream keyed by a device-side seed (rc_sasrec_batch_fwd), never from torch's RNG.
 Shapes outside those kernels' envelope (emb_size other than 32 / 64, history beyond 64 -- 128 with one block and no dropout --,
 more than four blocks) run the same parameters layer by layer on the shape-generic HIP kernels of csrc/seq_layers.hip and the
 fp32 MFMA GEMMs of csrc/mlp.hip (rechorus_amd.nn.sasrec_encode_layers): any emb_size that is a multiple of 4, any head / block

@@ -4,7 +4,7 @@ Stores params, a batch, prediction, loss, autograd grads of every parameter, and
 after two fit() iterations with Adam / SGD through the reference's own optimizer construction.
 neumfdrop_*: the reference model in TRAINING mode with --dropout p, its nn.Dropout swapped for a module
 that applies a GIVEN keep mask with nn.Dropout's arithmetic (zero, or scale by 1/(1-p)); the mask is the
-counter-based one of rc_neumf_fwd_dropout (oracle/neumf_oracle.dropout_keep), since torch's own random
+counter-based one of rc_neumf_fwd (oracle/neumf_oracle.dropout_keep), since torch's own random
 stream is not something another implementation can reproduce."""
 import os
 import sys

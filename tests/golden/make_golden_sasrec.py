@@ -3,7 +3,7 @@ build container only:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golde
 
 sasrecdrop_*: the reference model in TRAINING mode with --dropout p, the two nn.Dropout modules of every
 TransformerLayer (utils/layers.py:104,114) swapped for modules that apply a GIVEN keep-and-scale mask -- the
-counter-based one of rc_sasrec_batch_fwd_dropout (oracle/sasrec_oracle.dropout_keep), since torch's own random
+counter-based one of rc_sasrec_batch_fwd (oracle/sasrec_oracle.dropout_keep), since torch's own random
 stream cannot be reproduced by another implementation.  Everything else (the order of operations, LayerNorm,
 autograd) is the reference's."""
 import os

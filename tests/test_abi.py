@@ -52,6 +52,32 @@ def test_version_and_error_reporting(lib):
     assert b"C >= 2" in lib.rc_last_error_string()
 
 
+def test_folded_entry_points_reject_meaningless_argument_combinations(lib):
+    """rc_plan_update_pair and rc_bprmf_fwd_bwd_update express what used to be separate entry points as argument combinations; the
+    combinations that mean nothing are RC_ERR_INVALID_ARG with a message, before anything is launched.  (The arguments are chosen so
+    that a missing check could not launch either: an empty occurrence list, a null table.)"""
+    p = C.c_void_p(64)      # non-null and 16-byte aligned; never dereferenced
+    h = C.byref(_lib.OptHyper(opt=_lib.RC_OPT_SGD, lr=0.1))
+    d = 32
+
+    def pair(src_b, src_ld):
+        return lib.rc_plan_update_pair(p, None, None, p, None, None, d, p, p, p, 0, p, src_b, src_ld, 0, h, None, p, 1 << 20, None)
+    # two contiguous sources take no row stride; a block source needs one: a multiple of 4 floats, at least 2 d
+    for src_b, src_ld in ((p, 2 * d), (p, 4), (None, 0), (None, 2 * d - 4), (None, 2 * d + 2), (None, 2 * d + 1), (None, -4)):
+        assert pair(src_b, src_ld) == -1, (src_b, src_ld)
+        assert b"rc_plan_update_pair: src_ld" in lib.rc_last_error_string(), (src_b, src_ld)
+    assert pair(p, 0) == 0 and pair(None, 2 * d) == 0 and pair(None, 2 * d + 4) == 0     # (n_occ = 0: accepted, nothing to do)
+
+    def fused(single, multi):
+        return lib.rc_bprmf_fwd_bwd_update(None, p, None, None, p, p, single, multi, 8, 4, d, 0.125, h, None, p, p, p, None)
+    for single, multi in ((p, p), (None, None)):
+        assert fused(single, multi) == -1
+        assert b"exactly one of single / multi" in lib.rc_last_error_string()
+    for single, multi in ((p, None), (None, p)):      # a valid pair gets as far as the next check (U is null)
+        assert fused(single, multi) == -1
+        assert b"null pointer" in lib.rc_last_error_string()
+
+
 def test_sasrec_shape_envelope(lib):
     """rc_sasrec_supported is host logic: d in {32, 64}, 1..4 blocks, heads | d, history_max <= 64 on every route; 65..128 with ONE
     block and 1 / 2 / 4 heads (the batch encoder's one-row path).  engine.sasrec_supported adds: no training-mode dropout there."""

@@ -97,7 +97,7 @@ def test_linear_is_deterministic_and_matches_torch_modules(cuda, eng):
 @pytest.mark.parametrize("M,widths,p", [(300, (96, 512, 64, 1), 0.0), (1024, (512, 512, 64), 0.3), (66000, (64, 512, 130), 0.0),
                                         (20000, (128, 256, 128, 8), 0.25)])
 def test_mlp_chain_with_fused_masks_equals_layer_by_layer(M, widths, p, cuda, eng, monkeypatch):
-    """the whole-MLP autograd node (rc_linear_bwd_chain: the dX product of layer i + 1 applies layer i's ReLU / dropout mask in its
+    """the whole-MLP autograd node (rc_linear_bwd: the dX product of layer i + 1 applies layer i's ReLU / dropout mask in its
     epilogue) against one autograd node per layer with the separate masking pass (rc_linear_bwd): same products, same mask
     arithmetic -- every gradient bit-identical; small and 128 x 128-tile shapes, split-K shapes, with and without dropout"""
     from rechorus_amd import nn as hnn

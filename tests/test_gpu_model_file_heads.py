@@ -3,7 +3,7 @@ DeepFM context family at the end of this file).  Model files written the way a u
 layers over the plugin's task bases, tests/user_models/ (this repository's own code; the reference's files never leave
 /root/reference, and tests/test_dropin_heads_cpu.py checks dropin.py's table of THEIR syntax trees there) -- are given to the
 plugin's main.py through RECHORUS_MODEL_DIRS.  rechorus_amd/dropin.py recognises the head by structure + a probe batch, and the run
-(i) trains through the fused one-call fit() iteration (rc_bprmf_train_step_ahead / rc_neumf_train_step* / engine.SasrecTrainer),
+(i) trains through the fused one-call fit() iteration (rc_bprmf_train_step_ahead / rc_neumf_train_step / engine.SasrecTrainer),
 (ii) leaves a checkpoint that is BIT-IDENTICAL to the one the plugin's own class of the same name leaves from the same seed, with
 the reference's state_dict keys, and (iii) an edited model file whose forward no longer computes the head keeps its own route.
 A file whose syntax tree is not in dropin's table is bound only with dropout 0 (a probe batch cannot verify a stochastic forward);
@@ -51,13 +51,13 @@ def dataset_root(tmp_path_factory):
 CASES = [
     ("general", "BPRMF", ["--emb_size", "32", "--optimizer", "SGD", "--lr", "40", "--l2", "0"], "BprmfTrainer", r"rc_bprmf_train_step_ahead"),
     ("general", "NeuMF", ["--emb_size", "32", "--layers", "[32]", "--lr", "5e-3", "--l2", "1e-6", "--dropout", "0"], "NeumfTrainer",
-     r"rc_neumf_train_step(_marked)?"),
+     r"rc_neumf_train_step"),
     ("sequential", "SASRec", ["--emb_size", "32", "--num_layers", "1", "--num_heads", "2", "--history_max", "10", "--lr", "3e-3",
                               "--l2", "1e-6", "--dropout", "0"], "SasrecTrainer", r"rc_sasrec\w*"),
     # the reference's own NeuMF command line (docs/demo_scripts_results/Topk_Amazon.sh:8): --dropout 0.2 -> the mask inside the fused
     # kernel (the file's syntax tree is listed first: _list_as_known)
     ("general", "NeuMF", ["--emb_size", "64", "--layers", "[64]", "--lr", "5e-4", "--l2", "1e-7", "--dropout", "0.2"], "NeumfTrainer",
-     r"rc_neumf_train_step_dropout"),
+     r"rc_neumf_train_step"),
 ]
 
 
@@ -71,11 +71,13 @@ def _run(model_args, name, dataset_root, out, monkeypatch, model_dir, known=None
         monkeypatch.setenv("RECHORUS_MODEL_DIRS", model_dir)
     else:
         monkeypatch.delenv("RECHORUS_MODEL_DIRS", raising=False)
-    names, steps = set(), {}
+    names, steps, neumf_drop_p = set(), {}, []
     real_call = _lib.call
 
     def call(fn_name, *a):
         names.add(fn_name)
+        if fn_name == "rc_neumf_train_step":
+            neumf_drop_p.append(a[22].value)      # drop_p: the 23rd argument (include/rechorus_hip.h), a ctypes float
         return real_call(fn_name, *a)
     monkeypatch.setattr(_lib, "call", call)
     for tr in ("BprmfTrainer", "NeumfTrainer", "SasrecTrainer"):
@@ -92,24 +94,27 @@ def _run(model_args, name, dataset_root, out, monkeypatch, model_dir, known=None
                     "--num_workers", "0", "--engine", "rowwise", "--regenerate", "1", "--random_seed", "7", "--log_file", log,
                     "--model_path", str(out / "model" / "m.pt"), "--topk", "5,10", "--save_final_results", "0"])
     monkeypatch.undo()
-    return res, open(log).read(), torch.load(str(out / "model" / "m.pt"), map_location="cpu"), names, steps
+    return res, open(log).read(), torch.load(str(out / "model" / "m.pt"), map_location="cpu"), names, steps, neumf_drop_p
 
 
 @pytest.mark.parametrize("sub,name,model_args,trainer,entry", CASES)
 def test_a_users_model_file_trains_through_the_fused_step(sub, name, model_args, trainer, entry, dataset_root, tmp_path, monkeypatch, cuda):
     (tmp_path / "ref").mkdir(), (tmp_path / "mirror").mkdir()
     stochastic = float(model_args[model_args.index("--dropout") + 1]) > 0 if "--dropout" in model_args else False
-    res_a, text_a, sd_a, names_a, steps_a = _run(model_args, name, dataset_root, tmp_path / "ref", monkeypatch, os.path.join(FIX, sub),
+    res_a, text_a, sd_a, names_a, steps_a, drop_a = _run(model_args, name, dataset_root, tmp_path / "ref", monkeypatch, os.path.join(FIX, sub),
                                                  known=(sub, name) if stochastic else None)
     assert "Recognised the %s head" % name in text_a, text_a[-1500:]
     assert ("(edited forward, verified on a probe batch)" in text_a) == (not stochastic)
     assert "Adopted" in text_a
     assert steps_a.get(trainer, 0) > 3, steps_a
     assert any(re.fullmatch(entry, n) for n in names_a), sorted(names_a)
+    if name == "NeuMF":      # the entry point is the same with and without dropout: every call carries the run's --dropout or none does
+        assert drop_a and all((p > 0) == stochastic for p in drop_a), drop_a
     losses = [float(x) for x in re.findall(r"Epoch \d+\s+loss=([0-9.]+)", text_a)]
     assert len(losses) >= 2 and losses[-1] < losses[0], losses
-    res_b, text_b, sd_b, names_b, steps_b = _run(model_args, name, dataset_root, tmp_path / "mirror", monkeypatch, None)
+    res_b, text_b, sd_b, names_b, steps_b, drop_b = _run(model_args, name, dataset_root, tmp_path / "mirror", monkeypatch, None)
     assert "Recognised the" not in text_b and steps_b.get(trainer, 0) == steps_a[trainer]
+    assert all((p > 0) == stochastic for p in drop_b), drop_b
     # the reference's own state_dict keys, and the plugin's class of the same name ends on the same bits
     assert set(sd_a) == set(sd_b) and not any("drop_seed" in k for k in sd_a)
     for k in sd_a:

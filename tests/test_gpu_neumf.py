@@ -94,7 +94,7 @@ def test_neumf_random_shapes_vs_oracle(cuda, eng):
     assert not eng.neumf_supported(48, 64) and not eng.neumf_supported(128, 128)
 
 
-# ---- hidden-layer dropout inside the kernels (rc_neumf_fwd_dropout / rc_neumf_bwd_dropout) ---------------------
+# ---- hidden-layer dropout inside the kernels (rc_neumf_fwd / rc_neumf_bwd with drop_p > 0) ---------------------
 
 def _seed(cuda, value):
     return torch.tensor([value], dtype=torch.int64, device=cuda)
@@ -280,7 +280,7 @@ def _check_fused_against(eng, P, Pd, state, uid, iid, opt, lr, l2, step, want_pr
     h = eng.make_hyper(opt, lr=lr, l2=l2, step=step)
     if drop is None:
         eng.neumf_train_step(Pd, state, u, i, h, marks, out, pred=pred)
-    else:      # (p, device seed): rc_neumf_train_step_dropout
+    else:      # (p, device seed): rc_neumf_train_step with drop_p > 0
         eng.neumf_train_step(Pd, state, u, i, h, marks, out, pred=pred, drop_p=drop[0], seed=drop[1])
     torch.cuda.synchronize()
     n_items = Pd["mf_i"].shape[0]
@@ -533,7 +533,7 @@ def test_neumf_trainer_short_step_consumes_prepared_flags_and_clears_them(cuda, 
     assert not torch.equal(res[0]["mf_i"][500:510], t(P0["mf_i"])[500:510])
 
 
-# ---- dropout inside the fused step (rc_neumf_train_step_dropout) -------------------------------------------------------------
+# ---- dropout inside the fused step (rc_neumf_train_step, drop_p > 0) -------------------------------------------------------------
 
 @pytest.mark.parametrize("opt", ["SGD", "Adam", "Adagrad"])
 def test_neumf_fused_step_with_dropout_matches_the_reference_run_with_the_same_mask(opt, cuda, eng):

@@ -174,7 +174,7 @@ def test_neumf_model_file_matches_reference(case, cuda):
 
 @pytest.mark.parametrize("case", ["neumfdrop_d64_l64_k4_p0.2", "neumfdrop_d32_l128_k9_p0.5"])
 def test_neumf_model_file_trains_with_dropout_in_the_kernels(case, cuda):
-    """--dropout p: train mode runs rc_neumf_fwd_dropout / rc_neumf_bwd_dropout (no torch layers); with the
+    """--dropout p: train mode runs rc_neumf_fwd / rc_neumf_bwd with drop_p > 0 (no torch layers); with the
     model's mask seed set to the golden's, prediction and autograd gradients equal the reference's run with
     that mask; eval mode is the plain head"""
     from models.general.NeuMF import NeuMF

@@ -1,7 +1,7 @@
 """GPU: the entry points round 6 added, each against the call sequence it replaces, bit for bit --
-rc_gather_rows_pair (two rc_gather_rows + a concatenation), rc_plan_update_pair_zeroed (rc_plan_update_pair without its memset),
-rc_plan_update_pair_block (the same update reading both gradients from one strided block),
-rc_sasrec_batch_bwd_part (the backward pass of rc_sasrec_batch_bwd_dropout in two calls), rc_ctr_head_fwd_full (rc_ctr_head_fwd_bwd_sums
+rc_gather_rows_pair (two rc_gather_rows + a concatenation), rc_plan_update_pair with caller-zeroed counters (the update without its
+memset) and with a block source (the same update reading both gradients from one strided block),
+rc_sasrec_batch_bwd_part (the backward pass of rc_sasrec_batch_bwd in two calls), rc_ctr_head_fwd_full (rc_ctr_head_fwd_bwd_sums
 + rc_ctr_head_bwd for a seed gradient of one, and the counter that rides along).  The fused field gather and the planned row sums
 have their own tests in test_gpu_deepfm.py.
 Reference semantics: models/general/NeuMF.py:39-42,61-66 (the two table families of a side), helpers/BaseRunner.py:193-206 (the
@@ -62,7 +62,7 @@ def test_pair_update_with_prezeroed_counters_equals_the_plain_call(opt, cuda):
 
 @pytest.mark.parametrize("opt", ["SGD", "Adam"])
 def test_pair_update_from_one_block_equals_two_contiguous_sources(opt, cuda):
-    """rc_plan_update_pair_block: the (gradient of table a | gradient of table b) rows of one [n, 2 d] block (also with a wider row
+    """rc_plan_update_pair with src_b = NULL: the (gradient of table a | gradient of table b) rows of one [n, 2 d] block (also with a wider row
     stride) against rc_plan_update_pair on contiguous copies of the halves"""
     from rechorus_amd import engine
     g = torch.Generator(device=cuda).manual_seed(5)

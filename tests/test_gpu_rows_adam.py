@@ -23,7 +23,7 @@ def cuda():
 def test_rows_passes_equal_the_dense_update_bitwise(cuda, l2):
     """three 'tables' ([rows, 64], [rows, 1], [rows, 20] -- float4, scalar and unaligned-width paths) and one plain tensor: the
     pass over every row that reads a gradient only where the row carries the step's stamp -- and its two halves run one after
-    the other -- == rc_dense_update_multi_dev with a zero-filled dense gradient"""
+    the other -- == rc_dense_update_multi (step_dev) with a zero-filled dense gradient"""
     from rechorus_amd import engine
     g = torch.Generator(device=cuda)
     g.manual_seed(3)

@@ -326,7 +326,7 @@ def test_sasrec_register_attention_equals_lds_attention(d, n_layers, n_heads, L,
                                                       (32, 1000, 3000, 6, 5000, None)])
 def test_segmented_update_rows_equals_head_list_route(d, n_rows, n_a, C, n_b, opt, cuda, eng, monkeypatch):
     """rc_segmented_update_rows (one wave per table row, every row collecting many occurrences) against a float64 sum
-    and against rc_segmented_update2's head list: coef * src[o / C] occurrences followed by plain src2 rows, rows that
+    and against rc_segmented_update's head list: coef * src[o / C] occurrences followed by plain src2 rows, rows that
     never occur, a row past the 192-occurrence hand-over to the chunked path, dense-gradient and optimizer outputs"""
     rng = np.random.default_rng(d + n_rows)
     ids_a = rng.integers(0, n_rows, size=(n_a, C)).astype(np.int64)
@@ -491,7 +491,7 @@ def test_sasrec_trainer_graph_replay_equals_eager_one_or_two_streams(opt, overla
     """SasrecTrainer(graph=True) replays the step from a hipGraph (both streams captured, the batch copied into static
     buffers): seven steps over different batches -- two eager, the capture, four replays -- leave the loss sequence and every
     parameter bit-identical to the eager trainer.  Adam: the replayed trainer keeps the step count in device memory and forms the
-    bias corrections in the kernels (rc_segmented_update_rows_dev, rc_dense_update_multi_dev) -- the same double-precision
+    bias corrections in the kernels (rc_segmented_update_rows, rc_dense_update_multi with step_dev) -- the same double-precision
     expressions as the host's, compared to rounding."""
     from rechorus_amd import graph as hgraph
     if not hgraph.usable():
@@ -730,7 +730,7 @@ def test_sasrec_pos_grad_chunks(cuda, eng):
 
 @pytest.mark.parametrize("case", DROP_CASES)
 def test_sasrec_training_mode_dropout_matches_reference(case, cuda, eng):
-    """rc_sasrec_batch_fwd_dropout / _bwd_dropout vs the reference in training mode with its nn.Dropout modules
+    """rc_sasrec_batch_fwd / _bwd with drop_p > 0 vs the reference in training mode with its nn.Dropout modules
     swapped for the same counter-based mask (tests/golden/sasrecdrop_*.npz)"""
     g = load_golden(case)
     n_layers, n_heads = int(g["meta"][2]), int(g["meta"][3])

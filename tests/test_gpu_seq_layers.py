@@ -78,7 +78,7 @@ def test_sasrec_model_matches_reference_inside_and_outside_the_envelope(case, cu
         n_layers = model.num_layers
         assert names.count("rc_seq_attention_fwd") == n_layers and names.count("rc_seq_attention_bwd") == n_layers, names
         assert names.count("rc_seq_add_layernorm_fwd") == 2 * n_layers and names.count("rc_seq_embed_fwd") == 1
-        assert names.count("rc_linear_fwd_ws") == 5 * n_layers
+        assert names.count("rc_linear_fwd") == 5 * n_layers
         assert not any(n.startswith("rc_sasrec_batch") or n in ("rc_sasrec_fwd", "rc_sasrec_bwd") for n in names)
     else:
         assert not any(n.startswith("rc_seq_") for n in names)

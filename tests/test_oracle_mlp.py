@@ -39,7 +39,7 @@ def test_oracle_layer_matches_torch_autograd(M, N, K, relu, p):
 
 @pytest.mark.parametrize("p", [0.0, 0.3])
 def test_chain_backward_with_the_mask_in_the_dx_product_equals_layer_by_layer(p):
-    """the algebra behind rc_linear_bwd_chain (one autograd node per MLP): masking dX of layer i + 1 with layer i's saved
+    """the algebra behind rc_linear_bwd (one autograd node per MLP): masking dX of layer i + 1 with layer i's saved
     output (X > 0, scale 1 / (1 - p)) and handing it down as that layer's dZ gives the gradients of the layer-by-layer backward,
     where every layer masks its own dY -- the saved output of drop(relu(.)) is its own mask (dropped or clipped elements are 0)"""
     rng = np.random.default_rng(7)

@@ -36,7 +36,7 @@ DROP_CASES = sorted(f[:-4] for f in os.listdir(GOLDEN_DIR) if f.startswith("sasr
 @pytest.mark.parametrize("case", DROP_CASES)
 def test_sasrec_training_mode_dropout(case):
     """the reference in training mode with its nn.Dropout modules applying the counter-based mask: the oracle
-    regenerates the mask from the seed (same scheme as rc_sasrec_batch_fwd_dropout)"""
+    regenerates the mask from the seed (same scheme as rc_sasrec_batch_fwd)"""
     g = load_golden(case)
     P = params(g)
     n_layers, n_heads = int(g["meta"][2]), int(g["meta"][3])
