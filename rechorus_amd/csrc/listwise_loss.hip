@@ -72,6 +72,16 @@ __global__ __launch_bounds__(kBlock) void listwise_softmax_ce_kernel(
   }
 }
 
+// A row without a valid negative: b is a softmax over nothing.  The reference returns NaN for the whole batch there (its softmax of
+// all -inf), and the host stops on np.isnan(loss): the four re-weighting kernels write a NaN loss and a NaN gradient row instead of
+// -log 0 = +inf (BPR / BPRhard) or whatever 0 / 0 happens to give.  Wave-uniform; rows that have a negative take the old path unchanged.
+__device__ __forceinline__ void list_row_nan(int lane, int64_t row, int n, float* __restrict__ loss_vec, float* __restrict__ gpred) {
+  const float nan = __builtin_nanf("");
+  if (lane == 0) loss_vec[row] = nan;
+  if (gpred)
+    for (int c = lane; c < n; c += 64) gpred[row * n + c] = nan;
+}
+
 // ---- list-level BPR (ImpressionModel.loss, loss_n 'BPR' / 'BPRhard': models/BaseImpressionModel.py:50-89) ----
 //   valid positives i (columns < P, target != -1), valid negatives j (columns >= P, target != -1)
 //   a = softmax over the positives of s (of -s for 'hard'),  b = softmax over the negatives of s
@@ -105,6 +115,7 @@ __global__ __launch_bounds__(kBlock) void list_bpr_kernel(const float* __restric
   }
   sa = wave_allreduce_sum(sa);
   sb = wave_allreduce_sum(sb);
+  if (mb == -INFINITY) return list_row_nan(lane, row, n, loss_vec, gpred);  // no valid negative
   // Q = sum_i a_i Q_i
   float q_part = 0.f;
   for (int i = lane; i < P && i < n; i += 64) {
@@ -191,6 +202,7 @@ __global__ __launch_bounds__(kBlock) void list_bpr_reweight_kernel(const float* 
   sa = wave_allreduce_sum(sa);
   sb = wave_allreduce_sum(sb);
   n_pos = wave_allreduce_sum(n_pos);
+  if (mb == -INFINITY) return list_row_nan(lane, row, n, loss_vec, gpred);  // no valid negative
   if (BEFORE) {
     float m = 0.f;
     for (int j = P + lane; j < n; j += 64)

@@ -11,6 +11,7 @@ import torch
 
 from conftest import GOLDEN_DIR, ROOT, assert_close
 from oracle import impression_oracle as IO
+from oracle import listloss_oracle as LLO
 from oracle import listwise_oracle as LO
 from synth_data import make_impression_dataset
 
@@ -38,6 +39,87 @@ def test_oracle_list_losses_match_the_reference(key):
         loss, _, g = IO.list_bpr(c["pred"], c["target"], int(c["max_pos"]), hard=(name == "BPRhard"))
     assert_close(loss, c["loss"], what="loss " + key)
     assert_close(g, c["gpred"], what="grad " + key, atol_scale=2e-5)
+
+
+# ---- the float64 autograd oracle of all ten names (oracle/listloss_oracle.py) vs the reference ---------------------------------
+# tests/golden/listloss_f64.npz (make_golden_listloss.py): the reference run in float64 and in fp32 on the same inputs
+
+LL = dict(np.load(os.path.join(GOLDEN_DIR, "listloss_f64.npz")))
+LL_SETS = ("a0", "a1", "a2", "c0", "c1", "c2", "gap", "gap1")
+LL_CASES = sorted("/".join(k.split("/")[:2]) for k in LL if k.split("/")[0] in LL_SETS and k.endswith("/loss64"))
+
+
+def ll_case(key):
+    """'<set>/<name>' -> dict(pred fp32, target int64, max_pos, loss64, g64, loss32, g32)"""
+    s, name = key.split("/")
+    c = {k[len(key) + 1:]: v for k, v in LL.items() if k.startswith(key + "/")}
+    c["pred"], c["max_pos"] = LL[s + "/pred"], int(LL[s + "/max_pos"])
+    c["target"] = LL[s + "/target/" + ("h" if name in LLO.H_NORMALISED else "bpr")].astype(np.int64)
+    return c
+
+
+def test_listloss_fixture_holds_every_name_at_every_shape():
+    assert os.path.getsize(os.path.join(GOLDEN_DIR, "listloss_f64.npz")) < 1 << 20
+    for s in ("a0", "a1", "a2", "c0", "c1", "c2"):
+        assert {k.split("/")[1] for k in LL_CASES if k.startswith(s + "/")} == set(LLO.NAMES), s
+    assert {k.split("/")[1] for k in LL_CASES if k.startswith("gap/")} == set(LLO.NAMES) - {"attention_rank"}
+    c = ll_case("a0/BPRhardbefore")
+    t = c["target"]
+    assert c["max_pos"] == 100 and ((t[:, :100] != -1).sum(1) > 64).any() and ((t[:, 100:] != -1).sum(1) > 64).any()
+    p, t = LL["gap/pred"].astype(np.float64), LL["gap/target/bpr"]
+    gaps = np.where((t[:, :6, None] == 1) & (t[:, None, 6:] == 0), p[:, :6, None] - p[:, None, 6:], 0.0)
+    assert gaps.max() > 90 and gaps.min() < -90
+
+
+@pytest.mark.parametrize("key", LL_CASES)
+def test_autograd_oracle_matches_the_reference_in_float64(key):
+    """forward-only float64 oracle + autograd vs the reference's own float64 run, scaled by the tensor's largest entry: 1e-12; 1e-6
+    for listnet / attention_rank, whose reference builds the label softmax from target.float() -- one fp32 rounding in its 'float64'"""
+    c = ll_case(key)
+    name = key.split("/")[1]
+    bound = 1e-6 if name in ("listnet", "attention_rank") else 1e-12
+    loss, g = LLO.list_loss(name, c["pred"], c["target"], c["max_pos"])
+    assert np.isfinite(c["loss64"]).all() and np.isfinite(c["g64"]).all()
+    el = np.abs(loss - c["loss64"]).max() / np.abs(c["loss64"]).max()
+    eg = np.abs(g - c["g64"]).max() / np.abs(c["g64"]).max()
+    print("%s: loss %.2e grad %.2e (bound %.0e)" % (key, el, eg, bound))
+    assert el <= bound and eg <= bound, (key, el, eg)
+
+
+@pytest.mark.parametrize("key", LOSS_CASES)
+def test_autograd_oracle_matches_the_fp32_goldens(key):
+    c = case(key)
+    loss, g = LLO.list_loss(key.split("/")[-1], c["pred"], c["target"], int(c["max_pos"]))
+    assert_close(loss, c["loss"], what="loss " + key)
+    assert_close(g, c["gpred"], what="grad " + key, atol_scale=2e-5)
+
+
+@pytest.mark.parametrize("name", ["BPRsimple", "BPRhardsimple"])
+def test_autograd_oracle_matches_the_bpr_simple_golden(name):
+    g = np.load(os.path.join(GOLDEN_DIR, "impression_bpr_simple.npz"))
+    for shape_id in range(3):
+        key = "loss/{}/{}/".format(shape_id, name)
+        rows, grad = LLO.list_loss(name, g[key + "pred"], g[key + "target"], int(g[key + "max_pos"]))
+        assert_close(rows, g[key + "rows"], what=name + " rows")
+        assert_close(grad, g[key + "gpred"], what=name + " grad", atol_scale=2e-5)
+
+
+def test_autograd_oracle_non_finite_cases_follow_the_reference():
+    """a row without negatives: NaN loss under the six re-weighting kinds, 0 and a zero gradient row under 'simple'; no row with a
+    negative: NaN under the three H-normalised kinds -- the reference's fp32 run (nf/ fixtures) and the oracle alike"""
+    for name in LLO.NAMES:
+        s = "all" if name in LLO.H_NORMALISED else "row"
+        k = "nf/{}/{}/".format(s, name)
+        pred, target, mp = LL["nf/%s/pred" % s], LL["nf/%s/target" % s].astype(np.int64), int(LL["nf/%s/max_pos" % s])
+        loss, g = LLO.list_loss(name, pred, target, mp)
+        assert np.array_equal(np.isnan(loss), LL[k + "loss_isnan"]) and not LL[k + "loss_isinf"].any(), name
+        if name == "BPRsimple":
+            assert not LL[k + "loss_isnan"].any() and LL[k + "loss_finite"][2] == 0 and loss[2] == 0 and not g[2].any()
+            assert not LL[k + "g_isnan"].any() and not LL[k + "g_finite"][2].any()
+            assert_close(loss, LL[k + "loss_finite"], what="simple rows")
+            assert_close(g, LL[k + "g_finite"], what="simple grad", atol_scale=2e-5)
+        else:
+            assert LL[k + "loss_isnan"].all(), name
 
 
 # every --loss_n the reference's substring rules resolve (models/BaseImpressionModel.py:50-126) is a HIP kernel
