@@ -152,6 +152,7 @@ struct FusedCall {
   float* gpred;
   float* ugrad;
   int mode;  // MODE_NONE or the optimizer mode of the singleton update
+  const char* who;  // the entry point, for refusals
   FusedUpd upd;
   hipStream_t s;
   const SmallPlanArgs* small;  // non-null: launch small_front_kernel (plan workgroups + this kernel's body)
@@ -177,19 +178,12 @@ static int launch_fused(const FusedCall& f) {
     RC_LAUNCH_CHECK();
     return RC_OK;
   }
-#define RC_GO(MODE_)                                                                          \
-  hipLaunchKernelGGL((bprmf_fwd_bwd_kernel<D, GS, CPL, MODE_>), dim3(blocks), dim3(kBlock), 0, \
-                     f.s, f.U, f.I, f.uid, f.iid, f.B, f.C, f.inv_b, f.pred, f.loss_vec,       \
-                     f.gpred, f.ugrad, f.upd)
-  switch (f.mode) {
-    case MODE_SGD: RC_GO(MODE_SGD); break;
-    case MODE_ADAM: RC_GO(MODE_ADAM); break;
-    case MODE_ADAGRAD: RC_GO(MODE_ADAGRAD); break;
-    default: RC_GO(MODE_NONE); break;
-  }
-#undef RC_GO
-  RC_LAUNCH_CHECK();
-  return RC_OK;
+  return dispatch_or_fail<MODE_NONE, MODE_SGD, MODE_ADAM, MODE_ADAGRAD>(f.who, "update mode", f.mode, [&](auto M) -> int {
+    hipLaunchKernelGGL((bprmf_fwd_bwd_kernel<D, GS, CPL, M()>), dim3(blocks), dim3(kBlock), 0, f.s, f.U, f.I, f.uid, f.iid, f.B, f.C,
+                       f.inv_b, f.pred, f.loss_vec, f.gpred, f.ugrad, f.upd);
+    RC_LAUNCH_CHECK();
+    return RC_OK;
+  });
 }
 
 // pick (GS, CPL) for C candidates when a wave offers G = 64/LPR lane-groups
@@ -226,22 +220,17 @@ static bool register_path_ok(int d, int C) {
   return (C + G - 1) / G <= 32;
 }
 
+// *handled = false: no register-resident kernel for this (d, C); the caller refuses or takes its generic kernel
 static int run_fused(const FusedCall& f, int d, bool* handled) {
   *handled = false;
-  switch (d) {
-    case 16: return dispatch_fused<16>(f, handled);
-    case 32: return dispatch_fused<32>(f, handled);
-    case 64: return dispatch_fused<64>(f, handled);
-    case 128: return dispatch_fused<128>(f, handled);
-    default: return RC_OK;
-  }
+  int rc = RC_OK;
+  dispatch_int<16, 32, 64, 128>(d, &rc, [&](auto D) { return dispatch_fused<D()>(f, handled); });
+  return rc;
 }
 
 }  // namespace rc
 
 using namespace rc;
-
-static bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 extern "C" int rc_bprmf_fused_supported(int d, int C) { return register_path_ok(d, C) ? 1 : 0; }
 
@@ -254,12 +243,12 @@ extern "C" int rc_bprmf_fwd_bwd(const float* U, const float* I, const int64_t* u
   RC_REQUIRE(B > 0 && C >= 2 && d >= 1,
              "rc_bprmf_fwd_bwd: need C >= 2 (one negative), got B=%d C=%d d=%d", B, C, d);
   hipStream_t s = as_stream(stream);
-  if (aligned16(U) && aligned16(I) && aligned16(ugrad) && register_path_ok(d, C)) {
+  if (aligned16(U, I, ugrad) && register_path_ok(d, C)) {
     FusedCall f;
     memset(&f, 0, sizeof(f));
     f.U = U; f.I = I; f.uid = uid; f.iid = iid; f.B = B; f.C = C; f.inv_b = inv_b;
     f.pred = pred; f.loss_vec = loss_vec; f.gpred = gpred; f.ugrad = ugrad;
-    f.mode = MODE_NONE; f.s = s;
+    f.mode = MODE_NONE; f.s = s; f.who = "rc_bprmf_fwd_bwd";
     bool handled = false;
     const int rc_ = run_fused(f, d, &handled);
     if (handled) return rc_;
@@ -291,16 +280,14 @@ extern "C" int rc_bprmf_fwd_bwd_update(const float* U, float* I, float* mI, floa
                 "(check rc_bprmf_fused_supported; use rc_bprmf_fwd_bwd + rc_segmented_update)", who, d, C);
   FusedCall f;
   memset(&f, 0, sizeof(f));
-  RC_TRY(fill_opt_scalars(h, &f.upd.o));
+  RC_TRY(fill_opt_scalars(who, h, &f.upd.o));
   f.mode = mode_of(h);
-  RC_REQUIRE(f.mode != MODE_ADAM || (mI && vI), "%s: Adam needs mI and vI", who);
-  RC_REQUIRE(f.mode != MODE_ADAGRAD || mI, "%s: Adagrad needs mI", who);
-  RC_REQUIRE(aligned16(U) && aligned16(I) && aligned16(ugrad) && aligned16(mI) && aligned16(vI),
-             "%s: tables must be 16-byte aligned", who);
+  RC_TRY(opt_state_check(who, f.mode, mI != nullptr, vI != nullptr));
+  RC_REQUIRE(aligned16(U, I, ugrad, mI, vI), "%s: tables must be 16-byte aligned", who);
   f.U = U; f.I = I; f.uid = uid; f.iid = iid; f.B = B; f.C = C; f.inv_b = inv_b;
   f.pred = pred; f.loss_vec = loss_vec; f.gpred = gpred; f.ugrad = ugrad;
   f.upd.I = I; f.upd.M = mI; f.upd.V = vI; f.upd.single = single; f.upd.multi = multi;
-  f.s = as_stream(stream);
+  f.s = as_stream(stream); f.who = who;
   bool handled = false;
   const int rc_ = run_fused(f, d, &handled);
   if (!handled) return fail(RC_ERR_UNSUPPORTED, "%s: dispatch failed", who);
@@ -312,13 +299,13 @@ namespace rc {
 int small_front_launch(const float* U, const float* I, const int64_t* uid, const int64_t* iid, int B, int C, int d, float inv_b,
                        float* pred, float* loss_vec, float* gpred, float* ugrad, float* ub, const SmallPlanArgs& plan,
                        hipStream_t s) {
-  RC_REQUIRE(aligned16(U) && aligned16(I) && aligned16(ugrad) && aligned16(ub) && register_path_ok(d, C),
+  RC_REQUIRE(aligned16(U, I, ugrad, ub) && register_path_ok(d, C),
              "small-batch step: unsupported shape or alignment (d=%d C=%d)", d, C);
   FusedCall f;
   memset(&f, 0, sizeof(f));
   f.U = U; f.I = I; f.uid = uid; f.iid = iid; f.B = B; f.C = C; f.inv_b = inv_b;
   f.pred = pred; f.loss_vec = loss_vec; f.gpred = gpred; f.ugrad = ugrad;
-  f.mode = MODE_NONE; f.s = s; f.small = &plan; f.ub = ub;
+  f.mode = MODE_NONE; f.s = s; f.small = &plan; f.ub = ub; f.who = "rc_bprmf_train_step";
   bool handled = false;
   const int rc_ = run_fused(f, d, &handled);
   if (!handled) return fail(RC_ERR_UNSUPPORTED, "small-batch step: dispatch failed (d=%d C=%d)", d, C);

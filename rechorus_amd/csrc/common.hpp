@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cmath>
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,28 @@ inline int fail(int code, const char* fmt, ...) {
 inline hipStream_t as_stream(rc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// every pointer is 16-byte aligned (float4 access); a null (absent) buffer passes
+template <class... P>
+inline bool aligned16(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) % 16 == 0) && ...);
+}
+
+// ---- run-time value -> template argument ---------------------------------------------------------
+// dispatch_int<16, 32, 64>(d, &rc, f): *rc = f(std::integral_constant<int, V>{}) for the V of the list that equals v.
+// false = v is not in the list: nothing was called, *rc is untouched.  A site lists exactly the values it has kernels for.
+template <int... Vs, class F>
+inline bool dispatch_int(int v, int* rc, F&& f) {
+  return ((v == Vs ? (*rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// the same with the usual refusal: "<who>: <what> <v> has no kernel"
+template <int... Vs, class F>
+inline int dispatch_or_fail(const char* who, const char* what, int v, F&& f) {
+  int rc = RC_OK;
+  if (dispatch_int<Vs...>(v, &rc, f)) return rc;
+  return fail(RC_ERR_UNSUPPORTED, "%s: %s %d has no kernel", who, what, v);
+}
 
 // carve a sub-buffer out of a caller workspace (256-byte aligned slices)
 struct Carver {

@@ -245,22 +245,21 @@ extern "C" int rc_dense_update(float* W, const float* G, float* m, float* v, int
   RC_REQUIRE(W && G, "rc_dense_update: null pointer");
   RC_REQUIRE(n > 0, "rc_dense_update: n < 0");
   OptScalars o;
-  RC_TRY(fill_opt_scalars(h, &o, /*dense=*/true));
+  RC_TRY(fill_opt_scalars("rc_dense_update", h, &o, /*dense=*/true));
   hipStream_t s = as_stream(stream);
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  bool aligned = al(W) && al(G);
+  bool aligned = aligned16(W, G);
   switch (h->opt) {
     case RC_OPT_SGD:
       return launch_dense<MODE_SGD>(o, W, G, m, v, n, aligned, s);
     case RC_OPT_ADAM:
       RC_REQUIRE(m && v, "rc_dense_update: Adam needs m and v");
-      return launch_dense<MODE_ADAM>(o, W, G, m, v, n, aligned && al(m) && al(v), s);
+      return launch_dense<MODE_ADAM>(o, W, G, m, v, n, aligned && aligned16(m, v), s);
     case RC_OPT_ADAGRAD:
       RC_REQUIRE(m, "rc_dense_update: Adagrad needs m (state_sum)");
-      return launch_dense<MODE_ADAGRAD>(o, W, G, m, v, n, aligned && al(m), s);
+      return launch_dense<MODE_ADAGRAD>(o, W, G, m, v, n, aligned && aligned16(m), s);
     case RC_OPT_ADADELTA:
       RC_REQUIRE(m && v, "rc_dense_update: Adadelta needs m (square_avg) and v (acc_delta)");
-      return launch_dense<MODE_ADADELTA>(o, W, G, m, v, n, aligned && al(m) && al(v), s);
+      return launch_dense<MODE_ADADELTA>(o, W, G, m, v, n, aligned && aligned16(m, v), s);
     default:
       return fail(RC_ERR_INVALID_ARG, "rc_dense_update: unknown optimizer %d", h->opt);
   }
@@ -292,7 +291,6 @@ extern "C" int rc_dense_update_multi(float* const* W, const float* const* G, flo
   if (n_tensors == 0) return RC_OK;
   RC_REQUIRE(W && G && n && h && n_tensors > 0, "rc_dense_update_multi: bad arguments");
   hipStream_t s = as_stream(stream);
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
   const int opt = h[0].opt;
   for (int t0 = 0; t0 < n_tensors;) {
     MultiArgs a;
@@ -309,11 +307,11 @@ extern "C" int rc_dense_update_multi(float* const* W, const float* const* G, flo
       RC_REQUIRE((opt != RC_OPT_ADAM && opt != RC_OPT_ADADELTA) || (mt && vt), "rc_dense_update_multi: Adam / Adadelta need m and v (tensor %d)", t);
       RC_REQUIRE(opt != RC_OPT_ADAGRAD || mt, "rc_dense_update_multi: Adagrad needs m (tensor %d)", t);
       a.W[T] = W[t]; a.G[T] = G[t]; a.M[T] = mt; a.V[T] = vt; a.n[T] = n[t];
-      RC_TRY(fill_opt_scalars(&h[t], &a.o[T], /*dense=*/true));
+      RC_TRY(fill_opt_scalars("rc_dense_update_multi", &h[t], &a.o[T], /*dense=*/true));
       a.lr[T] = (float)h[t].lr;
       RC_REQUIRE(step_dev == nullptr || (h[t].beta1 == h[0].beta1 && h[t].beta2 == h[0].beta2),
                  "rc_dense_update_multi: one (beta1, beta2) per call with step_dev");
-      a.aligned[T] = al(W[t]) && al(G[t]) && al(mt) && al(vt);
+      a.aligned[T] = aligned16(W[t], G[t], mt, vt);
       a.blk0[T] = blocks;
       const int64_t nb = (n[t] + kMultiChunk - 1) / kMultiChunk;
       RC_REQUIRE(nb < ((int64_t)1 << 30) - blocks, "rc_dense_update_multi: grid too large");
@@ -356,7 +354,6 @@ extern "C" int rc_dense_update_rows_dev(float* const* W, const float* const* G, 
   RC_REQUIRE(step_dev != nullptr, "rc_dense_update_rows_dev: the step count lives in device memory (step_dev)");
   RC_REQUIRE(touched >= 0 && touched <= 2, "rc_dense_update_rows_dev: touched is 0, 1 or 2");
   hipStream_t s = as_stream(stream);
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
   for (int t0 = 0; t0 < n_tensors;) {
     RowsArgs a;
     memset(&a, 0, sizeof(a));
@@ -375,9 +372,9 @@ extern "C" int rc_dense_update_rows_dev(float* const* W, const float* const* G, 
       a.W[T] = W[t]; a.G[T] = needs_g ? G[t] : nullptr; a.M[T] = m[t]; a.V[T] = v[t]; a.n[T] = n[t];
       a.flags[T] = flags[t];
       a.row_w[T] = flags[t] ? row_w[t] : 4;
-      RC_TRY(fill_opt_scalars(&h[t], &a.o[T], /*dense=*/true));
+      RC_TRY(fill_opt_scalars("rc_dense_update_rows_dev", &h[t], &a.o[T], /*dense=*/true));
       a.lr[T] = (float)h[t].lr;
-      a.aligned[T] = al(W[t]) && (!needs_g || al(G[t])) && al(m[t]) && al(v[t]) && a.row_w[T] % 4 == 0;
+      a.aligned[T] = aligned16(W[t]) && (!needs_g || aligned16(G[t])) && aligned16(m[t], v[t]) && a.row_w[T] % 4 == 0;
       a.blk0[T] = blocks;
       const int64_t nb = (n[t] + kMultiChunk - 1) / kMultiChunk;
       RC_REQUIRE(nb < ((int64_t)1 << 30) - blocks, "rc_dense_update_rows_dev: grid too large");

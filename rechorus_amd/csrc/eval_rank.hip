@@ -349,15 +349,14 @@ extern "C" int rc_full_catalogue_rank(const float* Uvec, const float* I, const i
              "rc_full_catalogue_rank: clicked_ptr, clicked_items and users go together");
   RC_REQUIRE(N > 0 && n_items >= 2 && n_items < ((int64_t)1 << 31), "rc_full_catalogue_rank: bad shape N=%lld n_items=%lld",
              (long long)N, (long long)n_items);
-  RC_REQUIRE(reinterpret_cast<uintptr_t>(Uvec) % 16 == 0 && reinterpret_cast<uintptr_t>(I) % 16 == 0,
-             "rc_full_catalogue_rank: tables must be 16-byte aligned");
+  RC_REQUIRE(aligned16(Uvec, I), "rc_full_catalogue_rank: tables must be 16-byte aligned");
   hipStream_t s = as_stream(stream);
-  switch (d) {
-    case 32: return launch_full_rank<32>(Uvec, I, users, targets, N, n_items, clicked_ptr, clicked_items, target_score, rank, s);
-    case 64: return launch_full_rank<64>(Uvec, I, users, targets, N, n_items, clicked_ptr, clicked_items, target_score, rank, s);
-    case 128: return launch_full_rank<128>(Uvec, I, users, targets, N, n_items, clicked_ptr, clicked_items, target_score, rank, s);
-    default: return fail(RC_ERR_UNSUPPORTED, "rc_full_catalogue_rank: emb_size must be 32, 64 or 128, got %d", d);
-  }
+  int rc = RC_OK;
+  if (dispatch_int<32, 64, 128>(d, &rc, [&](auto D) {
+        return launch_full_rank<D()>(Uvec, I, users, targets, N, n_items, clicked_ptr, clicked_items, target_score, rank, s);
+      }))
+    return rc;
+  return fail(RC_ERR_UNSUPPORTED, "rc_full_catalogue_rank: emb_size must be 32, 64 or 128, got %d", d);
 }
 
 extern "C" int rc_list_metrics_supported(int n, int max_pos, int n_k) {

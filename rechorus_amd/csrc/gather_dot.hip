@@ -169,8 +169,7 @@ extern "C" int rc_gather_rows(const float* W, int d, const int64_t* ids, int64_t
   RC_REQUIRE(W && ids && out, "rc_gather_rows: null pointer");
   RC_REQUIRE(d >= 1 && n > 0, "rc_gather_rows: bad shape d=%d n=%lld", d, (long long)n);
   hipStream_t s = as_stream(stream);
-  const bool vec = (d % 4 == 0) && (reinterpret_cast<uintptr_t>(W) % 16 == 0) &&
-                   (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+  const bool vec = (d % 4 == 0) && aligned16(W, out);
   const int64_t total = vec ? n * (d / 4) : n * (int64_t)d;
   int64_t blocks = (total + kBlock - 1) / kBlock;
   if (blocks > 256 * 32) blocks = 256 * 32;  // grid-stride above 32 blocks/CU
@@ -190,7 +189,7 @@ extern "C" int rc_gather_rows_pair(const float* Wa, const float* Wb, int d, cons
   if (n == 0) return RC_OK;
   RC_REQUIRE(Wa && Wb && ids && out, "rc_gather_rows_pair: null pointer");
   RC_REQUIRE(d >= 4 && d % 4 == 0 && n > 0, "rc_gather_rows_pair: bad shape d=%d (a multiple of 4) n=%lld", d, (long long)n);
-  RC_REQUIRE(reinterpret_cast<uintptr_t>(Wa) % 16 == 0 && reinterpret_cast<uintptr_t>(Wb) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+  RC_REQUIRE(aligned16(Wa, Wb, out),
              "rc_gather_rows_pair: tables and output must be 16-byte aligned");
   const int64_t total = n * (d / 2);
   int64_t blocks = (total + kBlock - 1) / kBlock;
@@ -209,18 +208,10 @@ extern "C" int rc_gather_dot_fwd(const float* U, const float* I, const int64_t* 
   RC_REQUIRE(B > 0 && C >= 1 && d >= 1, "rc_gather_dot_fwd: bad shape B=%d C=%d d=%d", B, C, d);
   hipStream_t s = as_stream(stream);
   const int64_t n_pairs = (int64_t)B * C;
-  const bool aligned = (reinterpret_cast<uintptr_t>(U) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(I) % 16 == 0);
-  if (aligned) {
-    switch (d) {
-      case 16: return launch_gather_dot<16>(U, I, uid, iid, n_pairs, C, pred, s);
-      case 32: return launch_gather_dot<32>(U, I, uid, iid, n_pairs, C, pred, s);
-      case 64: return launch_gather_dot<64>(U, I, uid, iid, n_pairs, C, pred, s);
-      case 128: return launch_gather_dot<128>(U, I, uid, iid, n_pairs, C, pred, s);
-      case 256: return launch_gather_dot<256>(U, I, uid, iid, n_pairs, C, pred, s);
-      default: break;
-    }
-  }
+  int rc = RC_OK;   // a width without a vector kernel, or unaligned tables: the generic kernel below
+  if (aligned16(U, I) &&
+      dispatch_int<16, 32, 64, 128, 256>(d, &rc, [&](auto D) { return launch_gather_dot<D()>(U, I, uid, iid, n_pairs, C, pred, s); }))
+    return rc;
   int64_t blocks = (n_pairs + 3) / 4;
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipLaunchKernelGGL(gather_dot_fwd_generic_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s,
@@ -235,25 +226,14 @@ extern "C" int rc_weighted_row_sum(const float* W, const int64_t* ids, const flo
   RC_REQUIRE(W && ids && coef && out, "rc_weighted_row_sum: null pointer");
   RC_REQUIRE(B > 0 && C >= 1 && d >= 1, "rc_weighted_row_sum: bad shape B=%d C=%d d=%d", B, C, d);
   hipStream_t s = as_stream(stream);
-  const bool aligned = (reinterpret_cast<uintptr_t>(W) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(out) % 16 == 0);
   const int blocks = (B + (kBlock / 64) - 1) / (kBlock / 64);
-#define RC_WRS(D_)                                                                           \
-  hipLaunchKernelGGL((weighted_row_sum_kernel<D_>), dim3(blocks), dim3(kBlock), 0, s, W, ids, \
-                     coef, B, C, out);                                                       \
-  RC_LAUNCH_CHECK();                                                                         \
-  return RC_OK
-  if (aligned) {
-    switch (d) {
-      case 16: RC_WRS(16);
-      case 32: RC_WRS(32);
-      case 64: RC_WRS(64);
-      case 128: RC_WRS(128);
-      case 256: RC_WRS(256);
-      default: break;
-    }
-  }
-#undef RC_WRS
+  int rc = RC_OK;   // a width without a vector kernel, or unaligned buffers: the generic kernel below
+  if (aligned16(W, out) && dispatch_int<16, 32, 64, 128, 256>(d, &rc, [&](auto D) -> int {
+        hipLaunchKernelGGL((weighted_row_sum_kernel<D()>), dim3(blocks), dim3(kBlock), 0, s, W, ids, coef, B, C, out);
+        RC_LAUNCH_CHECK();
+        return RC_OK;
+      }))
+    return rc;
   int64_t gblocks = ((int64_t)B * d + kBlock - 1) / kBlock;
   if (gblocks > 256 * 32) gblocks = 256 * 32;
   hipLaunchKernelGGL(weighted_row_sum_generic_kernel, dim3((unsigned)gblocks), dim3(kBlock), 0, s, W,

@@ -780,7 +780,7 @@ extern "C" int rc_neumf_train_step(float* mf_u, float* mf_i, float* mlp_u, float
     return fail(RC_ERR_WORKSPACE, "rc_neumf_train_step: workspace %zu < %zu", ws_bytes, rc_neumf_train_step_workspace_bytes(B, C, d, l1));
   NeumfStepArgs a;
   memset(&a, 0, sizeof(a));
-  RC_TRY(fill_opt_scalars(h, &a.opt));
+  RC_TRY(fill_opt_scalars("rc_neumf_train_step", h, &a.opt));
   if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(RC_ERR_INVALID_ARG, "rc_neumf_train_step: dropout p=%g outside [0, 1)", (double)drop_p);
   if (drop_p > 0.f) {
     if (!seed_dev) return fail(RC_ERR_INVALID_ARG, "rc_neumf_train_step: dropout p=%g needs a device seed", (double)drop_p);

@@ -25,11 +25,12 @@ struct OptScalars {
   float eps;
 };
 
-inline int fill_opt_scalars(const rc_opt_hyper* h, OptScalars* a, bool dense = false) {
-  RC_REQUIRE(h != nullptr, "optimizer hyper-parameters missing");
+// who: the entry point, for the refusals' text
+inline int fill_opt_scalars(const char* who, const rc_opt_hyper* h, OptScalars* a, bool dense = false) {
+  RC_REQUIRE(h != nullptr, "%s: optimizer hyper-parameters missing", who);
   RC_REQUIRE(h->opt == RC_OPT_SGD || h->opt == RC_OPT_ADAM || h->opt == RC_OPT_ADAGRAD || (dense && h->opt == RC_OPT_ADADELTA),
-             h->opt == RC_OPT_ADADELTA ? "Adadelta (optimizer %d) is built for dense steps only (rc_dense_update*)"
-                                       : "unknown optimizer %d", h->opt);
+             h->opt == RC_OPT_ADADELTA ? "%s: Adadelta (optimizer %d) is built for dense steps only (rc_dense_update*)"
+                                       : "%s: unknown optimizer %d", who, h->opt);
   a->l2 = (float)h->l2;
   a->neg_lr = (float)(-h->lr);
   a->eps = (float)h->eps;
@@ -40,7 +41,7 @@ inline int fill_opt_scalars(const rc_opt_hyper* h, OptScalars* a, bool dense = f
     a->one_m_b2 = (float)(1.0 - h->beta1);
   }
   if (h->opt == RC_OPT_ADAM) {
-    RC_REQUIRE(h->step >= 1, "Adam needs step >= 1 (got %lld)", (long long)h->step);
+    RC_REQUIRE(h->step >= 1, "%s: Adam needs step >= 1 (got %lld)", who, (long long)h->step);
     const double bc1 = 1.0 - pow(h->beta1, (double)h->step);
     const double bc2 = 1.0 - pow(h->beta2, (double)h->step);
     a->one_m_b1 = (float)(1.0 - h->beta1);
@@ -54,6 +55,13 @@ inline int fill_opt_scalars(const rc_opt_hyper* h, OptScalars* a, bool dense = f
 
 inline int mode_of(const rc_opt_hyper* h) {
   return h->opt == RC_OPT_SGD ? MODE_SGD : (h->opt == RC_OPT_ADAM ? MODE_ADAM : (h->opt == RC_OPT_ADADELTA ? MODE_ADADELTA : MODE_ADAGRAD));
+}
+
+// the state tensors a row-update entry point needs for its optimizer (have_m / have_v: every table of the call has them)
+inline int opt_state_check(const char* who, int mode, bool have_m, bool have_v) {
+  RC_REQUIRE(mode != MODE_ADAM || (have_m && have_v), "%s: Adam needs m and v (exp_avg, exp_avg_sq)", who);
+  RC_REQUIRE(mode != MODE_ADAGRAD || have_m, "%s: Adagrad needs m (state_sum)", who);
+  return RC_OK;
 }
 
 #if defined(__HIPCC__)
@@ -109,10 +117,7 @@ __device__ __forceinline__ void opt_row4(const OptScalars& a, float* __restrict_
   float4 m = make_float4(0, 0, 0, 0), v = make_float4(0, 0, 0, 0);
   if (mode_has_m(MODE)) m = load_stream4(reinterpret_cast<const float4*>(M) + idx4);
   if (mode_has_v(MODE)) v = load_stream4(reinterpret_cast<const float4*>(V) + idx4);
-  opt_elem<MODE>(a, g.x, w.x, m.x, v.x);
-  opt_elem<MODE>(a, g.y, w.y, m.y, v.y);
-  opt_elem<MODE>(a, g.z, w.z, m.z, v.z);
-  opt_elem<MODE>(a, g.w, w.w, m.w, v.w);
+  opt_apply4<MODE>(a, w, m, v, g);
   store_row4(reinterpret_cast<float4*>(W) + idx4, w);
   if (mode_has_m(MODE)) store_row4(reinterpret_cast<float4*>(M) + idx4, m);
   if (mode_has_v(MODE)) store_row4(reinterpret_cast<float4*>(V) + idx4, v);

@@ -214,24 +214,11 @@ __global__ __launch_bounds__(kBlock) void owner_backward_kernel(OwnerArgs a) {
   reinterpret_cast<float4*>(a.pug)[(size_t)t * LPR + l] = acc;
 }
 
-template <int MODE>
-static int launch_owner_backward(const OwnerArgs& a, int d, int64_t n, hipStream_t s) {
-#define RC_OWNER_CASE(DD)                                                                                   \
-  case DD: {                                                                                                \
-    const int64_t blocks = (n + (kBlock / (DD / 4)) - 1) / (kBlock / (DD / 4));                             \
-    if (blocks > kMaxGridX) return fail(RC_ERR_UNSUPPORTED, "rc_owner_backward: grid too large");           \
-    hipLaunchKernelGGL((owner_backward_kernel<DD, MODE>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);   \
-    break;                                                                                                  \
-  }
-  switch (d) {
-    RC_OWNER_CASE(16)
-    RC_OWNER_CASE(32)
-    RC_OWNER_CASE(64)
-    RC_OWNER_CASE(128)
-    RC_OWNER_CASE(256)
-    default: return fail(RC_ERR_UNSUPPORTED, "rc_owner_backward: emb_size must be 16/32/64/128/256, got %d", d);
-  }
-#undef RC_OWNER_CASE
+template <int D, int MODE>
+static int launch_owner_backward(const OwnerArgs& a, int64_t n, hipStream_t s) {
+  const int64_t blocks = (n + (kBlock / (D / 4)) - 1) / (kBlock / (D / 4));
+  if (blocks > kMaxGridX) return fail(RC_ERR_UNSUPPORTED, "rc_owner_backward: grid too large");
+  hipLaunchKernelGGL((owner_backward_kernel<D, MODE>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
   RC_LAUNCH_CHECK();
   return RC_OK;
 }
@@ -313,8 +300,7 @@ extern "C" int rc_owner_backward(float* I, float* mI, float* vI, int d, const fl
   RC_REQUIRE(I && Uall && t32 && rows && g && ws, "rc_owner_backward: null pointer");
   RC_REQUIRE(n > 0 && n < ((int64_t)1 << 31), "rc_owner_backward: bad n=%lld", (long long)n);
   RC_REQUIRE(ws_bytes >= rc_owner_backward_workspace_bytes(n), "rc_owner_backward: workspace too small");
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  RC_REQUIRE(al(I) && al(mI) && al(vI) && al(Uall) && al(pug), "rc_owner_backward: tables must be 16-byte aligned");
+  RC_REQUIRE(aligned16(I, mI, vI, Uall, pug), "rc_owner_backward: tables must be 16-byte aligned");
   uint32_t* n_heads = static_cast<uint32_t*>(ws);
   uint32_t* heads = n_heads + 64;
   // run starts: positions where the tuple index changes (t32 is non-decreasing by construction)
@@ -323,14 +309,16 @@ extern "C" int rc_owner_backward(float* I, float* mI, float* vI, int d, const fl
   memset(&a, 0, sizeof(a));
   a.I = I; a.M = mI; a.V = vI; a.Uall = Uall; a.t32 = t32; a.rows = rows; a.g = g; a.single = single;
   a.heads = heads; a.n_heads = n_heads; a.n = n; a.pug = pug;
-  if (single == nullptr) return launch_owner_backward<MODE_NONE>(a, d, n, s);
-  RC_TRY(fill_opt_scalars(h, &a.o));
-  const int mode = mode_of(h);
-  RC_REQUIRE(mode != MODE_ADAM || (mI && vI), "rc_owner_backward: Adam needs m and v");
-  RC_REQUIRE(mode != MODE_ADAGRAD || mI, "rc_owner_backward: Adagrad needs m (state_sum)");
-  switch (mode) {
-    case MODE_SGD: return launch_owner_backward<MODE_SGD>(a, d, n, s);
-    case MODE_ADAM: return launch_owner_backward<MODE_ADAM>(a, d, n, s);
-    default: return launch_owner_backward<MODE_ADAGRAD>(a, d, n, s);
+  int mode = MODE_NONE;   // no singleton flags: partial user gradients only, no row is updated
+  if (single != nullptr) {
+    RC_TRY(fill_opt_scalars("rc_owner_backward", h, &a.o));
+    mode = mode_of(h);
+    RC_TRY(opt_state_check("rc_owner_backward", mode, mI != nullptr, vI != nullptr));
   }
+  return dispatch_or_fail<MODE_NONE, MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_owner_backward", "update mode", mode, [&](auto M) {
+    constexpr int MODE = M;
+    int rc = RC_OK;
+    if (dispatch_int<16, 32, 64, 128, 256>(d, &rc, [&](auto D) { return launch_owner_backward<D(), MODE>(a, n, s); })) return rc;
+    return fail(RC_ERR_UNSUPPORTED, "rc_owner_backward: emb_size must be 16/32/64/128/256, got %d", d);
+  });
 }

@@ -453,18 +453,6 @@ static int launch_side_update(const PlanUpdArgs& a_in, int64_t n_occ, hipStream_
   return RC_OK;
 }
 
-template <int MODE>
-static int launch_side_update_d(const PlanUpdArgs& a, int d, int64_t n_occ, hipStream_t s) {
-  switch (d) {
-    case 16: return launch_side_update<16, MODE>(a, n_occ, s);
-    case 32: return launch_side_update<32, MODE>(a, n_occ, s);
-    case 64: return launch_side_update<64, MODE>(a, n_occ, s);
-    case 128: return launch_side_update<128, MODE>(a, n_occ, s);
-    case 256: return launch_side_update<256, MODE>(a, n_occ, s);
-    default: return fail(RC_ERR_UNSUPPORTED, "rc_plan_update: row width %d floats (16/32/64/128/256)", d);
-  }
-}
-
 template <int D, int MODE>
 static int launch_step_updates(const PlanUpdArgs& a, int64_t n_occ, hipStream_t s, hipEvent_t* ev_items_done) {
   const uint32_t cus = (uint32_t)device_cus();
@@ -496,17 +484,6 @@ static int launch_step_updates(const PlanUpdArgs& a, int64_t n_occ, hipStream_t 
   return RC_OK;
 }
 
-template <int MODE>
-static int launch_step_updates_d(const PlanUpdArgs& a, int d, int64_t n_occ, hipStream_t s, hipEvent_t* ev) {
-  switch (d) {
-    case 16: return launch_step_updates<16, MODE>(a, n_occ, s, ev);
-    case 32: return launch_step_updates<32, MODE>(a, n_occ, s, ev);
-    case 64: return launch_step_updates<64, MODE>(a, n_occ, s, ev);
-    case 128: return launch_step_updates<128, MODE>(a, n_occ, s, ev);
-    default: return fail(RC_ERR_UNSUPPORTED, "plan update: d=%d (16/32/64/128)", d);
-  }
-}
-
 // The three update launches of a BPRMF step (train_step.hip): item rows, chunks of hot rows, user rows + hot rows
 // + loss mean.  Item-side gradients read pre-step U rows, so every read of U precedes the last launch.
 int plan_bprmf_step_updates(float* U, float* mU, float* vU, float* I, float* mI, float* vI, int d, const int64_t* uid,
@@ -520,10 +497,9 @@ int plan_bprmf_step_updates(float* U, float* mU, float* vU, float* I, float* mI,
   memset(&a, 0, sizeof(a));
   a.long_planned = long_planned ? 1 : 0;
   a.chunk = kPlanChunk;
-  RC_TRY(fill_opt_scalars(h, &a.o));
+  RC_TRY(fill_opt_scalars("rc_bprmf_train_step", h, &a.o));
   const int mode = mode_of(h);
-  RC_REQUIRE(mode != MODE_ADAM || (mU && vU && mI && vI), "rc_bprmf_train_step: Adam needs m and v tables");
-  RC_REQUIRE(mode != MODE_ADAGRAD || (mU && mI), "rc_bprmf_train_step: Adagrad needs the state_sum tables");
+  RC_TRY(opt_state_check("rc_bprmf_train_step", mode, mU && mI, vU && vI));
   a.side[0].t = PlanTable{I, mI, vI};
   a.side[0].g = PlanGrad{gpred, U, uid, C, nullptr, 0xFFFFFFFFu, nullptr, 0};
   a.side[0].rows = rows_i;
@@ -539,11 +515,13 @@ int plan_bprmf_step_updates(float* U, float* mU, float* vU, float* I, float* mI,
   a.loss_n = B;
   a.loss_scale = loss_scale;
   a.loss_out = loss_out;
-  switch (mode) {
-    case MODE_SGD: return launch_step_updates_d<MODE_SGD>(a, d, n_i + B, s, ev_items_done);
-    case MODE_ADAM: return launch_step_updates_d<MODE_ADAM>(a, d, n_i + B, s, ev_items_done);
-    default: return launch_step_updates_d<MODE_ADAGRAD>(a, d, n_i + B, s, ev_items_done);
-  }
+  return dispatch_or_fail<MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_bprmf_train_step", "update mode", mode, [&](auto M) {
+    constexpr int MODE = M;
+    int rc = RC_OK;
+    if (dispatch_int<16, 32, 64, 128>(d, &rc, [&](auto D) { return launch_step_updates<D(), MODE>(a, n_i + B, s, ev_items_done); }))
+      return rc;
+    return fail(RC_ERR_UNSUPPORTED, "plan update: d=%d (16/32/64/128)", d);
+  });
 }
 
 }  // namespace rc
@@ -573,19 +551,19 @@ int run_side_update(PlanUpdArgs& a, const rc_opt_hyper* h, int d_eff, int64_t n_
                     rc_stream_t stream, const char* who, uint32_t* zeroed_counters = nullptr) {
   const UpdWs w = carve_upd_ws(ws, n_occ, d_eff);
   if (ws_bytes < w.total) return fail(RC_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.total);
-  if (h != nullptr) RC_TRY(fill_opt_scalars(h, &a.o));
+  if (h != nullptr) RC_TRY(fill_opt_scalars(who, h, &a.o));
   a.counters = zeroed_counters != nullptr ? zeroed_counters : w.counters;
   a.lw = w.lw;
   hipStream_t s = as_stream(stream);
   if (zeroed_counters == nullptr) RC_HIP(hipMemsetAsync(w.counters, 0, PC_N * sizeof(uint32_t), s));
-  if (h == nullptr) return launch_side_update_d<MODE_DENSE_GRAD>(a, d_eff, n_occ, s);
-  switch (mode_of(h)) {
-    case MODE_SGD: return launch_side_update_d<MODE_SGD>(a, d_eff, n_occ, s);
-    case MODE_ADAM: return launch_side_update_d<MODE_ADAM>(a, d_eff, n_occ, s);
-    default: return launch_side_update_d<MODE_ADAGRAD>(a, d_eff, n_occ, s);
-  }
+  const int mode = h == nullptr ? MODE_DENSE_GRAD : mode_of(h);
+  return dispatch_or_fail<MODE_DENSE_GRAD, MODE_SGD, MODE_ADAM, MODE_ADAGRAD>(who, "update mode", mode, [&](auto M) {
+    constexpr int MODE = M;
+    int rc = RC_OK;
+    if (dispatch_int<16, 32, 64, 128, 256>(d_eff, &rc, [&](auto D) { return launch_side_update<D(), MODE>(a, n_occ, s); })) return rc;
+    return fail(RC_ERR_UNSUPPORTED, "rc_plan_update: row width %d floats (16/32/64/128/256)", d_eff);
+  });
 }
-bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 }  // namespace
 
 extern "C" size_t rc_plan_update_workspace_bytes(int64_t n_occ, int d) {
@@ -603,9 +581,8 @@ extern "C" int rc_plan_update(float* W, float* m, float* v, int d, const rc_plan
   RC_REQUIRE(n_occ > 0 && n_occ < ((int64_t)1 << 31) && div >= 1 && n_split >= 0 && n_split <= n_occ,
              "rc_plan_update: bad sizes n_occ=%lld div=%d n_split=%lld", (long long)n_occ, div, (long long)n_split);
   RC_REQUIRE(src || src2, "rc_plan_update: gradient source missing (src for positions < n_split, src2 for the others)");
-  RC_REQUIRE(mode_of(h) != MODE_ADAM || (m && v), "rc_plan_update: Adam needs m and v");
-  RC_REQUIRE(mode_of(h) != MODE_ADAGRAD || m, "rc_plan_update: Adagrad needs m (state_sum)");
-  RC_REQUIRE(al16(W) && al16(m) && al16(v) && al16(src) && al16(src2), "rc_plan_update: buffers must be 16-byte aligned");
+  RC_TRY(opt_state_check("rc_plan_update", mode_of(h), m != nullptr, v != nullptr));
+  RC_REQUIRE(aligned16(W, m, v, src, src2), "rc_plan_update: buffers must be 16-byte aligned");
   PlanUpdArgs a;
   memset(&a, 0, sizeof(a));
   a.side[0].t = PlanTable{W, m, v};
@@ -638,9 +615,8 @@ extern "C" int rc_plan_update_pair(float* W_a, float* m_a, float* v_a, float* W_
   RC_REQUIRE(W_a && W_b && rows && n_rows && occ && src_a && src_b && h && ws, "rc_plan_update_pair: null pointer");
   RC_REQUIRE(n_occ > 0 && n_occ < ((int64_t)1 << 31) && occ_base >= 0 && occ_base < ((int64_t)1 << 31),
              "rc_plan_update_pair: bad sizes");
-  RC_REQUIRE(mode_of(h) != MODE_ADAM || (m_a && v_a && m_b && v_b), "rc_plan_update_pair: Adam needs m and v");
-  RC_REQUIRE(mode_of(h) != MODE_ADAGRAD || (m_a && m_b), "rc_plan_update_pair: Adagrad needs m (state_sum)");
-  RC_REQUIRE(al16(W_a) && al16(W_b) && al16(m_a) && al16(m_b) && al16(v_a) && al16(v_b) && al16(src_a) && al16(src_b),
+  RC_TRY(opt_state_check("rc_plan_update_pair", mode_of(h), m_a && m_b, v_a && v_b));
+  RC_REQUIRE(aligned16(W_a, W_b, m_a, m_b, v_a, v_b, src_a, src_b),
              "rc_plan_update_pair: buffers must be 16-byte aligned");
   if (d != 8 && d != 16 && d != 32 && d != 64 && d != 128)
     return fail(RC_ERR_UNSUPPORTED, "rc_plan_update_pair: d=%d (2 d must be 16/32/64/128/256)", d);
@@ -665,7 +641,7 @@ extern "C" int rc_plan_row_sums(float* out, int d, const rc_plan_row* rows, cons
   RC_REQUIRE(n_occ > 0 && n_occ < ((int64_t)1 << 31) && div >= 1 && n_split >= 0 && n_split <= n_occ,
              "rc_plan_row_sums: bad sizes n_occ=%lld div=%d n_split=%lld", (long long)n_occ, div, (long long)n_split);
   RC_REQUIRE(src || src2, "rc_plan_row_sums: gradient source missing (src for positions < n_split, src2 for the others)");
-  RC_REQUIRE(al16(out) && al16(src) && al16(src2), "rc_plan_row_sums: buffers must be 16-byte aligned");
+  RC_REQUIRE(aligned16(out, src, src2), "rc_plan_row_sums: buffers must be 16-byte aligned");
   PlanUpdArgs a;
   memset(&a, 0, sizeof(a));
   a.side[0].t = PlanTable{out, nullptr, nullptr};

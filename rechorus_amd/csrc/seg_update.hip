@@ -611,17 +611,6 @@ static int launch_seg_planned(const SegArgs& a, const uint32_t* start, const uin
   return RC_OK;
 }
 
-template <int MODE>
-static int launch_seg_planned_mode(const SegArgs& a, const uint32_t* start, const uint32_t* end, uint32_t n_rows, hipStream_t s) {
-  switch (a.d) {
-    case 16: return launch_seg_planned<16, MODE>(a, start, end, n_rows, s);
-    case 32: return launch_seg_planned<32, MODE>(a, start, end, n_rows, s);
-    case 64: return launch_seg_planned<64, MODE>(a, start, end, n_rows, s);
-    case 128: return launch_seg_planned<128, MODE>(a, start, end, n_rows, s);
-    default: return launch_seg_planned<256, MODE>(a, start, end, n_rows, s);
-  }
-}
-
 template <int D, int MODE>
 static int launch_seg_rows(const SegArgs& a, const uint32_t* start, const uint32_t* end, uint32_t n_rows, hipStream_t s) {
   const unsigned blocks = (n_rows + (kBlock / 64) - 1) / (kBlock / 64);
@@ -636,17 +625,6 @@ static int launch_seg_rows(const SegArgs& a, const uint32_t* start, const uint32
     RC_LAUNCH_CHECK();
   }
   return RC_OK;
-}
-
-template <int MODE>
-static int launch_seg_rows_mode(const SegArgs& a, const uint32_t* start, const uint32_t* end, uint32_t n_rows, hipStream_t s) {
-  switch (a.d) {
-    case 16: return launch_seg_rows<16, MODE>(a, start, end, n_rows, s);
-    case 32: return launch_seg_rows<32, MODE>(a, start, end, n_rows, s);
-    case 64: return launch_seg_rows<64, MODE>(a, start, end, n_rows, s);
-    case 128: return launch_seg_rows<128, MODE>(a, start, end, n_rows, s);
-    default: return launch_seg_rows<256, MODE>(a, start, end, n_rows, s);
-  }
 }
 
 // ---- 5. the rows route without the radix sort: per-row [start, end) from a counting sort of the batch's ids ----------------
@@ -1267,16 +1245,8 @@ static int launch_seg(const SegArgs& a, hipStream_t s) {
 
 template <int MODE>
 static int launch_seg_mode(const SegArgs& a, bool vec_ok, hipStream_t s) {
-  if (vec_ok) {
-    switch (a.d) {
-      case 16: return launch_seg<16, MODE>(a, s);
-      case 32: return launch_seg<32, MODE>(a, s);
-      case 64: return launch_seg<64, MODE>(a, s);
-      case 128: return launch_seg<128, MODE>(a, s);
-      case 256: return launch_seg<256, MODE>(a, s);
-      default: break;
-    }
-  }
+  int rc = RC_OK;
+  if (vec_ok && dispatch_int<16, 32, 64, 128, 256>(a.d, &rc, [&](auto D) { return launch_seg<D(), MODE>(a, s); })) return rc;
   if (a.d > 64 * kGenChunks)
     return fail(RC_ERR_UNSUPPORTED, "rc_segmented_update: d=%d > %d", a.d, 64 * kGenChunks);
   const int64_t blocks = (a.n_occ + (kBlock / 64) - 1) / (kBlock / 64);
@@ -1299,6 +1269,18 @@ static int launch_seg_mode(const SegArgs& a, bool vec_ok, hipStream_t s) {
 }
 
 static bool vector_kernel_for(int d) { return d == 16 || d == 32 || d == 64 || d == 128 || d == 256; }
+
+// f(integral_constant) for the update mode / for the row width of the vector kernels.  (The width's refusal is not reached today:
+// both users refuse a width outside vector_kernel_for with their own message first.  It stays, so that a list that drifts apart
+// from vector_kernel_for ends in a refusal and not in a kernel of another width.)
+template <class F>
+static int for_seg_mode(const char* who, int mode, F&& f) {
+  return dispatch_or_fail<MODE_DENSE_GRAD, MODE_SGD, MODE_ADAM, MODE_ADAGRAD>(who, "update mode", mode, f);
+}
+template <class F>
+static int for_seg_width(const char* who, int d, F&& f) {
+  return dispatch_or_fail<16, 32, 64, 128, 256>(who, "row width", d, f);
+}
 
 struct SegWs {
   uint32_t* counters;
@@ -1325,6 +1307,44 @@ static SegWs carve_seg_ws(void* base, int64_t n_occ, int d) {
   w.partial = cv.take<float>((size_t)w.partial_cap * (size_t)d);
   w.total = cv.off;
   return w;
+}
+
+// where an occurrence's gradient row comes from: coef[o] * src[src_index[o / div]] (coef / src_index may be null), and plain rows
+// src2[o - n_split] for the occurrences o >= n_split
+struct SegSources {
+  const float* coef;
+  const float* src;
+  const int64_t* src_index;
+  int div;
+  const float* src2;
+  int64_t n_split;
+};
+
+// What rc_segmented_update, _rows, rc_rows_plan_update and _pair fill alike in SegArgs (all else is zeroed): the table and its state,
+// the sorted occurrences, the gradient sources, the long-row workspace (counters: w's own; the rows routes point them elsewhere
+// afterwards), and -- unless a dense gradient is asked for -- the optimizer: its scalars, *mode, the state check for m / v and
+// capturable Adam for step_dev.  Reads no workspace byte, so it runs before the caller's workspace-size check.
+static int seg_args_init(const char* who, SegArgs* a, int* mode, float* W, float* m, float* v, int d, const uint32_t* keys,
+                         const uint32_t* perm, int64_t n_occ, const SegSources& g, float* dense_grad, const SegWs& w,
+                         const rc_opt_hyper* h, const int64_t* step_dev) {
+  memset(a, 0, sizeof(*a));
+  a->W = W; a->M = m; a->V = v;
+  a->keys = keys; a->perm = perm; a->n_occ = n_occ;
+  a->coef = g.coef; a->src = g.src; a->src_index = g.src_index; a->div = g.div; a->d = d;
+  a->src2 = g.src2; a->n_split = (uint32_t)g.n_split;
+  a->dense_grad = dense_grad;
+  a->counters = w.counters; a->long_list = w.long_list; a->rows = w.rows; a->chunks = w.chunks;
+  a->partial = w.partial;
+  a->long_cap = w.long_cap; a->chunk_cap = w.chunk_cap; a->partial_cap = w.partial_cap;
+  *mode = MODE_DENSE_GRAD;
+  if (dense_grad) return RC_OK;
+  RC_TRY(fill_opt_scalars(who, h, &a->o));
+  *mode = mode_of(h);
+  RC_TRY(opt_state_check(who, *mode, m != nullptr, v != nullptr));
+  if (*mode == MODE_ADAM && step_dev) {
+    a->step_dev = step_dev; a->beta1 = h->beta1; a->beta2 = h->beta2; a->lr = h->lr;
+  }
+  return RC_OK;
 }
 
 }  // namespace rc
@@ -1369,33 +1389,17 @@ extern "C" int rc_segmented_update(float* W, float* m, float* v, int d, const ui
   RC_REQUIRE((heads == nullptr) == (n_heads == nullptr),
              "rc_segmented_update: heads and n_heads go together");
   const SegWs w = carve_seg_ws(ws, n_occ, d);
+  SegArgs a;
+  int mode;
+  RC_TRY(seg_args_init("rc_segmented_update", &a, &mode, W, m, v, d, keys, perm, n_occ, {coef, src, src_index, div, src2, n_split},
+                       dense_grad, w, h, nullptr));
   if (ws_bytes < w.total)
     return fail(RC_ERR_WORKSPACE, "rc_segmented_update: workspace %zu < %zu", ws_bytes, w.total);
   hipStream_t s = as_stream(stream);
-  SegArgs a;
-  memset(&a, 0, sizeof(a));
-  a.W = W; a.M = m; a.V = v;
-  a.keys = keys; a.perm = perm; a.n_occ = n_occ;
-  a.coef = coef; a.src = src; a.src_index = src_index; a.div = div; a.d = d;
-  a.src2 = src2; a.n_split = (uint32_t)n_split;
   a.key_base = (uint32_t)key_base; a.occ_base = (uint32_t)occ_base;
-  a.dense_grad = dense_grad;
   a.skip_single = (flags & RC_SEG_SKIP_SINGLETONS) ? 1 : 0;
-  a.counters = w.counters; a.long_list = w.long_list; a.rows = w.rows; a.chunks = w.chunks;
-  a.partial = w.partial;
-  a.long_cap = w.long_cap; a.chunk_cap = w.chunk_cap; a.partial_cap = w.partial_cap;
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  bool vec_ok = vector_kernel_for(d) && al(src) && al(src2);
-  int mode = MODE_DENSE_GRAD;
-  if (dense_grad) {
-    vec_ok = vec_ok && al(dense_grad);
-  } else {
-    RC_TRY(fill_opt_scalars(h, &a.o));
-    mode = mode_of(h);
-    RC_REQUIRE(mode != MODE_ADAM || (m && v), "rc_segmented_update: Adam needs m and v");
-    RC_REQUIRE(mode != MODE_ADAGRAD || m, "rc_segmented_update: Adagrad needs m (state_sum)");
-    vec_ok = vec_ok && al(W) && al(m) && al(v);
-  }
+  const bool vec_ok = vector_kernel_for(d) && aligned16(src, src2) &&
+                      (dense_grad ? aligned16(dense_grad) : aligned16(W, m, v));
   RC_HIP(hipMemsetAsync(w.counters, 0, CNT_N * sizeof(uint32_t), s));
   // (off the vector route the head list's room -- n_occ words -- is free: 2 slots of 6 words per 512 positions fit)
   if (!vec_ok && n_occ >= 4 * kNtTile) a.narrow_ws = w.heads;
@@ -1410,12 +1414,7 @@ extern "C" int rc_segmented_update(float* W, float* m, float* v, int d, const ui
       a.n_heads = &w.counters[CNT_HEADS];
     }
   }
-  switch (mode) {
-    case MODE_DENSE_GRAD: return launch_seg_mode<MODE_DENSE_GRAD>(a, vec_ok, s);
-    case MODE_SGD: return launch_seg_mode<MODE_SGD>(a, vec_ok, s);
-    case MODE_ADAM: return launch_seg_mode<MODE_ADAM>(a, vec_ok, s);
-    default: return launch_seg_mode<MODE_ADAGRAD>(a, vec_ok, s);
-  }
+  return for_seg_mode("rc_segmented_update", mode, [&](auto M) { return launch_seg_mode<M()>(a, vec_ok, s); });
 }
 
 extern "C" size_t rc_segmented_rows_workspace_bytes(int64_t n_rows, int64_t n_occ, int d) {
@@ -1439,48 +1438,31 @@ extern "C" int rc_segmented_update_rows(float* W, float* m, float* v, int d, int
              "rc_segmented_update_rows: bad shape div=%d n_occ=%lld n_rows=%lld", div, (long long)n_occ, (long long)n_rows);
   RC_REQUIRE(dense_grad != nullptr || W != nullptr, "rc_segmented_update_rows: no output (W or dense_grad)");
   if (!vector_kernel_for(d)) return fail(RC_ERR_UNSUPPORTED, "rc_segmented_update_rows: d=%d (16/32/64/128/256)", d);
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  RC_REQUIRE(al(src) && al(src2) && al(W) && al(m) && al(v) && al(dense_grad), "rc_segmented_update_rows: buffers must be 16-byte aligned");
-  if (ws_bytes < rc_segmented_rows_workspace_bytes(n_rows, n_occ, d))
-    return fail(RC_ERR_WORKSPACE, "rc_segmented_update_rows: workspace %zu < %zu", ws_bytes,
-                rc_segmented_rows_workspace_bytes(n_rows, n_occ, d));
+  RC_REQUIRE(aligned16(src, src2, W, m, v, dense_grad), "rc_segmented_update_rows: buffers must be 16-byte aligned");
   const SegWs w = carve_seg_ws(ws, n_occ, d);
   // [counters (64 words) | start | end]: zeroed by ONE fill (the counters of the long-row pass sit beside the bounds)
   uint32_t* counters = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + align_up(w.total, 256));
   uint32_t* start = counters + 64;
   uint32_t* end = start + n_rows;
-  hipStream_t s = as_stream(stream);
   SegArgs a;
-  memset(&a, 0, sizeof(a));
-  a.W = W; a.M = m; a.V = v;
-  a.keys = keys; a.perm = perm; a.n_occ = n_occ;
-  a.coef = coef; a.src = src; a.src_index = src_index; a.div = div; a.d = d;
-  a.src2 = src2; a.n_split = (uint32_t)n_split;
-  a.dense_grad = dense_grad;
-  a.counters = counters; a.long_list = w.long_list; a.rows = w.rows; a.chunks = w.chunks;
-  a.partial = w.partial;
-  a.long_cap = w.long_cap; a.chunk_cap = w.chunk_cap; a.partial_cap = w.partial_cap;
-  int mode = MODE_DENSE_GRAD;
-  if (!dense_grad) {
-    RC_TRY(fill_opt_scalars(h, &a.o));
-    mode = mode_of(h);
-    RC_REQUIRE(mode != MODE_ADAM || (m && v), "rc_segmented_update_rows: Adam needs m and v");
-    RC_REQUIRE(mode != MODE_ADAGRAD || m, "rc_segmented_update_rows: Adagrad needs m (state_sum)");
-    if (mode == MODE_ADAM && step_dev) {
-      a.step_dev = step_dev; a.beta1 = h->beta1; a.beta2 = h->beta2; a.lr = h->lr;
-    }
-  }
+  int mode;
+  RC_TRY(seg_args_init("rc_segmented_update_rows", &a, &mode, W, m, v, d, keys, perm, n_occ,
+                       {coef, src, src_index, div, src2, n_split}, dense_grad, w, h, step_dev));
+  a.counters = counters;
+  if (ws_bytes < rc_segmented_rows_workspace_bytes(n_rows, n_occ, d))
+    return fail(RC_ERR_WORKSPACE, "rc_segmented_update_rows: workspace %zu < %zu", ws_bytes,
+                rc_segmented_rows_workspace_bytes(n_rows, n_occ, d));
+  hipStream_t s = as_stream(stream);
   static_assert(CNT_N <= 64, "counters beside the bounds");
   RC_HIP(hipMemsetAsync(counters, 0, (64 + 2 * (size_t)n_rows) * sizeof(uint32_t), s));   // absent rows: start = end = 0
   hipLaunchKernelGGL(segment_bounds_kernel, dim3((unsigned)((n_occ + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, keys, n_occ, 0u,
                      (uint32_t)n_rows, start, end);
   RC_LAUNCH_CHECK();
-  switch (mode) {
-    case MODE_DENSE_GRAD: return launch_seg_rows_mode<MODE_DENSE_GRAD>(a, start, end, (uint32_t)n_rows, s);
-    case MODE_SGD: return launch_seg_rows_mode<MODE_SGD>(a, start, end, (uint32_t)n_rows, s);
-    case MODE_ADAM: return launch_seg_rows_mode<MODE_ADAM>(a, start, end, (uint32_t)n_rows, s);
-    default: return launch_seg_rows_mode<MODE_ADAGRAD>(a, start, end, (uint32_t)n_rows, s);
-  }
+  return for_seg_mode("rc_segmented_update_rows", mode, [&](auto M) {
+    constexpr int MODE = M;
+    return for_seg_width("rc_segmented_update_rows", d,
+                         [&](auto D) { return launch_seg_rows<D(), MODE>(a, start, end, (uint32_t)n_rows, s); });
+  });
 }
 
 // ---- rows route from a counting sort (section 5) -----------------------------------------------------------------------------
@@ -1593,38 +1575,21 @@ extern "C" int rc_rows_plan_update(float* W, float* m, float* v, int d, int64_t 
   RC_REQUIRE(src && ws && div >= 1 && n_split >= 0 && n_split <= n_occ, "rc_rows_plan_update: bad arguments");
   RC_REQUIRE(dense_grad != nullptr || W != nullptr, "rc_rows_plan_update: no output (W or dense_grad)");
   if (!rc_rows_plan_supported(n_rows, n_occ, d)) return fail(RC_ERR_UNSUPPORTED, "rc_rows_plan_update: shape not supported");
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  RC_REQUIRE(al(src) && al(src2) && al(W) && al(m) && al(v) && al(dense_grad), "rc_rows_plan_update: buffers must be 16-byte aligned");
+  RC_REQUIRE(aligned16(src, src2, W, m, v, dense_grad), "rc_rows_plan_update: buffers must be 16-byte aligned");
   const RowsPlanWs w = carve_rows_plan_ws(ws, n_rows, n_occ, d);
+  SegArgs a;
+  int mode;
+  RC_TRY(seg_args_init("rc_rows_plan_update", &a, &mode, W, m, v, d, w.keys, w.perm, n_occ,
+                       {coef, src, src_index, div, src2, n_split}, dense_grad, w.seg, h, step_dev));
+  a.counters = w.counters;
   if (ws_bytes < w.total) return fail(RC_ERR_WORKSPACE, "rc_rows_plan_update: workspace %zu < %zu", ws_bytes, w.total);
   hipStream_t s = as_stream(stream);
-  SegArgs a;
-  memset(&a, 0, sizeof(a));
-  a.W = W; a.M = m; a.V = v;
-  a.keys = w.keys; a.perm = w.perm; a.n_occ = n_occ;
-  a.coef = coef; a.src = src; a.src_index = src_index; a.div = div; a.d = d;
-  a.src2 = src2; a.n_split = (uint32_t)n_split;
-  a.dense_grad = dense_grad;
-  a.counters = w.counters; a.long_list = w.seg.long_list; a.rows = w.seg.rows; a.chunks = w.seg.chunks;
-  a.partial = w.seg.partial;
-  a.long_cap = w.seg.long_cap; a.chunk_cap = w.seg.chunk_cap; a.partial_cap = w.seg.partial_cap;
   a.planned = 1;
-  int mode = MODE_DENSE_GRAD;
-  if (!dense_grad) {
-    RC_TRY(fill_opt_scalars(h, &a.o));
-    mode = mode_of(h);
-    RC_REQUIRE(mode != MODE_ADAM || (m && v), "rc_rows_plan_update: Adam needs m and v");
-    RC_REQUIRE(mode != MODE_ADAGRAD || m, "rc_rows_plan_update: Adagrad needs m (state_sum)");
-    if (mode == MODE_ADAM && step_dev) {
-      a.step_dev = step_dev; a.beta1 = h->beta1; a.beta2 = h->beta2; a.lr = h->lr;
-    }
-  }
-  switch (mode) {
-    case MODE_DENSE_GRAD: return launch_seg_planned_mode<MODE_DENSE_GRAD>(a, w.start, w.end, (uint32_t)n_rows, s);
-    case MODE_SGD: return launch_seg_planned_mode<MODE_SGD>(a, w.start, w.end, (uint32_t)n_rows, s);
-    case MODE_ADAM: return launch_seg_planned_mode<MODE_ADAM>(a, w.start, w.end, (uint32_t)n_rows, s);
-    default: return launch_seg_planned_mode<MODE_ADAGRAD>(a, w.start, w.end, (uint32_t)n_rows, s);
-  }
+  return for_seg_mode("rc_rows_plan_update", mode, [&](auto M) {
+    constexpr int MODE = M;
+    return for_seg_width("rc_rows_plan_update", d,
+                         [&](auto D) { return launch_seg_planned<D(), MODE>(a, w.start, w.end, (uint32_t)n_rows, s); });
+  });
 }
 
 // Two tables that share their ids (NeuMF's mf / mlp embedding of a user or an item: models/general/NeuMF.py:37-40
@@ -1644,28 +1609,21 @@ extern "C" int rc_segmented_update_pair(float* W_a, float* m_a, float* v_a, floa
   RC_REQUIRE((heads == nullptr) == (n_heads == nullptr), "rc_segmented_update_pair: heads and n_heads go together");
   if (!vector_kernel_for(2 * d))
     return fail(RC_ERR_UNSUPPORTED, "rc_segmented_update_pair: d=%d (2 d must be 16/32/64/128/256)", d);
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  RC_REQUIRE(al(W_a) && al(W_b) && al(m_a) && al(m_b) && al(v_a) && al(v_b) && al(src_a) && al(src_b) && al(dense_grad_a) &&
-                 al(dense_grad_b), "rc_segmented_update_pair: buffers must be 16-byte aligned");
+  RC_REQUIRE(aligned16(W_a, W_b, m_a, m_b, v_a, v_b, src_a, src_b, dense_grad_a, dense_grad_b),
+             "rc_segmented_update_pair: buffers must be 16-byte aligned");
   const SegWs w = carve_seg_ws(ws, n_occ, 2 * d);
+  SegArgs a;
+  int mode;
+  SegSources g = {};   // every occurrence o takes the plain rows src_a[o] / src_b[o]
+  g.src = src_a; g.div = 1; g.n_split = n_occ;
+  RC_TRY(seg_args_init("rc_segmented_update_pair", &a, &mode, W_a, m_a, v_a, 2 * d, keys, perm, n_occ, g, dense_grad_a, w, h, nullptr));
+  RC_TRY(opt_state_check("rc_segmented_update_pair", mode, m_b != nullptr, v_b != nullptr));
   if (ws_bytes < w.total) return fail(RC_ERR_WORKSPACE, "rc_segmented_update_pair: workspace %zu < %zu", ws_bytes, w.total);
   hipStream_t s = as_stream(stream);
-  SegArgs a;
-  memset(&a, 0, sizeof(a));
   a.pair = 1;
-  a.W = W_a; a.M = m_a; a.V = v_a; a.Wb = W_b; a.Mb = m_b; a.Vb = v_b;
-  a.keys = keys; a.perm = perm; a.n_occ = n_occ; a.src = src_a; a.srcb = src_b; a.div = 1; a.d = 2 * d;
-  a.n_split = (uint32_t)n_occ;
-  a.dense_grad = dense_grad_a; a.dense_grad_b = dense_grad_b;
-  a.counters = w.counters; a.long_list = w.long_list; a.rows = w.rows; a.chunks = w.chunks; a.partial = w.partial;
-  a.long_cap = w.long_cap; a.chunk_cap = w.chunk_cap; a.partial_cap = w.partial_cap;
-  int mode = MODE_DENSE_GRAD;
-  if (!dense_grad_a) {
-    RC_TRY(fill_opt_scalars(h, &a.o));
-    mode = mode_of(h);
-    RC_REQUIRE(mode != MODE_ADAM || (m_a && v_a && m_b && v_b), "rc_segmented_update_pair: Adam needs m and v");
-    RC_REQUIRE(mode != MODE_ADAGRAD || (m_a && m_b), "rc_segmented_update_pair: Adagrad needs m (state_sum)");
-  }
+  a.Wb = W_b; a.Mb = m_b; a.Vb = v_b;
+  a.srcb = src_b;
+  a.dense_grad_b = dense_grad_b;
   RC_HIP(hipMemsetAsync(w.counters, 0, CNT_N * sizeof(uint32_t), s));
   if (heads) {
     a.heads = heads;
@@ -1675,10 +1633,5 @@ extern "C" int rc_segmented_update_pair(float* W_a, float* m_a, float* v_a, floa
     a.heads = w.heads;
     a.n_heads = &w.counters[CNT_HEADS];
   }
-  switch (mode) {
-    case MODE_DENSE_GRAD: return launch_seg_mode<MODE_DENSE_GRAD>(a, true, s);
-    case MODE_SGD: return launch_seg_mode<MODE_SGD>(a, true, s);
-    case MODE_ADAM: return launch_seg_mode<MODE_ADAM>(a, true, s);
-    default: return launch_seg_mode<MODE_ADAGRAD>(a, true, s);
-  }
+  return for_seg_mode("rc_segmented_update_pair", mode, [&](auto M) { return launch_seg_mode<M()>(a, true, s); });
 }

@@ -165,18 +165,14 @@ __global__ __launch_bounds__(kBlock) void small_update_kernel(SmallUpdArgs a) {
   }
 }
 
-template <int D>
-static int small_update_launch_d(const SmallUpdArgs& a, int mode, hipStream_t s) {
+template <int D, int MODE>
+static int small_update_launch(const SmallUpdArgs& a, hipStream_t s) {
   // one lane-group per row, a few rows per group: the grid covers the worst case (every key a distinct row)
   constexpr int GPB = kBlock / (D / 4);
   unsigned blocks = (a.n + GPB - 1) / GPB;
   if (blocks > 2048u) blocks = 2048u;
   if (blocks < 1u) blocks = 1u;
-  switch (mode) {
-    case MODE_SGD: hipLaunchKernelGGL((small_update_kernel<D, MODE_SGD>), dim3(blocks + 1), dim3(kBlock), 0, s, a); break;
-    case MODE_ADAM: hipLaunchKernelGGL((small_update_kernel<D, MODE_ADAM>), dim3(blocks + 1), dim3(kBlock), 0, s, a); break;
-    default: hipLaunchKernelGGL((small_update_kernel<D, MODE_ADAGRAD>), dim3(blocks + 1), dim3(kBlock), 0, s, a); break;
-  }
+  hipLaunchKernelGGL((small_update_kernel<D, MODE>), dim3(blocks + 1), dim3(kBlock), 0, s, a);
   RC_LAUNCH_CHECK();
   return RC_OK;
 }
@@ -449,19 +445,17 @@ int small_step_launch(float* U, float* I, float* mU, float* vU, float* mI, float
   }
   SmallUpdArgs a;
   memset(&a, 0, sizeof(a));
-  RC_TRY(fill_opt_scalars(h, &a.o));
+  RC_TRY(fill_opt_scalars("rc_bprmf_train_step", h, &a.o));
   const int mode = mode_of(h);
-  RC_REQUIRE(mode != MODE_ADAM || (mU && vU && mI && vI), "rc_bprmf_train_step: Adam needs m and v tables");
-  RC_REQUIRE(mode != MODE_ADAGRAD || (mU && mI), "rc_bprmf_train_step: Adagrad needs the state_sum tables");
+  RC_TRY(opt_state_check("rc_bprmf_train_step", mode, mU && mI, vU && vI));
   a.I = I; a.mI = mI; a.vI = vI; a.U = U; a.mU = mU; a.vU = vU;
   a.rows = rows; a.occ = occ; a.cnt = cnt; a.n = (uint32_t)n; a.n_a = (uint32_t)n_i; a.C = C;
   a.gpred = gpred; a.ub = ub; a.ugrad = ugrad; a.loss_vec = loss_vec; a.B = B; a.loss_scale = inv_b; a.loss_out = loss_out;
-  switch (d) {
-    case 16: return small_update_launch_d<16>(a, mode, s);
-    case 32: return small_update_launch_d<32>(a, mode, s);
-    case 64: return small_update_launch_d<64>(a, mode, s);
-    default: return small_update_launch_d<128>(a, mode, s);
-  }
+  return dispatch_or_fail<16, 32, 64, 128>("rc_bprmf_train_step (small step)", "d", d, [&](auto D) {
+    constexpr int DD = D;
+    return dispatch_or_fail<MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_bprmf_train_step (small step)", "update mode", mode,
+                                                               [&](auto M) { return small_update_launch<DD, M()>(a, s); });
+  });
 }
 
 }  // namespace rc
@@ -511,10 +505,9 @@ static int small_row_sums_impl(bool build_plan, const int64_t* ids, int64_t n, i
                 (long long)n, kSmallMaxKeys, (long long)n_rows, d);
   if (ws_bytes < rc_small_row_sums_workspace_bytes(n))
     return fail(RC_ERR_WORKSPACE, "rc_small_row_sums: workspace %zu < %zu", ws_bytes, rc_small_row_sums_workspace_bytes(n));
-  RC_REQUIRE(d <= 4 || (reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0),
+  RC_REQUIRE(d <= 4 || aligned16(src, out),
              "rc_small_row_sums: src / out must be 16-byte aligned");
-  RC_REQUIRE(fm == nullptr || (d >= 16 && fm->V && fm->S && fm->g && fm->F >= 1 && n % fm->F == 0 && reinterpret_cast<uintptr_t>(fm->V) % 16 == 0 &&
-                               reinterpret_cast<uintptr_t>(fm->S) % 16 == 0),
+  RC_REQUIRE(fm == nullptr || (d >= 16 && fm->V && fm->S && fm->g && fm->F >= 1 && n % fm->F == 0 && aligned16(fm->V, fm->S)),
              "rc_small_row_sums_planned: the FM term's backward needs d >= 16, 16-byte aligned V [n / F, F, d] and S [n / F, d], and g [n / F]");
   hipStream_t s = as_stream(stream);
   Carver cv(ws);
@@ -565,21 +558,11 @@ static int small_row_sums_impl(bool build_plan, const int64_t* ids, int64_t n, i
     if (blocks > 2048u) blocks = 2048u;
     a.blocks_rows = blocks;
     const unsigned grid = blocks + (unsigned)(a.n_numeric * kSmallNumericSplits);     // the numeric fields' workgroups come last: the rows' are dispatched first
-    if (fm != nullptr) {
-      switch (d) {
-        case 16: hipLaunchKernelGGL((small_row_sums_kernel<16, true>), dim3(grid), dim3(kBlock), 0, s, a); break;
-        case 32: hipLaunchKernelGGL((small_row_sums_kernel<32, true>), dim3(grid), dim3(kBlock), 0, s, a); break;
-        case 64: hipLaunchKernelGGL((small_row_sums_kernel<64, true>), dim3(grid), dim3(kBlock), 0, s, a); break;
-        default: hipLaunchKernelGGL((small_row_sums_kernel<128, true>), dim3(grid), dim3(kBlock), 0, s, a); break;
-      }
-    } else {
-      switch (d) {
-        case 16: hipLaunchKernelGGL((small_row_sums_kernel<16, false>), dim3(grid), dim3(kBlock), 0, s, a); break;
-        case 32: hipLaunchKernelGGL((small_row_sums_kernel<32, false>), dim3(grid), dim3(kBlock), 0, s, a); break;
-        case 64: hipLaunchKernelGGL((small_row_sums_kernel<64, false>), dim3(grid), dim3(kBlock), 0, s, a); break;
-        default: hipLaunchKernelGGL((small_row_sums_kernel<128, false>), dim3(grid), dim3(kBlock), 0, s, a); break;
-      }
-    }
+    RC_TRY((dispatch_or_fail<16, 32, 64, 128>("rc_small_row_sums", "d", d, [&](auto D) -> int {
+      if (fm != nullptr) hipLaunchKernelGGL((small_row_sums_kernel<D(), true>), dim3(grid), dim3(kBlock), 0, s, a);
+      else hipLaunchKernelGGL((small_row_sums_kernel<D(), false>), dim3(grid), dim3(kBlock), 0, s, a);
+      return RC_OK;
+    })));
   }
   RC_LAUNCH_CHECK();
   return RC_OK;

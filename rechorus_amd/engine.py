@@ -394,9 +394,10 @@ def bprmf_fwd_bwd_update(U, I, uid, iid, single, hyper, mI=None, vI=None, inv_b=
 
 def segmented_update(keys, perm, src, hyper=None, W=None, m=None, v=None, coef=None,
                      src_index=None, div=1, dense_grad=None, skip_singletons=False, heads=None,
-                     n_heads=None):
+                     n_heads=None, src2=None, n_split=None):
     """rc_segmented_update: per distinct row r, grad_r = sum coef[o]*src[srow(o)], then either
-    write dense_grad[r] or apply the optimizer to W[r] (and m, v) in place."""
+    write dense_grad[r] or apply the optimizer to W[r] (and m, v) in place.
+    n_split (with src2): occurrences >= n_split take plain rows src2[o - n_split]."""
     n_occ = keys.numel()
     d = src.shape[-1]
     dev = keys.device
@@ -409,7 +410,8 @@ def segmented_update(keys, perm, src, hyper=None, W=None, m=None, v=None, coef=N
               _ptr(v, torch.float32, "v", allow_none=True), d,
               _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
               _ptr(coef, torch.float32, "coef", allow_none=True), _ptr(src, torch.float32, "src"),
-              _ptr(src_index, torch.int64, "src_index", allow_none=True), int(div), None, n_occ, 0, 0, hp,
+              _ptr(src_index, torch.int64, "src_index", allow_none=True), int(div),
+              _ptr(src2, torch.float32, "src2", allow_none=n_split is None), n_occ if n_split is None else int(n_split), 0, 0, hp,
               _ptr(dense_grad, torch.float32, "dense_grad", allow_none=True),
               _ptr(heads, torch.int32, "heads", True), _ptr(n_heads, torch.int32, "n_heads", True),
               _lib.RC_SEG_SKIP_SINGLETONS if skip_singletons else 0,
@@ -1647,12 +1649,7 @@ def segmented_update2(keys, perm, src, src2, n_split, hyper=None, W=None, m=None
     if step_dev is not None:
         raise RuntimeError("segmented_update2(step_dev=...): the device-side step count is carried by the one-wave-per-row "
                            "update only (seg_rows_route: a small catalogue under a large batch)")
-    ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, d), keys.device, "seg")
-    _lib.call("rc_segmented_update", _ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d,
-              _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
-              _ptr(coef, f32, "coef", True), _ptr(src, f32, "src"), _ptr(src_index, torch.int64, "src_index", True),
-              int(div), _ptr(src2, f32, "src2"), int(n_split), 0, 0, C.byref(hyper) if hyper is not None else None,
-              _ptr(dense_grad, f32, "dense_grad", True), None, None, 0, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+    segmented_update(keys, perm, src, hyper, W, m, v, coef, src_index, div, dense_grad, src2=src2, n_split=n_split)
 
 
 def rows_plan_supported(n_rows, n_occ, d):

@@ -78,6 +78,58 @@ def test_folded_entry_points_reject_meaningless_argument_combinations(lib):
         assert b"null pointer" in lib.rc_last_error_string()
 
 
+def test_segmented_update_entry_points_refuse_bad_arguments(lib):
+    """The four segmented-update entry points share their SegArgs setup; each keeps its own argument checks.  Every refusal carries
+    the entry point's name, and everything that inspects only the arguments comes before the workspace-size check: ws_bytes = 0 in
+    every case, so a lost check ends in RC_ERR_WORKSPACE instead of a launch on the made-up pointers below."""
+    p, q = C.c_void_p(64), C.c_void_p(68)      # never dereferenced; q is not 16-byte aligned
+    n_occ, d, n_rows = 100, 64, 10
+
+    def hyper(opt):
+        return C.byref(_lib.OptHyper(opt=opt, lr=0.1, beta1=0.9, beta2=0.999, eps=1e-8, step=1))
+    sgd, adam, adagrad, adadelta = (hyper(o) for o in (_lib.RC_OPT_SGD, _lib.RC_OPT_ADAM, _lib.RC_OPT_ADAGRAD, _lib.RC_OPT_ADADELTA))
+
+    def seg(W=p, m=None, v=None, h=sgd, dense_grad=None, heads=None, n_heads=None, src2=None, n_split=n_occ):
+        return lib.rc_segmented_update(W, m, v, d, p, p, n_occ, None, p, None, 1, src2, n_split, 0, 0, h, dense_grad, heads, n_heads, 0,
+                                       p, 0, None)
+
+    def rows(W=p, m=None, v=None, h=sgd, d=d):
+        return lib.rc_segmented_update_rows(W, m, v, d, n_rows, p, p, n_occ, None, p, None, 1, None, n_occ, h, None, None, p, 0, None)
+
+    def plan(m=None, v=None, h=sgd, n_rows=n_rows):
+        return lib.rc_rows_plan_update(p, m, v, d, n_rows, n_occ, None, p, None, 1, None, n_occ, h, None, None, p, 0, None)
+
+    def pair(h=sgd, d=32, dense_grad_a=None):
+        return lib.rc_segmented_update_pair(p, None, None, p, None, None, d, p, p, n_occ, p, p, h, dense_grad_a, None, None, None,
+                                            p, 0, None)
+    INVALID, WORKSPACE, UNSUPPORTED = -1, -2, -4
+    table = [
+        ("rc_segmented_update", lambda: seg(W=None), INVALID, b"no output"),
+        ("rc_segmented_update", lambda: seg(heads=p), INVALID, b"go together"),
+        ("rc_segmented_update", lambda: seg(src2=p, n_split=n_occ + 1), INVALID, b"n_split"),
+        ("rc_segmented_update", lambda: seg(h=adam), INVALID, b"Adam"),
+        ("rc_segmented_update", lambda: seg(h=adagrad), INVALID, b"Adagrad"),
+        ("rc_segmented_update", lambda: seg(h=adadelta), INVALID, b"dense steps only"),
+        ("rc_segmented_update_rows", lambda: rows(W=q), INVALID, b"16-byte aligned"),
+        ("rc_segmented_update_rows", lambda: rows(d=48), UNSUPPORTED, b""),
+        ("rc_segmented_update_rows", lambda: rows(h=adam), INVALID, b""),
+        ("rc_rows_plan_update", lambda: plan(n_rows=20000), UNSUPPORTED, b""),
+        ("rc_rows_plan_update", lambda: plan(h=adam), INVALID, b""),
+        ("rc_segmented_update_pair", lambda: pair(dense_grad_a=p), INVALID, b"both dense gradients or none"),
+        ("rc_segmented_update_pair", lambda: pair(d=24), UNSUPPORTED, b""),
+        ("rc_segmented_update_pair", lambda: pair(h=adam), INVALID, b""),
+        ("rc_segmented_update", seg, WORKSPACE, b"workspace 0 <"),
+        ("rc_segmented_update_rows", rows, WORKSPACE, b"workspace 0 <"),
+        ("rc_rows_plan_update", plan, WORKSPACE, b"workspace 0 <"),
+        ("rc_segmented_update_pair", pair, WORKSPACE, b"workspace 0 <"),
+    ]
+    for i, (name, call, code, text) in enumerate(table):
+        got = call()
+        msg = lib.rc_last_error_string()
+        assert got == code, (i, name, got, msg)
+        assert msg.startswith(name.encode() + b":") and text in msg, (i, name, msg)
+
+
 def test_sasrec_shape_envelope(lib):
     """rc_sasrec_supported is host logic: d in {32, 64}, 1..4 blocks, heads | d, history_max <= 64 on every route; 65..128 with ONE
     block and 1 / 2 / 4 heads (the batch encoder's one-row path).  engine.sasrec_supported adds: no training-mode dropout there."""

@@ -198,7 +198,7 @@ def test_neumf_trainer_with_dropout_draws_a_new_mask_every_step(cuda, eng):
         assert_update_close(P[k].cpu().numpy(), w0, w1, what=k)
 
 
-@pytest.mark.parametrize("d,opt", [(32, "SGD"), (64, "Adam"), (128, "Adagrad"), (64, "dense")])
+@pytest.mark.parametrize("d,opt", [(d, opt) for d in (8, 16, 32, 64, 128) for opt in ("SGD", "Adam", "Adagrad", "dense")])
 def test_segmented_update_pair_equals_two_single_updates(d, opt, cuda, eng):
     """rc_segmented_update_pair (two tables with the same ids in one pass) vs two rc_segmented_update calls:
     bit-identical rows, optimizer state and dense gradients for ordinary rows (same sequential sum); hot rows take

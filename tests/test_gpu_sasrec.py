@@ -321,9 +321,21 @@ def test_sasrec_register_attention_equals_lds_attention(d, n_layers, n_heads, L,
     assert np.all(out["1"][0][lengths == 0] == 0) and np.all(out["1"][1][lengths == 0] == 0)
 
 
-@pytest.mark.parametrize("d,n_rows,n_a,C,n_b,opt", [(64, 300, 4000, 5, 9000, None), (64, 97, 2000, 4, 1500, "Adam"),
-                                                      (16, 50, 600, 3, 700, "SGD"), (128, 40, 900, 2, 0, "Adagrad"),
-                                                      (32, 1000, 3000, 6, 5000, None)])
+# every vector width with every output (dense gradient / SGD / Adam / Adagrad) on the two rows routes: the combinations the cases
+# with shapes of their own do not reach, at the smallest shapes that still have a hot row of two 256-occurrence chunks (more than
+# 256 occurrences of row 7), a row that never occurs and n_occ >= 8 n_rows; every case has its own n_rows
+_SEG_COMBOS = [(d, opt) for d in (16, 32, 64, 128, 256) for opt in (None, "SGD", "Adam", "Adagrad")]
+_ROWS_CASES = [(64, 300, 4000, 5, 9000, None), (64, 97, 2000, 4, 1500, "Adam"), (16, 50, 600, 3, 700, "SGD"),
+               (128, 40, 900, 2, 0, "Adagrad"), (32, 1000, 3000, 6, 5000, None)]
+_ROWS_CASES += [(d, 41 + 3 * i, 300, 2, 900 + 7 * i, opt) for i, (d, opt) in enumerate(_SEG_COMBOS)
+                if (d, opt) not in {(c[0], c[5]) for c in _ROWS_CASES}]
+_PLAN_CASES = [(64, 300, 700, 5, 12, None), (64, 97, 500, 4, 3, "Adam"), (16, 50, 200, 3, 4, "SGD"), (128, 40, 450, 2, 0, "Adagrad"),
+               (32, 1000, 600, 6, 9, None), (64, 8714, 1100, 100, 50, "SGD"), (64, 12288, 2100, 64, 7, None)]
+_PLAN_CASES += [(d, 41 + 3 * i, 800 + 5 * i, 2, 3, opt) for i, (d, opt) in enumerate(_SEG_COMBOS)
+                if (d, opt) not in {(c[0], c[5]) for c in _PLAN_CASES}]
+
+
+@pytest.mark.parametrize("d,n_rows,n_a,C,n_b,opt", _ROWS_CASES)
 def test_segmented_update_rows_equals_head_list_route(d, n_rows, n_a, C, n_b, opt, cuda, eng, monkeypatch):
     """rc_segmented_update_rows (one wave per table row, every row collecting many occurrences) against a float64 sum
     and against rc_segmented_update's head list: coef * src[o / C] occurrences followed by plain src2 rows, rows that
@@ -372,9 +384,7 @@ def test_segmented_update_rows_equals_head_list_route(d, n_rows, n_a, C, n_b, op
         assert_close(a, b, what=f"rows route vs head list (d={d}, opt={opt})", rtol=2e-5, atol_scale=2e-5)
 
 
-@pytest.mark.parametrize("d,n_rows,B,C,L,opt", [(64, 300, 700, 5, 12, None), (64, 97, 500, 4, 3, "Adam"), (16, 50, 200, 3, 4, "SGD"),
-                                                 (128, 40, 450, 2, 0, "Adagrad"), (32, 1000, 600, 6, 9, None),
-                                                 (64, 8714, 1100, 100, 50, "SGD"), (64, 12288, 2100, 64, 7, None)])
+@pytest.mark.parametrize("d,n_rows,B,C,L,opt", _PLAN_CASES)
 def test_rows_plan_equals_the_sorted_rows_route(d, n_rows, B, C, L, opt, cuda, eng, monkeypatch):
     """rc_rows_plan_build / rc_rows_plan_update (row bounds from a counting sort of the id tensors themselves) against the route it
     replaces: the grouping is the stable sort's (keys ascending, occurrence numbers ascending inside a row; padding slots of the
