@@ -102,12 +102,10 @@ int rc_bpr_loss_fwd_bwd(const float* pred, int B, int C, float inv_b, float* los
  *   out[i] = sum_k 0.5*((sum_f V[i,f,k])^2 - sum_f V[i,f,k]^2);   dV[i,f,k] = gout[i]*((sum_f' V[i,f',k]) - V[i,f,k]).
  * d in {16,32,64,128}.                                                                              */
 int rc_fm_second_order_fwd(const float* V, int64_t n, int F, int d, float* out, rc_stream_t stream);
-int rc_fm_second_order_bwd(const float* V, const float* gout, int64_t n, int F, int d, float* dV,
+/* add (optional, [n, F, d], may be dV itself): dV = add + d fm2 / dV in one pass -- the field vectors' gradient through the FM term on
+ * top of their gradient through the deep tower (models/context/DeepFM.py:19-28 feeds the same stacked vectors to both). */
+int rc_fm_second_order_bwd(const float* V, const float* gout, int64_t n, int F, int d, const float* add, float* dV,
                            rc_stream_t stream);
-/* dV = add + d fm2 / dV in one pass: the field vectors' gradient through the FM term on top of their gradient through the deep
- * tower (models/context/DeepFM.py:19-28 feeds the same stacked vectors to both); add [n, F, d] may be dV itself. */
-int rc_fm_second_order_bwd_add(const float* V, const float* gout, int64_t n, int F, int d, const float* add, float* dV,
-                               rc_stream_t stream);
 
 /* All F categorical field lookups of a context model in one launch (FMBase._get_embeddings_FM,
  * models/context/FM.py:44-57): tables / ids / per_row / row_offset are HOST arrays of length F holding device
@@ -115,38 +113,30 @@ int rc_fm_second_order_bwd_add(const float* V, const float* gout, int64_t n, int
  * constants.  out [B, C, F, d] = the stacked field vectors (per-row fields broadcast over the C candidates);
  * cid [B, C, F] (optional) = row_offset[f] + id, the composite row index of a virtual table that
  * concatenates all fields -- the sort key for ONE rc_sort_ids + rc_segmented_update(dense_grad) pass that
- * yields every field's dense gradient.  F <= 48.                                                          */
-int rc_gather_fields(const float* const* tables, const int64_t* const* ids, const int* per_row,
-                     const int64_t* row_offset, int F, int64_t B, int C, int d, float* out, int64_t* cid,
-                     rc_stream_t stream);
-/* rc_gather_fields for the TWO table families the FM models gather with the same ids (models/context/FM.py:44-57: the [vocab, d]
- * field vectors and the [vocab, 1] first-order weights): out [B, C, F, d] and out1 [B, C, F] in one launch.                      */
-int rc_gather_fields_pair(const float* const* tables, const float* const* tables1, const int64_t* const* ids, const int* per_row,
-                          const int64_t* row_offset, int F, int64_t B, int C, int d, float* out, float* out1, int64_t* cid,
-                          rc_stream_t stream);
-/* The same, and every composite row the batch looks up is stamped row_flags[row_offset[f] + id] = (int32) (step_dev[0] + step_add):
- * the rows of THIS step for rc_dense_update_rows_dev (row_flags [sum of vocab sizes], never reset: a stamp of an earlier step is
- * not equal to the current one; step_add = 1 when the optimizer increments its count after the backward pass).                    */
-int rc_gather_fields_pair_mark(const float* const* tables, const float* const* tables1, const int64_t* const* ids,
-                               const int* per_row, const int64_t* row_offset, int F, int64_t B, int C, int d, float* out,
-                               float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add,
-                               rc_stream_t stream);
-
-/* Field kinds of rc_gather_fields_mixed.  A numeric context feature (a name ending neither '_c' nor '_id', e.g. MIND's c_day_f) is
- * nn.Linear(1, d, bias=False) / nn.Linear(1, 1, bias=False) applied to feed_dict[f].float().unsqueeze(-1)
- * (models/context/FM.py:38-41,47-48,51-52): the value type says how the feature arrives in the feed dict.                          */
+ * yields every field's dense gradient.  F <= 48.
+ * Optional (NULL), each selecting more work of the same launch:
+ *   tables1 / out1 (together)       a second table family gathered with the same ids (models/context/FM.py:44-57: the [vocab, 1]
+ *                                   first-order weights beside the [vocab, d] field vectors): out1 [B, C, F];
+ *   row_flags / step_dev (together) every composite row the batch looks up is stamped row_flags[row_offset[f] + id] =
+ *                                   (int32) (step_dev[0] + step_add): the rows of THIS step for rc_dense_update_rows_dev (row_flags
+ *                                   [sum of vocab sizes], never reset: a stamp of an earlier step is not equal to the current one;
+ *                                   step_add = 1 when the optimizer increments its count after the backward pass);
+ *   kind                            NULL: every field a table.  Else kind[f] = RC_FIELD_IDS, or the value type of a NUMERIC context
+ *                                   feature (a name ending neither '_c' nor '_id', e.g. MIND's c_day_f), which is
+ *                                   nn.Linear(1, d, bias=False) / nn.Linear(1, 1, bias=False) applied to
+ *                                   feed_dict[f].float().unsqueeze(-1) (models/context/FM.py:38-41,47-48,51-52): ids[f] then points
+ *                                   at the feature's VALUES (float / double / int64, [B] if per_row[f] else [B, C]), tables[f] at the
+ *                                   d weights of context_embedding[f] ([d, 1] contiguous), tables1[f] at the one weight of
+ *                                   linear_embedding[f]: out[b, c, f, :] = x * W[:, 0], out1[b, c, f] = x * w1.
+ * Numeric fields own no row of the virtual concatenated table (row_offset[f] is ignored, no flag is stamped): their occurrences
+ * carry numeric_key in cid -- -1 for the groupings that skip negative keys (rc_small_row_sums, rc_bucket_plan), or the total row
+ * count, which sorts them behind every real row (rc_sort_ids).                                                                     */
 enum rc_field_kind { RC_FIELD_IDS = 0, RC_FIELD_F32 = 1, RC_FIELD_F64 = 2, RC_FIELD_I64 = 3 };
-/* rc_gather_fields_pair(_mark) for a field list that holds numeric features (FMBase._get_embeddings_FM, models/context/FM.py:44-57,
- * both branches of its conditional expressions): kind[f] = RC_FIELD_IDS as before; otherwise ids[f] points at the feature's VALUES
- * (float / double / int64, [B] if per_row[f] else [B, C]), tables[f] at the d weights of context_embedding[f] ([d, 1] contiguous),
- * tables1[f] at the one weight of linear_embedding[f]: out[b, c, f, :] = x * W[:, 0], out1[b, c, f] = x * w1.  Numeric fields own no
- * row of the virtual concatenated table (row_offset[f] is ignored, no flag is stamped): their occurrences carry numeric_key in cid
- * -- -1 for the groupings that skip negative keys (rc_small_row_sums, rc_bucket_plan), or the total row count, which sorts them
- * behind every real row (rc_sort_ids).  tables1 / out1, cid and row_flags / step_dev are optional (NULL) as in the calls above.     */
-int rc_gather_fields_mixed(const float* const* tables, const float* const* tables1, const void* const* ids, const int* per_row,
-                           const int* kind, int64_t numeric_key, const int64_t* row_offset, int F, int64_t B, int C, int d, float* out,
-                           float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add, rc_stream_t stream);
-/* rc_gather_fields_mixed with what the rest of a SMALL training step needs from the same ids, in the same launch (each optional):
+int rc_gather_fields(const float* const* tables, const float* const* tables1, const void* const* ids, const int* per_row,
+                     const int* kind, int64_t numeric_key, const int64_t* row_offset, int F, int64_t B, int C, int d, float* out,
+                     float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add, rc_stream_t stream);
+/* rc_gather_fields with what the rest of a SMALL training step needs from the same ids, in the same launch (each optional, but
+ * fm_out or plan_ws is given -- with neither this is rc_gather_fields; fm_out and fm_sum come together):
  *   fm_out [B * C], fm_sum [B * C, d]  the FM pairwise term of every row (models/context/FM.py:61; rc_fm_second_order_fwd's value bit
  *                                      for bit) and the field sum sum_f out[r, f, :] its backward needs;
  *   plan_ws                            the grouping of the composite (field, id) keys that aten::embedding_dense_backward's sort
@@ -156,7 +146,7 @@ int rc_gather_fields_mixed(const float* const* tables, const float* const* table
  *   bump                               a device counter that one thread of the launch increments (NULL: none) -- the dropout seed
  *                                      of the deep tower that runs next (utils/layers.py:201-243's nn.Dropout sites), which would
  *                                      otherwise be a one-thread launch of its own; nothing in this launch may read it (not step_dev).
- * d in {16, 32, 64, 128}; kind may be NULL (every field a table); the other arguments as rc_gather_fields_mixed.                     */
+ * d in {16, 32, 64, 128}; the other arguments as rc_gather_fields.                                                                  */
 int rc_gather_fields_fused(const float* const* tables, const float* const* tables1, const void* const* ids, const int* per_row,
                            const int* kind, int64_t numeric_key, const int64_t* row_offset, int F, int64_t B, int C, int d, float* out,
                            float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add, float* fm_out,
@@ -261,19 +251,15 @@ int rc_bprmf_fwd_bwd_update(const float* U, float* I, float* mI, float* vI,
 
 size_t rc_sort_workspace_bytes(int64_t n);
 
-/* keys_out = ids sorted ascending (as uint32), perm_out = stable sorting permutation
- * (perm_out[j] = position in `ids` of the j-th smallest).  n_rows bounds the ids
- * (only ceil(log2 n_rows) key bits are sorted).  n < 2^31, n_rows <= 2^32.            */
-int rc_sort_ids(const int64_t* ids, int64_t n, int64_t n_rows, uint32_t* keys_out,
-                uint32_t* perm_out, void* ws, size_t ws_bytes, rc_stream_t stream);
-
-/* Two id lists sorted in ONE call as the virtual concatenation [ids_a ; key_offset_b + ids_b]
- * (keys < key_range).  With key_offset_b >= every id of list a, the first n_a sorted positions are
- * list a's segment and the tail is list b's (perm values n_a .. n_a+n_b-1): a BPRMF step sorts its
- * item and user ids together and hands the two slices to rc_segmented_update(key_base, occ_base). */
-int rc_sort_ids2(const int64_t* ids_a, int64_t n_a, const int64_t* ids_b, int64_t n_b,
-                 int64_t key_offset_b, int64_t key_range, uint32_t* keys_out, uint32_t* perm_out,
-                 void* ws, size_t ws_bytes, rc_stream_t stream);
+/* keys_out = the keys sorted ascending (as uint32), perm_out = stable sorting permutation (perm_out[j] = position of the j-th
+ * smallest).  Two id lists are sorted in ONE call as the virtual concatenation [ids_a ; key_offset_b + ids_b]; key_range bounds
+ * the keys (only ceil(log2 key_range) key bits are sorted).  With key_offset_b >= every id of list a, the first n_a sorted positions
+ * are list a's segment and the tail is list b's (perm values n_a .. n_a+n_b-1): a BPRMF step sorts its item and user ids together
+ * and hands the two slices to rc_segmented_update(key_base, occ_base).  One list: ids_b = NULL, n_b = 0, key_offset_b = 0,
+ * key_range = n_rows.  n_a + n_b < 2^31, key_offset_b < key_range <= 2^32.                                                        */
+int rc_sort_ids(const int64_t* ids_a, int64_t n_a, const int64_t* ids_b, int64_t n_b,
+                int64_t key_offset_b, int64_t key_range, uint32_t* keys_out, uint32_t* perm_out,
+                void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* One pass over the sorted ids (keys/perm from rc_sort_ids) that
  *  - if single != NULL: single[o] = 1 iff occurrence o = perm[j] is the only one of its row;
@@ -306,7 +292,7 @@ size_t rc_segmented_workspace_bytes(int64_t n_occ, int d);
  * src2[o - n_split, :] instead of coef[o]*Src[srow(o)] (one source: src2 = NULL, n_split = n_occ).  SASRec updates its
  * item table from the candidates (g[b,c] * encoder output, rebuilt on the fly) and from the history positions
  * (gradient rows written by the encoder backward) in ONE pass, so the optimizer sees each row once.
- * key_base / occ_base: keys and perm may be a SLICE of a joint sort (rc_sort_ids2): the table row
+ * key_base / occ_base: keys and perm may be a SLICE of a joint sort (rc_sort_ids): the table row
  * is keys[j] - key_base, the occurrence index perm[j] - occ_base (0, 0 for a plain sort).           */
 enum rc_seg_flags { RC_SEG_SKIP_SINGLETONS = 1 };
 int rc_segmented_update(float* W, float* m, float* v, int d, const uint32_t* keys,
@@ -337,7 +323,7 @@ int rc_step_increment2(int64_t* a_dev, int64_t* b_dev, rc_stream_t stream);
 /* torch.optim.Adam over dense gradients of embedding tables whose batch touches few rows (helpers/BaseRunner.py:110-114,206 with
  * the nn.Embedding tables of models/context/FM.py:33-41 at batch_size 1024: 0.4 % of the rows have a gradient), WITHOUT a dense
  * gradient: tensor t is [n[t] / row_w[t], row_w[t]] with one int32 flag per row, and a row whose flag equals (int32) step_dev[0]
- * was looked up by this step's batch (rc_gather_fields_pair_mark); only those rows of G[t] hold (and are read for) a gradient, the
+ * was looked up by this step's batch (rc_gather_fields' row_flags); only those rows of G[t] hold (and are read for) a gradient, the
  * rest of G[t] is never read -- so nothing zero-fills it.  touched = 2: every row takes its Adam step, g = G's row where stamped
  * and 0 elsewhere (Adam still decays m, v and steps along m there): bit-identical to rc_dense_update_multi (step_dev) on a zero-filled
  * dense gradient.  touched = 0 / 1 are the two halves of that pass -- the unstamped rows with g = 0 (G[t] may be NULL) / the
@@ -403,32 +389,27 @@ int rc_rows_plan_update(float* W, float* m, float* v, int d, int64_t n_rows, int
  * a quarter of the list) selects its rows one by one -- correct, slow (the engine keeps such lists on the sort route).     */
 int rc_small_row_sums_supported(int64_t n, int64_t n_rows, int d);
 size_t rc_small_row_sums_workspace_bytes(int64_t n);
-int rc_small_row_sums(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out, void* ws,
-                      size_t ws_bytes, rc_stream_t stream);
-/* A second table gathered with the SAME ids (the [vocab, d] vectors and the [vocab, 1] first-order weights of the FM family,
- * models/context/FM.py:44-57): the row sums of another src / out pair on the grouping that the preceding rc_small_row_sums call
- * left in `ws` (same n, same n_rows, ws untouched in between) -- one launch instead of two.                                    */
-int rc_small_row_sums_again(int64_t n, int64_t n_rows, const float* src, int d, float* out, void* ws, size_t ws_bytes,
-                            rc_stream_t stream);
-/* ... and where the second table is one float wide (the [vocab, 1] first-order weights, src1 [n], out1 [n_rows]) and d >= 16, both
- * sums in the SAME launch: grouping + one row-sums kernel.                                                                     */
-int rc_small_row_sums_pair(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out,
-                           const float* src1, float* out1, void* ws, size_t ws_bytes, rc_stream_t stream);
-/* rc_small_row_sums_pair over the gradient blocks of a field list that holds numeric features (rc_gather_fields_mixed: their
- * occurrences carry id -1 and take no part in the grouping): src = gV [B * C, F, d] as n = B * C * F occurrence rows, src1 = gL, and
- * the numeric fields' weight gradients (rc_numeric_field_grads: values / per_row / kind / field / dW / dw1, HOST arrays of length
- * n_numeric <= 4) are formed by one extra workgroup each of the SAME launch.  d a multiple of 4, 16 <= d <= 128.                   */
-int rc_small_row_sums_pair_numeric(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out,
-                                   const float* src1, float* out1, const void* const* values, const int* per_row, const int* kind,
-                                   const int* field, int n_numeric, int F, int64_t B, int C, float* const* dW, float* const* dw1,
-                                   void* ws, size_t ws_bytes, rc_stream_t stream);
+/* Optional, riding in the second launch:
+ *   src1 / out1 (together; d >= 16)  a second table gathered with the SAME ids that is one float wide (the [vocab, 1] first-order
+ *                                    weights of the FM family, models/context/FM.py:44-57): src1 [n], out1 [n_rows];
+ *   n_numeric > 0 (needs src1; d >= 16, B * C * F == n)  src / src1 are the gradient blocks gV [B * C, F, d] / gL of a field list that
+ *                                    holds numeric features (rc_gather_fields' kind: their occurrences carry id -1 and take no part in
+ *                                    the grouping), whose weight gradients (rc_numeric_field_grads: values / per_row / kind / field /
+ *                                    dW / dw1, HOST arrays of length n_numeric <= 4) are formed by extra workgroups of the same launch.
+ *                                    n_numeric = 0 goes with NULL arrays; F, B, C are then not looked at.                          */
+int rc_small_row_sums(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out,
+                      const float* src1, float* out1, const void* const* values, const int* per_row, const int* kind,
+                      const int* field, int n_numeric, int F, int64_t B, int C, float* const* dW, float* const* dw1,
+                      void* ws, size_t ws_bytes, rc_stream_t stream);
 
-/* The row sums of a backward pass whose grouping rc_gather_fields_fused left in ws (no plan launch): both table families of the FM
- * models (src = gV [B * C, F, d] as n = B * C * F occurrence rows, src1 = gL [n]), with -- each optional -- the numeric fields' weight
- * gradients riding along (n_numeric > 0, arguments as rc_small_row_sums_pair_numeric) and the FM pairwise term's backward folded in
- * (fm_V != NULL: the stacked field vectors [B * C, F, d], fm_S their field sums [B * C, d], fm_g = d loss / d fm [B * C]):
- * occurrence o = r F + f then contributes src[o] + fm_g[r] * (fm_S[r] - fm_V[o]) -- rc_fm_second_order_bwd_add's rows, never
- * written out (models/context/FM.py:61, DeepFM.py:19-28); src may be NULL when nothing else consumed the field vectors.            */
+/* The second launch alone, on the grouping that a preceding rc_small_row_sums call or rc_gather_fields_fused(plan_ws) left in ws
+ * (same n, same n_rows, ws untouched in between): the row sums of another src / out pair of any supported width (src1 / out1 and
+ * everything after them NULL / 0), or of both table families of the FM models (src = gV [B * C, F, d] as n = B * C * F occurrence
+ * rows, src1 = gL [n]) with -- each optional -- the numeric fields' weight gradients riding along (n_numeric > 0, as above) and the
+ * FM pairwise term's backward folded in (fm_V, fm_S, fm_g together: the stacked field vectors [B * C, F, d], their field sums
+ * [B * C, d], d loss / d fm [B * C]): occurrence o = r F + f then contributes src[o] + fm_g[r] * (fm_S[r] - fm_V[o]) --
+ * rc_fm_second_order_bwd's rows with `add`, never written out (models/context/FM.py:61, DeepFM.py:19-28); src may be NULL when
+ * nothing else consumed the field vectors.  Numeric fields and the FM term need d >= 16 and B * C * F == n.                        */
 int rc_small_row_sums_planned(int64_t n, int64_t n_rows, const float* src, int d, float* out, const float* src1, float* out1,
                               const void* const* values, const int* per_row, const int* kind, const int* field, int n_numeric, int F,
                               int64_t B, int C, float* const* dW, float* const* dw1, const float* fm_V, const float* fm_S,
@@ -441,19 +422,16 @@ int rc_small_row_sums_planned(int64_t n, int64_t n_rows, const float* src, int d
 int rc_ctr_head_fwd_bwd(const float* bias, const float* lin, int F, const float* term1, const float* term2,
                         const int64_t* label, int64_t n, float* p, float* loss_vec, float* gz, rc_stream_t stream);
 /* rc_ctr_head_fwd_bwd for n <= 65,536 rows in ONE workgroup that also forms sums[0] = the BCE loss (mean of loss_vec, nn.BCELoss's
- * reduction, BaseModel.py:262-267) and sums[1] = sum gz (= d loss / d overall_bias) -- two launches fewer per step; and the
- * backward fan-out of the head: g [n] = gz g_loss[0], g_lin [n, F] = g broadcast over the F first-order weights of a row
- * (contiguous), g_bias [1] = sums[1] g_loss[0] (autograd's mul / sum / expand-copy in one launch).                              */
+ * reduction, BaseModel.py:262-267) and sums[1] = sum gz (= d loss / d overall_bias) -- two launches fewer per step.
+ * Optional: g_lin [n, F] / g_bias [1] (together), the backward fan-out for a seed gradient of exactly one (a whole training step
+ * calls loss.backward() on the scalar loss, helpers/BaseRunner.py:205): gz broadcast over a row's first-order weights and sum gz --
+ * rc_ctr_head_bwd's outputs for g_loss = 1, bit for bit (g itself is gz); bump, a device counter nothing in this launch reads
+ * that one thread increments (Adam's step count, read next by the update kernel).                                                */
 int rc_ctr_head_fwd_bwd_sums(const float* bias, const float* lin, int F, const float* term1, const float* term2,
-                             const int64_t* label, int64_t n, float* p, float* loss_vec, float* gz, float* sums,
-                             rc_stream_t stream);
-/* rc_ctr_head_fwd_bwd_sums that also leaves the backward fan-out for a seed gradient of exactly one (a whole training step calls
- * loss.backward() on the scalar loss, helpers/BaseRunner.py:205): g_lin [n, F] = gz broadcast over a row's first-order weights,
- * g_bias [1] = sum gz -- rc_ctr_head_bwd's outputs for g_loss = 1, bit for bit (g itself is gz) -- and optionally increments a
- * device counter nothing in this launch reads (bump, may be NULL: Adam's step count, read next by the update kernel).            */
-int rc_ctr_head_fwd_full(const float* bias, const float* lin, int F, const float* term1, const float* term2, const int64_t* label,
-                         int64_t n, float* p, float* loss_vec, float* gz, float* sums, float* g_lin, float* g_bias, int64_t* bump,
-                         rc_stream_t stream);
+                             const int64_t* label, int64_t n, float* p, float* loss_vec, float* gz, float* sums, float* g_lin,
+                             float* g_bias, int64_t* bump, rc_stream_t stream);
+/* The backward fan-out of the head for any seed: g [n] = gz g_loss[0], g_lin [n, F] = g broadcast over the F first-order weights of
+ * a row (contiguous), g_bias [1] = sums[1] g_loss[0] (autograd's mul / sum / expand-copy in one launch).                         */
 int rc_ctr_head_bwd(const float* gz, const float* sums, const float* g_loss, int64_t n, int F, float* g, float* g_lin,
                     float* g_bias, rc_stream_t stream);
 

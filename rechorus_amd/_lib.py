@@ -94,11 +94,7 @@ SIGNATURES = {
     "rc_softmax_ce_fwd_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "rc_list_loss_fwd_bwd": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "rc_fm_second_order_fwd": (_i, [_p, _i64, _i, _i, _p, _p]),
-    "rc_fm_second_order_bwd": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
-    "rc_fm_second_order_bwd_add": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
-    "rc_gather_fields": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _p, _p, _p]),
-    "rc_gather_fields_pair": (_i, [_p, _p, _p, _p, _p, _i, _i64, _i, _i, _p, _p, _p, _p]),
-    "rc_gather_fields_pair_mark": (_i, [_p, _p, _p, _p, _p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
+    "rc_fm_second_order_bwd": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
     "rc_neumf_zhead_supported": (_i, [_i, _i, _i]),
     "rc_neumf_zhead_workspace_bytes": (_sz, [_i, _i]),
     "rc_neumf_zhead_fwd_bwd": (_i, [_p, _i64, _p, _p, _i64, _p, _i, _i, _i, _i, _f, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
@@ -115,7 +111,7 @@ SIGNATURES = {
     "rc_seq_add_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _f, _p, C.c_uint32, _p, _p, _p, _p, _p, _sz, _p]),
     "rc_list_metrics_supported": (_i, [_i, _i, _i]),
     "rc_list_metrics": (_i, [_p, _p, _p, _i64, _i, _i, _p, _i, _p, _p, _p]),
-    "rc_gather_fields_mixed": (_i, [_p, _p, _p, _p, _p, _i64, _p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
+    "rc_gather_fields": (_i, [_p, _p, _p, _p, _p, _i64, _p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
     "rc_gather_fields_fused": (_i, [_p, _p, _p, _p, _p, _i64, _p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p, _p]),
     "rc_numeric_field_grads_workspace_bytes": (_sz, [_i64, _i, _i]),
     "rc_numeric_field_grads": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _sz, _p]),
@@ -138,7 +134,7 @@ SIGNATURES = {
     "rc_bprmf_fwd_bwd_update": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _hp, _p, _p, _p, _p, _p]),
     "rc_segment_heads": (_i, [_p, _p, _i64, _i, _p, _p, _p, _p]),
     "rc_sort_workspace_bytes": (_sz, [_i64]),
-    "rc_sort_ids": (_i, [_p, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "rc_sort_ids": (_i, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "rc_segmented_workspace_bytes": (_sz, [_i64, _i]),
     "rc_segmented_update": (_i, [_p, _p, _p, _i, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _i64, _i64, _hp, _p, _p,
                                  _p, _i, _p, _sz, _p]),
@@ -149,15 +145,11 @@ SIGNATURES = {
     "rc_dense_update_rows_dev": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "rc_stage_batch": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p]),
     "rc_ctr_head_fwd_bwd": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p]),
-    "rc_ctr_head_fwd_bwd_sums": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
-    "rc_ctr_head_fwd_full": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "rc_ctr_head_fwd_bwd_sums": (_i, [_p, _p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "rc_ctr_head_bwd": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p, _p]),
     "rc_small_row_sums_supported": (_i, [_i64, _i64, _i]),
     "rc_small_row_sums_workspace_bytes": (_sz, [_i64]),
-    "rc_small_row_sums": (_i, [_p, _i64, _i64, _p, _i, _p, _p, _sz, _p]),
-    "rc_small_row_sums_again": (_i, [_i64, _i64, _p, _i, _p, _p, _sz, _p]),
-    "rc_small_row_sums_pair": (_i, [_p, _i64, _i64, _p, _i, _p, _p, _p, _p, _sz, _p]),
-    "rc_small_row_sums_pair_numeric": (_i, [_p, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i, _p, _p, _p, _sz, _p]),
+    "rc_small_row_sums": (_i, [_p, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i, _p, _p, _p, _sz, _p]),
     "rc_small_row_sums_planned": (_i, [_i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "rc_segmented_rows_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "rc_segmented_update_rows": (_i, [_p, _p, _p, _i, _i64, _p, _p, _i64, _p, _p, _p, _i, _p, _i64, _hp, _p, _p, _p, _sz, _p]),
@@ -167,7 +159,6 @@ SIGNATURES = {
     "rc_rows_plan_views": (_i, [_p, _i64, _i64, _i, _p, _p, _p, _p, _p]),
     "rc_rows_plan_update": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _p, _i, _p, _i64, _hp, _p, _p, _p, _sz, _p]),
     "rc_segmented_update_pair": (_i, [_p] * 6 + [_i, _p, _p, _i64, _p, _p, _hp, _p, _p, _p, _p, _p, _sz, _p]),
-    "rc_sort_ids2": (_i, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "rc_sasrec_supported": (_i, [_i, _i, _i, _i]),
     "rc_sasrec_dense_param_count": (_i, [_i]),
     "rc_sasrec_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(kCtrOneWg) void ctr_head_sums_kernel(const float* _
     const float gp = (pi - yi) / fmaxf((1.0f - pi) * pi, 1e-12f) * inv_n;
     const float gi = gp * (1.0f - pi) * pi;
     gz[i] = gi;
-    if (g_lin)      // rc_ctr_head_fwd_full: the backward fan-out for a seed gradient of exactly 1 (gz * 1.0f is gz)
+    if (g_lin)      // the backward fan-out for a seed gradient of exactly 1 (gz * 1.0f is gz)
       for (int f = 0; f < F; ++f) g_lin[i * F + f] = gi;
     sl_loss += li;
     sl_gz += gi;
@@ -221,26 +221,16 @@ __global__ __launch_bounds__(kBlock) void ctr_head_bwd_kernel(const float* __res
 
 using namespace rc;
 
+/* g_lin / g_bias (together) and bump are optional: the backward fan-out of a seed gradient of exactly one -- g_lin [n, F] = gz
+ * broadcast over a row's first-order weights, g_bias [1] = sum gz (rc_ctr_head_bwd's outputs for g_loss = 1, bit for bit; g itself
+ * is gz) -- and a device counter that nothing in this launch reads: a whole training step that seeds loss.backward() with 1 needs
+ * no rc_ctr_head_bwd launch and no launch for Adam's step count. */
 extern "C" int rc_ctr_head_fwd_bwd_sums(const float* bias, const float* lin, int F, const float* term1, const float* term2,
-                                        const int64_t* label, int64_t n, float* p, float* loss_vec, float* gz, float* sums,
-                                        rc_stream_t stream) {
-  RC_REQUIRE(bias && lin && label && p && loss_vec && gz && sums, "rc_ctr_head_fwd_bwd_sums: null pointer");
+                                        const int64_t* label, int64_t n, float* p, float* loss_vec, float* gz, float* sums, float* g_lin,
+                                        float* g_bias, int64_t* bump, rc_stream_t stream) {
   RC_REQUIRE(n > 0 && n <= 65536 && F >= 1, "rc_ctr_head_fwd_bwd_sums: n=%lld (1 .. 65,536 rows: one workgroup) F=%d", (long long)n, F);
-  hipLaunchKernelGGL(ctr_head_sums_kernel, dim3(1), dim3(kCtrOneWg), 0, as_stream(stream), bias, lin, F, term1, term2, label, n,
-                     1.0f / (float)n, p, loss_vec, gz, sums, (float*)nullptr, (float*)nullptr, (int64_t*)nullptr);
-  RC_LAUNCH_CHECK();
-  return RC_OK;
-}
-
-/* rc_ctr_head_fwd_bwd_sums that also leaves the backward fan-out of a seed gradient of exactly one -- g_lin [n, F] = gz broadcast
- * over a row's first-order weights, g_bias [1] = sum gz (rc_ctr_head_bwd's outputs for g_loss = 1, bit for bit; g itself is gz) --
- * and, optionally, increments a device counter that nothing in this launch reads (bump, may be NULL): a whole training step that
- * seeds loss.backward() with 1 needs no rc_ctr_head_bwd launch and no launch for Adam's step count. */
-extern "C" int rc_ctr_head_fwd_full(const float* bias, const float* lin, int F, const float* term1, const float* term2,
-                                    const int64_t* label, int64_t n, float* p, float* loss_vec, float* gz, float* sums, float* g_lin,
-                                    float* g_bias, int64_t* bump, rc_stream_t stream) {
-  RC_REQUIRE(bias && lin && label && p && loss_vec && gz && sums && g_lin && g_bias, "rc_ctr_head_fwd_full: null pointer");
-  RC_REQUIRE(n > 0 && n <= 65536 && F >= 1, "rc_ctr_head_fwd_full: n=%lld (1 .. 65,536 rows: one workgroup) F=%d", (long long)n, F);
+  RC_REQUIRE((g_lin == nullptr) == (g_bias == nullptr), "rc_ctr_head_fwd_bwd_sums: g_lin and g_bias come together");
+  RC_REQUIRE(bias && lin && label && p && loss_vec && gz && sums, "rc_ctr_head_fwd_bwd_sums: null pointer");
   hipLaunchKernelGGL(ctr_head_sums_kernel, dim3(1), dim3(kCtrOneWg), 0, as_stream(stream), bias, lin, F, term1, term2, label, n,
                      1.0f / (float)n, p, loss_vec, gz, sums, g_lin, g_bias, bump);
   RC_LAUNCH_CHECK();
@@ -297,29 +287,16 @@ extern "C" int rc_fm_second_order_fwd(const float* V, int64_t n, int F, int d, f
   return RC_OK;
 }
 
-static int fm_second_order_bwd_impl(const float* V, const float* gout, int64_t n, int F, int d, const float* add, float* dV,
-                                    rc_stream_t stream);
-
-extern "C" int rc_fm_second_order_bwd(const float* V, const float* gout, int64_t n, int F, int d, float* dV,
+// add (optional; may be dV itself): dV = add + d fm2 / dV, the field vectors' gradient through the FM term on top of their gradient
+// through another consumer (the deep tower of DeepFM, models/context/DeepFM.py:19-28) in one pass -- autograd would form the two and add them
+extern "C" int rc_fm_second_order_bwd(const float* V, const float* gout, int64_t n, int F, int d, const float* add, float* dV,
                                       rc_stream_t stream) {
-  return fm_second_order_bwd_impl(V, gout, n, F, d, nullptr, dV, stream);
-}
-
-// dV = add + d fm2 / dV: the field vectors' gradient through the FM term on top of their gradient through another consumer
-// (the deep tower of DeepFM, models/context/DeepFM.py:19-28) in one pass -- autograd would form the two and add them
-extern "C" int rc_fm_second_order_bwd_add(const float* V, const float* gout, int64_t n, int F, int d, const float* add, float* dV,
-                                          rc_stream_t stream) {
-  RC_REQUIRE(add != nullptr && reinterpret_cast<uintptr_t>(add) % 16 == 0, "rc_fm_second_order_bwd_add: add is null / not 16-byte aligned");
-  return fm_second_order_bwd_impl(V, gout, n, F, d, add, dV, stream);
-}
-
-static int fm_second_order_bwd_impl(const float* V, const float* gout, int64_t n, int F, int d, const float* add, float* dV,
-                                    rc_stream_t stream) {
   if (n == 0) return RC_OK;
   RC_REQUIRE(V && gout && dV, "rc_fm_second_order_bwd: null pointer");
   RC_REQUIRE(n > 0 && F >= 1, "rc_fm_second_order_bwd: bad shape n=%lld F=%d", (long long)n, F);
   RC_REQUIRE(reinterpret_cast<uintptr_t>(V) % 16 == 0 && reinterpret_cast<uintptr_t>(dV) % 16 == 0,
              "rc_fm_second_order_bwd: V and dV must be 16-byte aligned");
+  RC_REQUIRE(reinterpret_cast<uintptr_t>(add) % 16 == 0, "rc_fm_second_order_bwd: add must be 16-byte aligned");
   hipStream_t s = as_stream(stream);
   auto blocks = [&](int dd) { return (unsigned)((n + (kBlock / (dd / 4)) - 1) / (kBlock / (dd / 4))); };
   bool generic = false;
@@ -357,8 +334,8 @@ struct FieldArgs {
   const int64_t* ids[kMaxFields];
   int64_t row_offset[kMaxFields];
   int per_row[kMaxFields];  // 1: ids [B] (user / situation field, broadcast over candidates); 0: ids [B, C]
-  const float* table1[kMaxFields];   // rc_gather_fields_pair: the [vocab, 1] tables gathered with the same ids (FM.py:44-57), else unused
-  int kind[kMaxFields];     // rc_gather_fields_mixed: RC_FIELD_IDS, or the value type of a numeric field (ids[f] then points at the values)
+  const float* table1[kMaxFields];   // tables1: the [vocab, 1] tables gathered with the same ids (FM.py:44-57), else unused
+  int kind[kMaxFields];     // RC_FIELD_IDS, or the value type of a numeric field (ids[f] then points at the values)
   int64_t numeric_key;      // what a numeric field's occurrences carry in cid (they are no rows of the virtual table)
   int F;
   int C;
@@ -385,7 +362,7 @@ __device__ __forceinline__ void gather_fields_body(const FieldArgs& a, float* __
                                                    float* __restrict__ fm_sum, unsigned block, unsigned n_blocks, int n_threads) {
   static_assert(FMQ == 0 || VEC == 4, "the FM term rides with the float4 tiling only");
   const int dq = FMQ > 0 ? FMQ : a.d / VEC;
-  // rc_gather_fields_pair_mark: every looked-up composite row is stamped with the step's number (the row-flagged dense update,
+  // row_flags given: every looked-up composite row is stamped with the step's number (the row-flagged dense update,
   // dense_opt.hip, tells the rows of this batch from the rest by it; equal stamps from duplicate ids race benignly)
   const int32_t gen = row_flags ? (int32_t)(*step_dev + step_add) : 0;
   const int64_t total = a.n * dq;
@@ -587,9 +564,7 @@ static int gather_fields_fused_launch(const FieldArgs& a, bool vec, bool mixed, 
                                       const int64_t* step_dev, int step_add, float* fm_out, float* fm_sum, void* plan_ws,
                                       size_t plan_ws_bytes, int64_t* bump, rc_stream_t stream) {
   const int d = a.d;
-  RC_REQUIRE(bump == nullptr || bump != step_dev, "rc_gather_fields_fused: the gather reads step_dev, it cannot be the counter to increment");
   RC_REQUIRE(vec && (d == 16 || d == 32 || d == 64 || d == 128), "rc_gather_fields_fused: d = %d (16 / 32 / 64 / 128, 16-byte aligned tables and output)", d);
-  RC_REQUIRE((fm_out == nullptr) == (fm_sum == nullptr), "rc_gather_fields_fused: the FM term and the field sums come together");
   RC_REQUIRE(fm_sum == nullptr || reinterpret_cast<uintptr_t>(fm_sum) % 16 == 0, "rc_gather_fields_fused: fm_sum must be 16-byte aligned");
   const int64_t n_keys = a.n * a.F;
   SmallPlanArgs p;
@@ -625,30 +600,30 @@ static int gather_fields_fused_launch(const FieldArgs& a, bool vec, bool mixed, 
 #undef RC_GF
 }
 
-static int gather_fields_impl(const float* const* tables, const float* const* tables1, const void* const* ids, const int* per_row,
-                              const int* kind, int64_t numeric_key, const int64_t* row_offset, int F, int64_t B, int C, int d, float* out,
-                              float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add, rc_stream_t stream,
-                              float* fm_out = nullptr, float* fm_sum = nullptr, void* plan_ws = nullptr, size_t plan_ws_bytes = 0,
-                              int64_t* bump = nullptr) {
+// the argument checks and the FieldArgs of both gather entry points; what the fused one adds is null for the plain one
+static int gather_fields_impl(const char* who, const float* const* tables, const float* const* tables1, const void* const* ids,
+                              const int* per_row, const int* kind, int64_t numeric_key, const int64_t* row_offset, int F, int64_t B, int C,
+                              int d, float* out, float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add,
+                              float* fm_out, float* fm_sum, void* plan_ws, size_t plan_ws_bytes, int64_t* bump, rc_stream_t stream) {
   if (B == 0) return RC_OK;
-  RC_REQUIRE((row_flags == nullptr) == (step_dev == nullptr), "rc_gather_fields_pair_mark: the row flags and the step count come together");
-  RC_REQUIRE(tables && ids && per_row && row_offset && out, "rc_gather_fields: null pointer");
-  RC_REQUIRE((tables1 == nullptr) == (out1 == nullptr), "rc_gather_fields_pair: the second table family and its output come together");
-  RC_REQUIRE(F >= 1 && F <= kMaxFields, "rc_gather_fields: F must be in [1, %d], got %d", kMaxFields, F);
-  RC_REQUIRE(B > 0 && C >= 1 && d >= 1, "rc_gather_fields: bad shape B=%lld C=%d d=%d", (long long)B, C, d);
+  RC_REQUIRE((row_flags == nullptr) == (step_dev == nullptr), "%s: the row flags and the step count come together", who);
+  RC_REQUIRE(tables && ids && per_row && row_offset && out, "%s: null pointer", who);
+  RC_REQUIRE((tables1 == nullptr) == (out1 == nullptr), "%s: the second table family and its output come together", who);
+  RC_REQUIRE(F >= 1 && F <= kMaxFields, "%s: F must be in [1, %d], got %d", who, kMaxFields, F);
+  RC_REQUIRE(B > 0 && C >= 1 && d >= 1, "%s: bad shape B=%lld C=%d d=%d", who, (long long)B, C, d);
   FieldArgs a;
   memset(&a, 0, sizeof(a));
   bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
   bool mixed = false;
   for (int f = 0; f < F; ++f) {
-    RC_REQUIRE(tables[f] && ids[f] && (!tables1 || tables1[f]), "rc_gather_fields: null table / ids for field %d", f);
+    RC_REQUIRE(tables[f] && ids[f] && (!tables1 || tables1[f]), "%s: null table / ids for field %d", who, f);
     a.table[f] = tables[f];
     a.table1[f] = tables1 ? tables1[f] : nullptr;
     a.ids[f] = static_cast<const int64_t*>(ids[f]);
     a.row_offset[f] = row_offset[f];
     a.per_row[f] = per_row[f];
     a.kind[f] = kind ? kind[f] : RC_FIELD_IDS;
-    RC_REQUIRE(a.kind[f] >= RC_FIELD_IDS && a.kind[f] <= RC_FIELD_I64, "rc_gather_fields_mixed: kind[%d] = %d is no rc_field_kind", f, a.kind[f]);
+    RC_REQUIRE(a.kind[f] >= RC_FIELD_IDS && a.kind[f] <= RC_FIELD_I64, "%s: kind[%d] = %d is no rc_field_kind", who, f, a.kind[f]);
     mixed = mixed || a.kind[f] != RC_FIELD_IDS;
     vec = vec && reinterpret_cast<uintptr_t>(tables[f]) % 16 == 0;
   }
@@ -666,51 +641,33 @@ static int gather_fields_impl(const float* const* tables, const float* const* ta
   return RC_OK;
 }
 
-extern "C" int rc_gather_fields(const float* const* tables, const int64_t* const* ids, const int* per_row,
-                                const int64_t* row_offset, int F, int64_t B, int C, int d, float* out, int64_t* cid,
+/* tables1 / out1 (a second, one-float-wide table family gathered with the same ids), kind (null: every field a table), cid and
+ * row_flags / step_dev (the stamps of this step's rows) are optional. */
+extern "C" int rc_gather_fields(const float* const* tables, const float* const* tables1, const void* const* ids, const int* per_row,
+                                const int* kind, int64_t numeric_key, const int64_t* row_offset, int F, int64_t B, int C, int d,
+                                float* out, float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add,
                                 rc_stream_t stream) {
-  return gather_fields_impl(tables, nullptr, reinterpret_cast<const void* const*>(ids), per_row, nullptr, -1, row_offset, F, B, C, d, out, nullptr, cid, nullptr, nullptr, 0, stream);
+  return gather_fields_impl("rc_gather_fields", tables, tables1, ids, per_row, kind, numeric_key, row_offset, F, B, C, d, out, out1, cid,
+                            row_flags, step_dev, step_add, nullptr, nullptr, nullptr, 0, nullptr, stream);
 }
 
-extern "C" int rc_gather_fields_pair(const float* const* tables, const float* const* tables1, const int64_t* const* ids, const int* per_row,
-                                     const int64_t* row_offset, int F, int64_t B, int C, int d, float* out, float* out1, int64_t* cid,
-                                     rc_stream_t stream) {
-  RC_REQUIRE(tables1 && out1, "rc_gather_fields_pair: null pointer");
-  return gather_fields_impl(tables, tables1, reinterpret_cast<const void* const*>(ids), per_row, nullptr, -1, row_offset, F, B, C, d, out, out1, cid, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int rc_gather_fields_pair_mark(const float* const* tables, const float* const* tables1, const int64_t* const* ids,
-                                          const int* per_row, const int64_t* row_offset, int F, int64_t B, int C, int d, float* out,
-                                          float* out1, int64_t* cid, int32_t* row_flags, const int64_t* step_dev, int step_add,
-                                          rc_stream_t stream) {
-  RC_REQUIRE(tables1 && out1 && row_flags && step_dev, "rc_gather_fields_pair_mark: null pointer");
-  return gather_fields_impl(tables, tables1, reinterpret_cast<const void* const*>(ids), per_row, nullptr, -1, row_offset, F, B, C, d, out, out1, cid, row_flags, step_dev, step_add, stream);
-}
-
-extern "C" int rc_gather_fields_mixed(const float* const* tables, const float* const* tables1, const void* const* ids,
-                                      const int* per_row, const int* kind, int64_t numeric_key, const int64_t* row_offset, int F,
-                                      int64_t B, int C, int d, float* out, float* out1, int64_t* cid, int32_t* row_flags,
-                                      const int64_t* step_dev, int step_add, rc_stream_t stream) {
-  RC_REQUIRE(kind, "rc_gather_fields_mixed: null pointer");
-  return gather_fields_impl(tables, tables1, ids, per_row, kind, numeric_key, row_offset, F, B, C, d, out, out1, cid, row_flags, step_dev,
-                            step_add, stream);
-}
-
-/* rc_gather_fields_mixed with what the rest of a small step needs from the same pass (each part optional):
+/* rc_gather_fields with what the rest of a small step needs from the same pass (each part optional, at least one of the first two):
  *   fm_out [B * C], fm_sum [B * C, d]   the FM pairwise term of every row (rc_fm_second_order_fwd's value, bit for bit) and the field
  *                                       sum its backward needs -- no second pass over the stacked block;
  *   plan_ws                             the grouping of the composite keys (rc_small_row_sums' first launch) by 128 workgroups
  *                                       beside the gather's, left where rc_small_row_sums_planned reads it.
  *   bump                                a device counter incremented by one thread of the launch (nothing in it may read it).
- * d in {16, 32, 64, 128}; the plan: B * C * F <= 32,768 keys.  kind may be null (every field a table). */
+ * d in {16, 32, 64, 128}; the plan: B * C * F <= 32,768 keys. */
 extern "C" int rc_gather_fields_fused(const float* const* tables, const float* const* tables1, const void* const* ids,
                                       const int* per_row, const int* kind, int64_t numeric_key, const int64_t* row_offset, int F,
                                       int64_t B, int C, int d, float* out, float* out1, int64_t* cid, int32_t* row_flags,
                                       const int64_t* step_dev, int step_add, float* fm_out, float* fm_sum, void* plan_ws,
                                       size_t plan_ws_bytes, int64_t* bump, rc_stream_t stream) {
   RC_REQUIRE(fm_out != nullptr || plan_ws != nullptr, "rc_gather_fields_fused: neither the FM term nor the plan was asked for");
-  return gather_fields_impl(tables, tables1, ids, per_row, kind, numeric_key, row_offset, F, B, C, d, out, out1, cid, row_flags, step_dev,
-                            step_add, stream, fm_out, fm_sum, plan_ws, plan_ws_bytes, bump);
+  RC_REQUIRE((fm_out == nullptr) == (fm_sum == nullptr), "rc_gather_fields_fused: the FM term and the field sums come together");
+  RC_REQUIRE(bump == nullptr || bump != step_dev, "rc_gather_fields_fused: the gather reads step_dev, it cannot be the counter to increment");
+  return gather_fields_impl("rc_gather_fields_fused", tables, tables1, ids, per_row, kind, numeric_key, row_offset, F, B, C, d, out, out1, cid,
+                            row_flags, step_dev, step_add, fm_out, fm_sum, plan_ws, plan_ws_bytes, bump, stream);
 }
 
 // ---- weight gradients of the numeric fields ---------------------------------------------------------------------------

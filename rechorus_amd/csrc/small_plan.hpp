@@ -36,7 +36,7 @@ constexpr int kSmallCapBig = 8192, kSmallWaveCapBig = 1024;
 constexpr size_t kSmallLdsBytesBig = small_lds_bytes(kSmallCapBig, kSmallWaveCapBig);
 
 // a key no row can have (n_rows < 2^32 - 1): an id of -1 narrows to it and takes no part in the grouping -- the occurrences of a
-// context model's numeric fields, which own no row of the virtual concatenated table (rc_gather_fields_mixed)
+// context model's numeric fields, which own no row of the virtual concatenated table (rc_gather_fields' kind)
 constexpr uint32_t kSmallSkipKey = 0xFFFFFFFFu;
 
 struct SmallCnt { uint32_t rows_a, rows_b, occ, pad; };   // per plan workgroup

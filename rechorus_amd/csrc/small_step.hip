@@ -204,7 +204,7 @@ struct SmallSumArgs {
   int d;
   const float* src1;         // optional second, ONE-float-wide gradient of the same occurrences ([n]) and its table [n_rows]:
   float* out1;               // the [vocab, 1] first-order weights of the FM family ride along with the [vocab, d] vectors
-  // rc_small_row_sums_pair_numeric: the weight gradients of up to kSmallNumeric numeric fields (numeric_grads.hpp) by one extra
+  // n_numeric > 0: the weight gradients of up to kSmallNumeric numeric fields (numeric_grads.hpp) by one extra
   // workgroup each behind the row workgroups -- independent work that would otherwise be a launch of its own (~13 us of a replayed
   // DeepFM step at B = 1,024 on MIND's field set)
   uint32_t blocks_rows;      // workgroups of the row sums (the grid may be longer)
@@ -489,31 +489,56 @@ extern "C" size_t rc_small_row_sums_workspace_bytes(int64_t n) {
          align_up((size_t)kSmallPlanWgs * (size_t)n * sizeof(uint32_t), 256) + align_up((size_t)kSmallPlanWgs * sizeof(SmallCnt), 256);
 }
 
-struct SmallNumericCall {     // host-side description of the numeric fields that ride in the launch
-  int n_numeric;
-  NumericSlot num[kSmallNumeric];
-  NumericCommon c;
-};
-
-static int small_row_sums_impl(bool build_plan, const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out, void* ws,
-                               size_t ws_bytes, rc_stream_t stream, const float* src1 = nullptr, float* out1 = nullptr,
-                               const SmallNumericCall* numeric = nullptr, const FmTap* fm = nullptr) {
+// Both entry points: the argument checks, [the plan launch,] the row-sums launch.  Everything that inspects only the arguments
+// comes before the workspace-size check, and that before the device's own answer (rc_small_row_sums_supported).
+static int small_row_sums_impl(const char* who, bool build_plan, const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d,
+                               float* out, const float* src1, float* out1, const void* const* values, const int* per_row, const int* kind,
+                               const int* field, int n_numeric, int F, int64_t B, int C, float* const* dW, float* const* dw1,
+                               const float* fm_V, const float* fm_S, const float* fm_g, void* ws, size_t ws_bytes, rc_stream_t stream) {
   if (n == 0) return RC_OK;
-  RC_REQUIRE((ids || !build_plan) && (src || fm) && out && ws, "rc_small_row_sums: null pointer");
-  if (!rc_small_row_sums_supported(n, n_rows, d))
-    return fail(RC_ERR_UNSUPPORTED, "rc_small_row_sums: n=%lld (<= %d), n_rows=%lld, d=%d (1..4, 16, 32, 64, 128) not covered",
-                (long long)n, kSmallMaxKeys, (long long)n_rows, d);
+  const bool fm = fm_V != nullptr;
+  RC_REQUIRE((fm_V == nullptr) == (fm_S == nullptr) && (fm_V == nullptr) == (fm_g == nullptr), "%s: fm_V, fm_S and fm_g come together", who);
+  RC_REQUIRE((ids || !build_plan) && (src || fm) && out && ws, "%s: null pointer", who);
+  RC_REQUIRE((src1 == nullptr) == (out1 == nullptr) && (src1 == nullptr || d >= 16), "%s: the one-float-wide pair (src1 / out1 together) rides with d >= 16 only", who);
+  RC_REQUIRE(d <= 4 || aligned16(src, out), "%s: src / out must be 16-byte aligned", who);
+  SmallSumArgs a;
+  a.src = src; a.out = out; a.d = d; a.src1 = src1; a.out1 = out1; a.n = (uint32_t)n;
+  a.n_numeric = 0;
+  memset(&a.numc, 0, sizeof(a.numc));
+  memset(&a.fm, 0, sizeof(a.fm));
+  if (n_numeric != 0 || fm) {     // what reads src as the [B * C, F, d] gradient block of a field list
+    RC_REQUIRE(n_numeric >= 0 && n_numeric <= kSmallNumeric && n_numeric <= F && F >= 1 && F <= kMaxFields,
+               "%s: %d numeric fields (0 .. %d) of F = %d", who, n_numeric, kSmallNumeric, F);
+    RC_REQUIRE(B >= 1 && C >= 1 && B * C * F == n && d % 4 == 0 && d >= 16, "%s: bad shape B=%lld C=%d F=%d n=%lld d=%d (numeric fields / FM term)",
+               who, (long long)B, C, F, (long long)n, d);
+  }
+  if (fm) {
+    RC_REQUIRE(aligned16(fm_V, fm_S), "%s: the FM term's backward needs 16-byte aligned V [n / F, F, d] and S [n / F, d]", who);
+    a.fm.V = fm_V; a.fm.S = fm_S; a.fm.g = fm_g; a.fm.F = (uint32_t)F; a.fm.magic_F = small_div_magic((uint32_t)F);
+  }
+  if (n_numeric > 0) {            // their weight gradients (rc_numeric_field_grads) ride in the row-sums launch
+    RC_REQUIRE(src1 && values && per_row && kind && field && dW && dw1, "%s: null pointer (numeric fields)", who);
+    a.n_numeric = n_numeric;
+    for (int j = 0; j < n_numeric; ++j) {
+      RC_REQUIRE(values[j] && dW[j] && dw1[j] && field[j] >= 0 && field[j] < F && kind[j] >= RC_FIELD_F32 && kind[j] <= RC_FIELD_I64,
+                 "%s: bad numeric field %d", who, j);
+      a.num[j].values = values[j]; a.num[j].dW = dW[j]; a.num[j].dw1 = dw1[j];
+      a.num[j].kind = kind[j]; a.num[j].per_row = per_row[j]; a.num[j].field = field[j];
+    }
+    a.numc.gV = src; a.numc.gL = src1; a.numc.part = nullptr; a.numc.n = B * C; a.numc.n_numeric = n_numeric; a.numc.F = F; a.numc.C = C;
+    a.numc.d = d; a.numc.fm = a.fm;
+  }
   if (ws_bytes < rc_small_row_sums_workspace_bytes(n))
-    return fail(RC_ERR_WORKSPACE, "rc_small_row_sums: workspace %zu < %zu", ws_bytes, rc_small_row_sums_workspace_bytes(n));
-  RC_REQUIRE(d <= 4 || aligned16(src, out),
-             "rc_small_row_sums: src / out must be 16-byte aligned");
-  RC_REQUIRE(fm == nullptr || (d >= 16 && fm->V && fm->S && fm->g && fm->F >= 1 && n % fm->F == 0 && aligned16(fm->V, fm->S)),
-             "rc_small_row_sums_planned: the FM term's backward needs d >= 16, 16-byte aligned V [n / F, F, d] and S [n / F, d], and g [n / F]");
+    return fail(RC_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, rc_small_row_sums_workspace_bytes(n));
+  if (!rc_small_row_sums_supported(n, n_rows, d))
+    return fail(RC_ERR_UNSUPPORTED, "%s: n=%lld (<= %d), n_rows=%lld, d=%d (1..4, 16, 32, 64, 128) not covered",
+                who, (long long)n, kSmallMaxKeys, (long long)n_rows, d);
   hipStream_t s = as_stream(stream);
   Carver cv(ws);
   rc_plan_row* rows = cv.take<rc_plan_row>((size_t)kSmallPlanWgs * (size_t)n);
   uint32_t* occ = cv.take<uint32_t>((size_t)kSmallPlanWgs * (size_t)n);
   SmallCnt* cnt = cv.take<SmallCnt>(kSmallPlanWgs);
+  a.rows = rows; a.occ = occ; a.cnt = cnt;
   if (build_plan) {
     SmallPlanArgs p;
     memset(&p, 0, sizeof(p));
@@ -533,21 +558,6 @@ static int small_row_sums_impl(bool build_plan, const int64_t* ids, int64_t n, i
     hipLaunchKernelGGL(small_plan_kernel, dim3(kSmallPlanWgs), dim3(kSmallThreads), kSmallLdsBytesBig, s, p);
     RC_LAUNCH_CHECK();
   }
-  SmallSumArgs a;
-  a.rows = rows; a.occ = occ; a.cnt = cnt; a.n = (uint32_t)n; a.src = src; a.out = out; a.d = d;
-  a.src1 = src1; a.out1 = out1;
-  a.n_numeric = 0;
-  memset(&a.numc, 0, sizeof(a.numc));
-  memset(&a.fm, 0, sizeof(a.fm));
-  if (fm != nullptr) a.fm = *fm;
-  RC_REQUIRE((src1 == nullptr) == (out1 == nullptr) && (src1 == nullptr || d >= 16), "rc_small_row_sums_pair: the one-float-wide pair rides with d >= 16 only");
-  RC_REQUIRE(numeric == nullptr || d >= 16, "rc_small_row_sums_pair_numeric: the numeric fields ride with the d >= 16 kernels only");
-  if (numeric != nullptr) {
-    a.n_numeric = numeric->n_numeric;
-    for (int j = 0; j < numeric->n_numeric; ++j) a.num[j] = numeric->num[j];
-    a.numc = numeric->c;
-    a.numc.fm = a.fm;
-  }
   if (d <= 4) {
     unsigned blocks = (unsigned)((n + kBlock / 64 - 1) / (kBlock / 64));
     if (blocks > 1024u) blocks = 1024u;
@@ -558,8 +568,8 @@ static int small_row_sums_impl(bool build_plan, const int64_t* ids, int64_t n, i
     if (blocks > 2048u) blocks = 2048u;
     a.blocks_rows = blocks;
     const unsigned grid = blocks + (unsigned)(a.n_numeric * kSmallNumericSplits);     // the numeric fields' workgroups come last: the rows' are dispatched first
-    RC_TRY((dispatch_or_fail<16, 32, 64, 128>("rc_small_row_sums", "d", d, [&](auto D) -> int {
-      if (fm != nullptr) hipLaunchKernelGGL((small_row_sums_kernel<D(), true>), dim3(grid), dim3(kBlock), 0, s, a);
+    RC_TRY((dispatch_or_fail<16, 32, 64, 128>(who, "d", d, [&](auto D) -> int {
+      if (fm) hipLaunchKernelGGL((small_row_sums_kernel<D(), true>), dim3(grid), dim3(kBlock), 0, s, a);
       else hipLaunchKernelGGL((small_row_sums_kernel<D(), false>), dim3(grid), dim3(kBlock), 0, s, a);
       return RC_OK;
     })));
@@ -568,76 +578,25 @@ static int small_row_sums_impl(bool build_plan, const int64_t* ids, int64_t n, i
   return RC_OK;
 }
 
-extern "C" int rc_small_row_sums(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out, void* ws,
-                                 size_t ws_bytes, rc_stream_t stream) {
-  return small_row_sums_impl(true, ids, n, n_rows, src, d, out, ws, ws_bytes, stream);
+/* Plan launch + row-sums launch.  src1 / out1 (the one-float-wide second table, d >= 16) are optional; so are the numeric fields of
+ * the gradient blocks src = gV [B * C, F, d] / src1 = gL (n_numeric = 0 goes with null arrays; F, B, C are then not looked at). */
+extern "C" int rc_small_row_sums(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out,
+                                 const float* src1, float* out1, const void* const* values, const int* per_row, const int* kind,
+                                 const int* field, int n_numeric, int F, int64_t B, int C, float* const* dW, float* const* dw1,
+                                 void* ws, size_t ws_bytes, rc_stream_t stream) {
+  return small_row_sums_impl("rc_small_row_sums", true, ids, n, n_rows, src, d, out, src1, out1, values, per_row, kind, field, n_numeric, F,
+                             B, C, dW, dw1, nullptr, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
-extern "C" int rc_small_row_sums_again(int64_t n, int64_t n_rows, const float* src, int d, float* out, void* ws, size_t ws_bytes,
-                                       rc_stream_t stream) {
-  return small_row_sums_impl(false, nullptr, n, n_rows, src, d, out, ws, ws_bytes, stream);
-}
-
-extern "C" int rc_small_row_sums_pair(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out,
-                                      const float* src1, float* out1, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(src1 && out1, "rc_small_row_sums_pair: null pointer");
-  return small_row_sums_impl(true, ids, n, n_rows, src, d, out, ws, ws_bytes, stream, src1, out1);
-}
-
-/* rc_small_row_sums_pair with the weight gradients of the numeric fields of the same gradient blocks (rc_numeric_field_grads)
- * riding in the row-sums launch: src = gV [rows, F, d] seen as n = rows * F occurrence rows, src1 = gL [rows * F]. */
-extern "C" int rc_small_row_sums_pair_numeric(const int64_t* ids, int64_t n, int64_t n_rows, const float* src, int d, float* out,
-                                              const float* src1, float* out1, const void* const* values, const int* per_row,
-                                              const int* kind, const int* field, int n_numeric, int F, int64_t B, int C,
-                                              float* const* dW, float* const* dw1, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(src1 && out1 && values && per_row && kind && field && dW && dw1, "rc_small_row_sums_pair_numeric: null pointer");
-  RC_REQUIRE(n_numeric >= 1 && n_numeric <= kSmallNumeric && n_numeric <= F && F <= kMaxFields,
-             "rc_small_row_sums_pair_numeric: %d numeric fields (1 .. %d) of F = %d", n_numeric, kSmallNumeric, F);
-  RC_REQUIRE(B >= 1 && C >= 1 && B * C * F == n && d % 4 == 0 && d <= 4 * kBlock, "rc_small_row_sums_pair_numeric: bad shape B=%lld C=%d F=%d n=%lld d=%d",
-             (long long)B, C, F, (long long)n, d);
-  SmallNumericCall nc;
-  memset(&nc, 0, sizeof(nc));
-  nc.n_numeric = n_numeric;
-  for (int j = 0; j < n_numeric; ++j) {
-    RC_REQUIRE(values[j] && dW[j] && dw1[j] && field[j] >= 0 && field[j] < F && kind[j] >= RC_FIELD_F32 && kind[j] <= RC_FIELD_I64,
-               "rc_small_row_sums_pair_numeric: bad numeric field %d", j);
-    nc.num[j].values = values[j]; nc.num[j].dW = dW[j]; nc.num[j].dw1 = dw1[j];
-    nc.num[j].kind = kind[j]; nc.num[j].per_row = per_row[j]; nc.num[j].field = field[j];
-  }
-  nc.c.gV = src; nc.c.gL = src1; nc.c.part = nullptr; nc.c.n = B * C; nc.c.n_numeric = n_numeric; nc.c.F = F; nc.c.C = C; nc.c.d = d;
-  return small_row_sums_impl(true, ids, n, n_rows, src, d, out, ws, ws_bytes, stream, src1, out1, &nc);
-}
-
-/* The row sums of a backward pass whose grouping rc_gather_fields_fused already left in `ws` (no plan launch), for both table
- * families of the FM models, with -- each optional -- the numeric fields' weight gradients riding along (n_numeric > 0, as
- * rc_small_row_sums_pair_numeric) and the FM pairwise term's backward folded in (fm_V != null): occurrence o = r F + f then
- * contributes  src[o] + fm_g[r] * (fm_S[r] - fm_V[o])  (rc_fm_second_order_bwd_add's rows, never written out; src may be null:
- * no other consumer of the field vectors). */
+/* The row-sums launch alone, on a grouping that rc_small_row_sums or rc_gather_fields_fused left in `ws` (same n, same n_rows, ws
+ * untouched in between): another src / out pair of any supported width, or both table families of the FM models with -- each
+ * optional -- the numeric fields' weight gradients and the FM pairwise term's backward folded in (fm_V != null): occurrence
+ * o = r F + f then contributes  src[o] + fm_g[r] * (fm_S[r] - fm_V[o])  (rc_fm_second_order_bwd's rows with `add`, never written
+ * out; src may be null: no other consumer of the field vectors). */
 extern "C" int rc_small_row_sums_planned(int64_t n, int64_t n_rows, const float* src, int d, float* out, const float* src1, float* out1,
                                          const void* const* values, const int* per_row, const int* kind, const int* field,
                                          int n_numeric, int F, int64_t B, int C, float* const* dW, float* const* dw1, const float* fm_V,
                                          const float* fm_S, const float* fm_g, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(src1 && out1, "rc_small_row_sums_planned: null pointer");
-  RC_REQUIRE(n_numeric >= 0 && n_numeric <= kSmallNumeric && n_numeric <= F && F >= 1 && F <= kMaxFields,
-             "rc_small_row_sums_planned: %d numeric fields (0 .. %d) of F = %d", n_numeric, kSmallNumeric, F);
-  RC_REQUIRE(B >= 1 && C >= 1 && B * C * F == n && d % 4 == 0 && d >= 16, "rc_small_row_sums_planned: bad shape B=%lld C=%d F=%d n=%lld d=%d",
-             (long long)B, C, F, (long long)n, d);
-  RC_REQUIRE((fm_V == nullptr) == (fm_S == nullptr) && (fm_V == nullptr) == (fm_g == nullptr), "rc_small_row_sums_planned: fm_V, fm_S and fm_g come together");
-  FmTap fm;
-  fm.V = fm_V; fm.S = fm_S; fm.g = fm_g; fm.F = (uint32_t)F; fm.magic_F = small_div_magic((uint32_t)F);
-  SmallNumericCall nc;
-  memset(&nc, 0, sizeof(nc));
-  if (n_numeric > 0) {
-    RC_REQUIRE(values && per_row && kind && field && dW && dw1, "rc_small_row_sums_planned: null pointer (numeric fields)");
-    nc.n_numeric = n_numeric;
-    for (int j = 0; j < n_numeric; ++j) {
-      RC_REQUIRE(values[j] && dW[j] && dw1[j] && field[j] >= 0 && field[j] < F && kind[j] >= RC_FIELD_F32 && kind[j] <= RC_FIELD_I64,
-                 "rc_small_row_sums_planned: bad numeric field %d", j);
-      nc.num[j].values = values[j]; nc.num[j].dW = dW[j]; nc.num[j].dw1 = dw1[j];
-      nc.num[j].kind = kind[j]; nc.num[j].per_row = per_row[j]; nc.num[j].field = field[j];
-    }
-    nc.c.gV = src; nc.c.gL = src1; nc.c.part = nullptr; nc.c.n = B * C; nc.c.n_numeric = n_numeric; nc.c.F = F; nc.c.C = C; nc.c.d = d;
-  }
-  return small_row_sums_impl(false, nullptr, n, n_rows, src, d, out, ws, ws_bytes, stream, src1, out1, n_numeric > 0 ? &nc : nullptr,
-                             fm_V != nullptr ? &fm : nullptr);
+  return small_row_sums_impl("rc_small_row_sums_planned", false, nullptr, n, n_rows, src, d, out, src1, out1, values, per_row, kind, field,
+                             n_numeric, F, B, C, dW, dw1, fm_V, fm_S, fm_g, ws, ws_bytes, stream);
 }

@@ -185,18 +185,18 @@ extern "C" size_t rc_sort_workspace_bytes(int64_t n) {
          align_up(kSortDigits * sizeof(uint32_t), 256) + 256;
 }
 
-extern "C" int rc_sort_ids2(const int64_t* ids_a, int64_t n_a, const int64_t* ids_b, int64_t n_b,
-                            int64_t key_offset_b, int64_t key_range, uint32_t* keys_out,
-                            uint32_t* perm_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
+extern "C" int rc_sort_ids(const int64_t* ids_a, int64_t n_a, const int64_t* ids_b, int64_t n_b,
+                           int64_t key_offset_b, int64_t key_range, uint32_t* keys_out,
+                           uint32_t* perm_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
   const int64_t n = n_a + n_b;
-  RC_REQUIRE(n_a >= 0 && n_b >= 0 && n < ((int64_t)1 << 31), "rc_sort_ids2: sizes out of range");
+  RC_REQUIRE(n_a >= 0 && n_b >= 0 && n < ((int64_t)1 << 31), "rc_sort_ids: sizes out of range");
   if (n == 0) return RC_OK;
-  RC_REQUIRE((n_a == 0 || ids_a) && (n_b == 0 || ids_b) && keys_out && perm_out && ws, "rc_sort_ids2: null pointer");
+  RC_REQUIRE((n_a == 0 || ids_a) && (n_b == 0 || ids_b) && keys_out && perm_out && ws, "rc_sort_ids: null pointer");
   RC_REQUIRE(key_range >= 1 && key_range <= ((int64_t)1 << 32) && key_offset_b >= 0 && key_offset_b < key_range,
-             "rc_sort_ids2: key_range=%lld / key_offset_b=%lld out of range", (long long)key_range,
+             "rc_sort_ids: key_range=%lld / key_offset_b=%lld out of range", (long long)key_range,
              (long long)key_offset_b);
   const size_t need = rc_sort_workspace_bytes(n);
-  if (ws_bytes < need) return fail(RC_ERR_WORKSPACE, "rc_sort_ids2: workspace %zu < %zu", ws_bytes, need);
+  if (ws_bytes < need) return fail(RC_ERR_WORKSPACE, "rc_sort_ids: workspace %zu < %zu", ws_bytes, need);
   hipStream_t s = as_stream(stream);
   Carver cv(ws);
   uint32_t* keys_tmp = cv.take<uint32_t>((size_t)n);
@@ -222,14 +222,4 @@ extern "C" int rc_sort_ids2(const int64_t* ids_a, int64_t n_a, const int64_t* id
     src.keys = ko; src.perm = po;
   }
   return RC_OK;
-}
-
-extern "C" int rc_sort_ids(const int64_t* ids, int64_t n, int64_t n_rows, uint32_t* keys_out,
-                           uint32_t* perm_out, void* ws, size_t ws_bytes, rc_stream_t stream) {
-  RC_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "rc_sort_ids: n=%lld out of range", (long long)n);
-  if (n == 0) return RC_OK;
-  RC_REQUIRE(ids && keys_out && perm_out && ws, "rc_sort_ids: null pointer");
-  RC_REQUIRE(n_rows >= 1 && n_rows <= ((int64_t)1 << 32), "rc_sort_ids: n_rows=%lld out of range",
-             (long long)n_rows);
-  return rc_sort_ids2(ids, n, nullptr, 0, 0, n_rows, keys_out, perm_out, ws, ws_bytes, stream);
 }

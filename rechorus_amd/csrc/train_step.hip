@@ -342,7 +342,7 @@ static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, 
   RC_MARK(0);
   // one joint radix sort: keys = item id | n_items + user id (all user keys sort after all item keys)
   RC_REQUIRE(n_items + n_users <= ((int64_t)1 << 32), "rc_bprmf_train_step: n_items + n_users exceeds 2^32");
-  RC_TRY(rc_sort_ids2(iid, n_i, uid, B, n_items, n_items + n_users, w.keys_i, w.perm_i, w.sort_ws,
+  RC_TRY(rc_sort_ids(iid, n_i, uid, B, n_items, n_items + n_users, w.keys_i, w.perm_i, w.sort_ws,
                       w.sort_ws_bytes, stream));
   RC_MARK(1);
   if (fused_upd)

@@ -4,6 +4,7 @@
 Nothing here falls back to torch arithmetic: a missing library, a CPU tensor or an
 unsupported shape raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -163,7 +164,7 @@ def sort_ids(ids, n_rows):
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     nbytes = _lib.load().rc_sort_workspace_bytes(n)
     ws = workspace(nbytes, dev, "sort")
-    _lib.call("rc_sort_ids", _ptr(ids_flat, torch.int64, "ids"), n, int(n_rows),
+    _lib.call("rc_sort_ids", _ptr(ids_flat, torch.int64, "ids"), n, None, 0, 0, int(n_rows),
               _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"),
               C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
     return keys, perm
@@ -495,7 +496,7 @@ def embedding_dense_backward(grad_out, ids, n_rows, route=None, presorted=None, 
     position order per row (no float atomics) -- bucket plan + rc_plan_row_sums; radix sort + segmented sum where no
     plan geometry exists.  presorted = sort_ids(ids, n_rows) of a caller that sorted the same ids already (route "sort").
     route "small" with small_again=True: the caller vouches that the preceding call on workspace `small_tag` grouped these very
-    ids (a second table family gathered with the same ids): only the row sums run (rc_small_row_sums_again)."""
+    ids (a second table family gathered with the same ids): only the row sums run (rc_small_row_sums_planned)."""
     d = grad_out.shape[-1]
     flat = ids.reshape(-1)
     G = torch.zeros((n_rows, d), dtype=torch.float32, device=grad_out.device)
@@ -510,12 +511,11 @@ def embedding_dense_backward(grad_out, ids, n_rows, route=None, presorted=None, 
     n_ids = flat.numel()
     if route == "small" and small_route_ok(n_ids, n_rows, d):
         ws = workspace(_lib.load().rc_small_row_sums_workspace_bytes(n_ids), go.device, small_tag)
+        src, out, ws_args = _ptr(go, torch.float32, "grad_out"), _ptr(G, torch.float32, "G"), (C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
         if small_again:
-            _lib.call("rc_small_row_sums_again", n_ids, int(n_rows), _ptr(go, torch.float32, "grad_out"), d,
-                      _ptr(G, torch.float32, "G"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+            _lib.call("rc_small_row_sums_planned", n_ids, int(n_rows), src, d, out, *_NO_PAIR, *_NO_NUMERIC, None, None, None, *ws_args)
         else:
-            _lib.call("rc_small_row_sums", _ptr(flat, torch.int64, "ids"), n_ids, int(n_rows), _ptr(go, torch.float32, "grad_out"), d,
-                      _ptr(G, torch.float32, "G"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+            _lib.call("rc_small_row_sums", _ptr(flat, torch.int64, "ids"), n_ids, int(n_rows), src, d, out, *_NO_PAIR, *_NO_NUMERIC, *ws_args)
         return G
     # (below a few thousand ids both routes are a handful of latency-bound launches; the plan pays off with the batch)
     # route="sort": id lists with very hot rows (the categorical fields of the CTR models: 131,072 occurrences of 7 weekdays) --
@@ -528,50 +528,63 @@ def embedding_dense_backward(grad_out, ids, n_rows, route=None, presorted=None, 
 
 
 SMALL_NUMERIC_MAX = 4      # numeric fields that can ride in the small route's row-sums launch (kSmallNumeric)
+_NO_PAIR = (None, None)                                          # src1, out1
+_NO_NUMERIC = (None, None, None, None, 0, 0, 0, 0, None, None)   # values, per_row, kind, field, n_numeric, F, B, C, dW, dw1
+
+
+def _numeric_arrays(values, fields, dev, d=None, want_dw1=True):
+    """the host arrays that describe numeric fields to the library (rc_numeric_field_grads' values / per_row / kind / field / dW /
+    dw1) and fresh outputs: -> ((val_arr, per_row, kind_arr, field_arr), dW [J, d, 1] | None, dW_arr, dw1 [J, 1, 1] | None, dw1_arr)"""
+    J, f32 = len(values), torch.float32
+    dW = torch.empty((J, d, 1), dtype=f32, device=dev) if d is not None else None
+    dw1 = torch.empty((J, 1, 1), dtype=f32, device=dev) if want_dw1 else None
+    arrays = ((C.c_void_p * J)(*[_ptr(x, x.dtype, "values").value for x in values]),
+              (C.c_int * J)(*[1 if x.dim() == 1 else 0 for x in values]),
+              (C.c_int * J)(*[field_kind(x) for x in values]),
+              (C.c_int * J)(*[int(f) for f in fields]))
+    ptrs = lambda t: None if t is None else (C.c_void_p * J)(*[t[j].data_ptr() for j in range(J)])
+    return arrays, dW, ptrs(dW), dw1, ptrs(dw1)
+
+
+def _riding_numeric(who, numeric, d, shape, dev):
+    """numeric = (values, fields, ...) | None of the small route, shape = (F, B, n_cand)
+    -> (rc_small_row_sums' ten numeric arguments, dW list | None, dw1 list | None)"""
+    F, B, n_cand = (int(x) for x in shape)
+    if numeric is None:
+        return (None, None, None, None, 0, F, B, n_cand, None, None), None, None
+    values, fields = numeric[:2]
+    J = len(values)
+    if not (16 <= d <= 128 and d % 4 == 0 and 1 <= J <= SMALL_NUMERIC_MAX):
+        raise ValueError("%s: the numeric fields ride with d in 16 .. 128 and at most %d of them" % (who, SMALL_NUMERIC_MAX))
+    arrays, dW, dW_arr, dw1, dw1_arr = _numeric_arrays(values, fields, dev, d)
+    return (*arrays, J, F, B, n_cand, dW_arr, dw1_arr), [dW[j] for j in range(J)], [dw1[j] for j in range(J)]
 
 
 def small_row_sums_pair(cid, n_rows, src_a, src_b, into=None, numeric=None):
     """two dense gradients [n_rows, d_a], [n_rows, d_b] of per-occurrence rows src_a [n, d_a], src_b [n, d_b] that share their ids:
-    ONE zero fill (both live in one buffer), ONE grouping (rc_small_row_sums, then rc_small_row_sums_again for the second).
+    ONE zero fill (both live in one buffer), ONE grouping: rc_small_row_sums with the second source riding (d_b = 1, d_a >= 16),
+    else rc_small_row_sums, then rc_small_row_sums_planned for the second on the same workspace.
     into: a float buffer of n_rows * (d_a + d_b) elements that is NOT zero-filled -- only the rows of `cid` are written (the
-    kernels assign row sums), for a consumer that reads only those (dense_update_rows(touched=True))"""
-    n = cid.numel()
+    kernels assign row sums), for a consumer that reads only those (dense_update_rows(touched=True))
+    numeric = (values, fields, F, n_cand): the weight gradients of the numeric fields of the same gradient blocks (src_a = gV
+    [rows * F, d], src_b = gL [rows * F, 1]) by extra workgroups of the row-sums launch -> (Ga, Gb, dW list, dw1 list)"""
+    n, f32 = cid.numel(), torch.float32
     d_a, d_b = src_a.shape[1], src_b.shape[1]
-    G = torch.zeros(n_rows * (d_a + d_b), dtype=torch.float32, device=src_a.device) if into is None else into
+    G = torch.zeros(n_rows * (d_a + d_b), dtype=f32, device=src_a.device) if into is None else into
     Ga, Gb = G[:n_rows * d_a].view(n_rows, d_a), G[n_rows * d_a:].view(n_rows, d_b)
     ws = workspace(_lib.load().rc_small_row_sums_workspace_bytes(n), src_a.device, "edb_small_pair")
-    flat = cid.reshape(-1)
-    if numeric is not None:
-        # numeric = (values, fields, F, n_cand): the weight gradients of the numeric fields of the same gradient blocks (src_a = gV
-        # [rows * F, d], src_b = gL [rows * F, 1]) by extra workgroups of the row-sums launch -> (Ga, Gb, dW list, dw1 list)
-        values, fields, F, n_cand = numeric
-        J = len(values)
-        if not (d_b == 1 and 16 <= d_a <= 128 and d_a % 4 == 0 and 1 <= J <= SMALL_NUMERIC_MAX):
-            raise ValueError("small_row_sums_pair: the numeric fields ride with d in 16 .. 128 and at most %d of them" % SMALL_NUMERIC_MAX)
-        f32 = torch.float32
-        B = values[0].shape[0]
-        dW = torch.empty((J, d_a, 1), dtype=f32, device=src_a.device)
-        dw1 = torch.empty((J, 1, 1), dtype=f32, device=src_a.device)
-        val_arr = (C.c_void_p * J)(*[_ptr(x, x.dtype, "values").value for x in values])
-        per_row = (C.c_int * J)(*[1 if x.dim() == 1 else 0 for x in values])
-        kind_arr = (C.c_int * J)(*[field_kind(x) for x in values])
-        field_arr = (C.c_int * J)(*[int(f) for f in fields])
-        dW_arr = (C.c_void_p * J)(*[dW[j].data_ptr() for j in range(J)])
-        dw1_arr = (C.c_void_p * J)(*[dw1[j].data_ptr() for j in range(J)])
-        _lib.call("rc_small_row_sums_pair_numeric", _ptr(flat, torch.int64, "ids"), n, int(n_rows), _ptr(src_a, f32, "src_a"), d_a,
-                  C.c_void_p(Ga.data_ptr()), _ptr(src_b, f32, "src_b"), C.c_void_p(Gb.data_ptr()), val_arr, per_row, kind_arr, field_arr, J,
-                  int(F), B, int(n_cand), dW_arr, dw1_arr, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
-        return Ga, Gb, [dW[j] for j in range(J)], [dw1[j] for j in range(J)]
-    if d_b == 1 and d_a >= 16:     # the one-float-wide table rides in the vectors' row-sums launch
-        _lib.call("rc_small_row_sums_pair", _ptr(flat, torch.int64, "ids"), n, int(n_rows), _ptr(src_a, torch.float32, "src_a"), d_a,
-                  C.c_void_p(Ga.data_ptr()), _ptr(src_b, torch.float32, "src_b"), C.c_void_p(Gb.data_ptr()), C.c_void_p(ws.data_ptr()),
-                  ws.numel(), _stream())
-        return Ga, Gb
-    _lib.call("rc_small_row_sums", _ptr(flat, torch.int64, "ids"), n, int(n_rows), _ptr(src_a, torch.float32, "src_a"), d_a,
-              C.c_void_p(Ga.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
-    _lib.call("rc_small_row_sums_again", n, int(n_rows), _ptr(src_b, torch.float32, "src_b"), d_b, C.c_void_p(Gb.data_ptr()),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
-    return Ga, Gb
+    ws_args = (C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+    rides = d_b == 1 and d_a >= 16      # the one-float-wide table rides in the vectors' row-sums launch
+    if numeric is not None and not rides:
+        raise ValueError("small_row_sums_pair: the numeric fields ride with d in 16 .. 128 beside a one-float-wide second source")
+    shape = (0, 0, 0) if numeric is None else (numeric[2], numeric[0][0].shape[0], numeric[3])      # F, B, n_cand
+    num_args, dW, dw1 = _riding_numeric("small_row_sums_pair", numeric, d_a, shape, src_a.device)
+    pair = (_ptr(src_b, f32, "src_b"), C.c_void_p(Gb.data_ptr()))
+    _lib.call("rc_small_row_sums", _ptr(cid.reshape(-1), torch.int64, "ids"), n, int(n_rows), _ptr(src_a, f32, "src_a"), d_a,
+              C.c_void_p(Ga.data_ptr()), *(pair if rides else _NO_PAIR), *num_args, *ws_args)
+    if not rides:
+        _lib.call("rc_small_row_sums_planned", n, int(n_rows), pair[0], d_b, pair[1], *_NO_PAIR, *_NO_NUMERIC, None, None, None, *ws_args)
+    return (Ga, Gb) if numeric is None else (Ga, Gb, dW, dw1)
 
 
 def small_row_sums_planned(plan_ws, n, n_rows, src_a, src_b, d, shape, into=None, numeric=None, fm=None):
@@ -583,32 +596,13 @@ def small_row_sums_planned(plan_ws, n, n_rows, src_a, src_b, d, shape, into=None
     dev, f32 = src_b.device, torch.float32
     G = torch.zeros(n_rows * (d + 1), dtype=f32, device=dev) if into is None else into
     Ga, Gb = G[:n_rows * d].view(n_rows, d), G[n_rows * d:].view(n_rows, 1)
-    J = 0
-    val_arr = per_row = kind_arr = field_arr = dW_arr = dw1_arr = dW = dw1 = None
-    F, B, n_cand = shape
-    if numeric is not None:
-        values, fields = numeric[:2]
-        J = len(values)
-        if not (1 <= J <= SMALL_NUMERIC_MAX):
-            raise ValueError("small_row_sums_planned: at most %d numeric fields ride along" % SMALL_NUMERIC_MAX)
-        dW = torch.empty((J, d, 1), dtype=f32, device=dev)
-        dw1 = torch.empty((J, 1, 1), dtype=f32, device=dev)
-        val_arr = (C.c_void_p * J)(*[_ptr(x, x.dtype, "values").value for x in values])
-        per_row = (C.c_int * J)(*[1 if x.dim() == 1 else 0 for x in values])
-        kind_arr = (C.c_int * J)(*[field_kind(x) for x in values])
-        field_arr = (C.c_int * J)(*[int(f) for f in fields])
-        dW_arr = (C.c_void_p * J)(*[dW[j].data_ptr() for j in range(J)])
-        dw1_arr = (C.c_void_p * J)(*[dw1[j].data_ptr() for j in range(J)])
-    fm_V = fm_S = fm_g = None
-    if fm is not None:
-        fm_V, fm_S, fm_g = fm
+    num_args, dW, dw1 = _riding_numeric("small_row_sums_planned", numeric, d, shape, dev)
+    fm_V, fm_S, fm_g = (None, None, None) if fm is None else fm
     _lib.call("rc_small_row_sums_planned", n, int(n_rows), _ptr(src_a, f32, "src_a", True), int(d), C.c_void_p(Ga.data_ptr()),
-              _ptr(src_b, f32, "src_b"), C.c_void_p(Gb.data_ptr()), val_arr, per_row, kind_arr, field_arr, J, int(F), int(B), int(n_cand),
-              dW_arr, dw1_arr, _ptr(fm_V, f32, "fm_V", True), _ptr(fm_S, f32, "fm_S", True), _ptr(fm_g, f32, "fm_g", True),
+              _ptr(src_b, f32, "src_b"), C.c_void_p(Gb.data_ptr()), *num_args,
+              _ptr(fm_V, f32, "fm_V", True), _ptr(fm_S, f32, "fm_S", True), _ptr(fm_g, f32, "fm_g", True),
               C.c_void_p(plan_ws.data_ptr()), plan_ws.numel(), _stream())
-    if J:
-        return Ga, Gb, [dW[j] for j in range(J)], [dw1[j] for j in range(J)]
-    return Ga, Gb
+    return (Ga, Gb) if numeric is None else (Ga, Gb, dW, dw1)
 
 
 def dense_update(W, G, hyper, m=None, v=None):
@@ -2019,12 +2013,8 @@ def fm_second_order_bwd(V, gout, add=None):
     F, d = V.shape[-2], V.shape[-1]
     n = V.numel() // (F * d)
     dV = torch.empty_like(V)
-    if add is None:
-        _lib.call("rc_fm_second_order_bwd", _ptr(V, torch.float32, "V"), _ptr(gout, torch.float32, "gout"), n, F, d,
-                  _ptr(dV, torch.float32, "dV"), _stream())
-    else:
-        _lib.call("rc_fm_second_order_bwd_add", _ptr(V, torch.float32, "V"), _ptr(gout, torch.float32, "gout"), n, F, d,
-                  _ptr(add, torch.float32, "add"), _ptr(dV, torch.float32, "dV"), _stream())
+    _lib.call("rc_fm_second_order_bwd", _ptr(V, torch.float32, "V"), _ptr(gout, torch.float32, "gout"), n, F, d,
+              _ptr(add, torch.float32, "add", True), _ptr(dV, torch.float32, "dV"), _stream())
     return dV
 
 
@@ -2050,22 +2040,26 @@ def field_kind(values):
     return kind
 
 
+# gather_fields' result; the parts that were not asked for are None.  offsets: row_offset per field + the total row count
+FieldGather = collections.namedtuple("FieldGather", "out out1 cid offsets fm_term fm_sum plan_ws")
+
+
 def gather_fields(tables, ids, n_cand, want_cid=True, tables1=None, mark=None, kinds=None, numeric_key=-1, fm=False, plan=False, bump=None):
     """tables: list of F [vocab_f, d] tensors; ids: list of F int64 tensors, [B] (per-row field) or [B, C]
-    -> (out [B, C, F, d], cid [B, C, F] | None, row_offset list): all field lookups in one launch.
-    tables1: F [vocab_f, 1] tables looked up with the same ids (rc_gather_fields_pair) -> (out, out1 [B, C, F, 1], cid, offsets)
+    -> FieldGather(out [B, C, F, d], out1, cid [B, C, F], offsets, fm_term, fm_sum, plan_ws): all field lookups in one launch
+    (rc_gather_fields; with fm / plan rc_gather_fields_fused).
+    tables1: F [vocab_f, 1] tables looked up with the same ids -> out1 [B, C, F, 1]
     mark = (row_flags int32 [sum of vocab sizes], step_dev int64 [1]): the looked-up rows are stamped with the number of the
-    step in progress, step_dev + 1 (rc_gather_fields_pair_mark, for dense_update_rows)
-    kinds: per field FIELD_IDS or the value type of a NUMERIC field (rc_gather_fields_mixed; models/context/FM.py:38-41,47-48):
+    step in progress, step_dev + 1 (for dense_update_rows)
+    kinds: per field FIELD_IDS or the value type of a NUMERIC field (models/context/FM.py:38-41,47-48):
     tables[f] is then the Linear(1, d) weight [d, 1], tables1[f] the Linear(1, 1) weight [1, 1], ids[f] the feature's values;
     such a field owns no row of the concatenated table and its occurrences carry `numeric_key` in cid
-    fm / plan (rc_gather_fields_fused; d in 16 / 32 / 64 / 128, tables1 given): the same launch also forms the FM pairwise term
-    [B, C] + the field sums [B, C, d], and / or groups the composite keys for the backward pass's row sums (small batches) into a
-    fresh workspace -> (out, out1, cid, offsets, fm_term | None, fm_sum | None, plan_ws | None); bump: an int64 [1] device counter
-    the same launch increments (the caller promises nothing in the launch reads it; recorded for step_increment: bumped_early)"""
+    fm / plan (d in 16 / 32 / 64 / 128, tables1 given): the same launch also forms the FM pairwise term fm_term [B, C] + the field
+    sums fm_sum [B, C, d], and / or groups the composite keys for the backward pass's row sums (small batches) into a fresh
+    workspace plan_ws; bump: an int64 [1] device counter the same launch increments (the caller promises nothing in the launch
+    reads it; recorded for step_increment: bumped_early)"""
     F = len(tables)
     kinds = [FIELD_IDS] * F if kinds is None else [int(k) for k in kinds]
-    mixed = any(k != FIELD_IDS for k in kinds)
     d = next((t.shape[1] for t, k in zip(tables, kinds) if k == FIELD_IDS), tables[0].shape[0])
     B = ids[0].shape[0]
     dev, f32, i64 = tables[0].device, torch.float32, torch.int64
@@ -2080,10 +2074,6 @@ def gather_fields(tables, ids, n_cand, want_cid=True, tables1=None, mark=None, k
     for x, k in zip(ids, kinds):
         if k != FIELD_IDS and field_kind(x) != k:
             raise ValueError("gather_fields: kind {} does not match the value dtype {}".format(k, x.dtype))
-    tab_arr = (C.c_void_p * F)(*[_ptr(t, f32, "table").value for t in tables])
-    ids_arr = (C.c_void_p * F)(*[_ptr(x, i64 if k == FIELD_IDS else x.dtype, "ids").value for x, k in zip(ids, kinds)])
-    per_row = (C.c_int * F)(*[1 if x.dim() == 1 else 0 for x in ids])
-    off_arr = (C.c_int64 * F)(*offs)
     out1 = tab1_arr = None
     if tables1 is not None:
         if len(tables1) != F or any(t1.shape != ((t.shape[0], 1) if k == FIELD_IDS else (1, 1)) for t, t1, k in zip(tables, tables1, kinds)):
@@ -2097,43 +2087,29 @@ def gather_fields(tables, ids, n_cand, want_cid=True, tables1=None, mark=None, k
             raise ValueError("gather_fields: row flags come with the pair gather")
         if flags.numel() != run:
             raise ValueError("gather_fields: one row flag per row of the concatenated tables")
-    if fm or plan:
-        if tables1 is None or d not in (16, 32, 64, 128):
-            raise ValueError("gather_fields: the FM term / the plan ride with the pair gather at d in 16 / 32 / 64 / 128")
-        kind_arr = (C.c_int * F)(*kinds)
-        fm_term = torch.empty((B, n_cand), dtype=f32, device=dev) if fm else None
-        fm_sum = torch.empty((B, n_cand, d), dtype=f32, device=dev) if fm else None
-        plan_ws = None
-        if plan:
-            # not the name-keyed workspace cache: the plan lives from this forward to its backward
-            plan_ws = torch.empty(_lib.load().rc_small_row_sums_workspace_bytes(B * n_cand * F), dtype=torch.uint8, device=dev)
-        _lib.call("rc_gather_fields_fused", tab_arr, tab1_arr, ids_arr, per_row, kind_arr, int(numeric_key), off_arr, F, B, int(n_cand), d,
-                  _ptr(out, f32, "out"), _ptr(out1, f32, "out1"), _ptr(cid, i64, "cid", True), _ptr(flags, torch.int32, "row_flags", True),
-                  _ptr(step_dev, i64, "step_dev", True), 1, _ptr(fm_term, f32, "fm_out", True), _ptr(fm_sum, f32, "fm_sum", True),
-                  C.c_void_p(plan_ws.data_ptr()) if plan else None, plan_ws.numel() if plan else 0, _ptr(bump, i64, "bump", True), _stream())
-        if bump is not None:
-            _bumped_early.append(bump)
-        return out, out1, cid, offs + [run], fm_term, fm_sum, plan_ws
-    if bump is not None:
+    fused = bool(fm or plan)
+    if fused and (tables1 is None or d not in (16, 32, 64, 128)):
+        raise ValueError("gather_fields: the FM term / the plan ride with the pair gather at d in 16 / 32 / 64 / 128")
+    if bump is not None and not fused:
         raise ValueError("gather_fields: a counter rides in the fused launch only (fm / plan)")
-    if mixed:
-        kind_arr = (C.c_int * F)(*kinds)
-        _lib.call("rc_gather_fields_mixed", tab_arr, tab1_arr, ids_arr, per_row, kind_arr, int(numeric_key), off_arr, F, B, int(n_cand), d,
-                  _ptr(out, f32, "out"), _ptr(out1, f32, "out1", True), _ptr(cid, i64, "cid", True), _ptr(flags, torch.int32, "row_flags", True),
-                  _ptr(step_dev, i64, "step_dev", True), 1, _stream())
-    elif mark is not None:
-        _lib.call("rc_gather_fields_pair_mark", tab_arr, tab1_arr, ids_arr, per_row, off_arr, F, B, int(n_cand), d,
-                  _ptr(out, f32, "out"), _ptr(out1, f32, "out1"), _ptr(cid, i64, "cid", True), _ptr(flags, torch.int32, "row_flags"),
-                  _ptr(step_dev, i64, "step_dev"), 1, _stream())
-    elif tables1 is not None:
-        _lib.call("rc_gather_fields_pair", tab_arr, tab1_arr, ids_arr, per_row, off_arr, F, B, int(n_cand), d, _ptr(out, f32, "out"),
-                  _ptr(out1, f32, "out1"), _ptr(cid, i64, "cid", True), _stream())
-    else:
-        _lib.call("rc_gather_fields", tab_arr, ids_arr, per_row, off_arr, F, B, int(n_cand), d, _ptr(out, f32, "out"),
-                  _ptr(cid, i64, "cid", True), _stream())
-    if tables1 is not None:
-        return out, out1, cid, offs + [run]
-    return out, cid, offs + [run]
+    args = [(C.c_void_p * F)(*[_ptr(t, f32, "table").value for t in tables]), tab1_arr,
+            (C.c_void_p * F)(*[_ptr(x, i64 if k == FIELD_IDS else x.dtype, "ids").value for x, k in zip(ids, kinds)]),
+            (C.c_int * F)(*[1 if x.dim() == 1 else 0 for x in ids]), (C.c_int * F)(*kinds), int(numeric_key), (C.c_int64 * F)(*offs),
+            F, B, int(n_cand), d, _ptr(out, f32, "out"), _ptr(out1, f32, "out1", True), _ptr(cid, i64, "cid", True),
+            _ptr(flags, torch.int32, "row_flags", True), _ptr(step_dev, i64, "step_dev", True), 1]
+    fm_term = fm_sum = plan_ws = None
+    if fused:
+        if fm:
+            fm_term = torch.empty((B, n_cand), dtype=f32, device=dev)
+            fm_sum = torch.empty((B, n_cand, d), dtype=f32, device=dev)
+        if plan:    # not the name-keyed workspace cache: the plan lives from this forward to its backward
+            plan_ws = torch.empty(_lib.load().rc_small_row_sums_workspace_bytes(B * n_cand * F), dtype=torch.uint8, device=dev)
+        args += [_ptr(fm_term, f32, "fm_out", True), _ptr(fm_sum, f32, "fm_sum", True), C.c_void_p(plan_ws.data_ptr()) if plan else None,
+                 plan_ws.numel() if plan else 0, _ptr(bump, i64, "bump", True)]
+    _lib.call("rc_gather_fields_fused" if fused else "rc_gather_fields", *args, _stream())
+    if bump is not None:
+        _bumped_early.append(bump)
+    return FieldGather(out, out1, cid, offs + [run], fm_term, fm_sum, plan_ws)
 
 
 def numeric_field_grads(gV, gL, values, fields, n_fields, n_cand, d):
@@ -2144,19 +2120,10 @@ def numeric_field_grads(gV, gL, values, fields, n_fields, n_cand, d):
     src = gV if gV is not None else gL
     dev, f32 = src.device, torch.float32
     B = values[0].shape[0]
-    n = B * n_cand
-    dW = torch.empty((J, d, 1), dtype=f32, device=dev) if gV is not None else None
-    dw1 = torch.empty((J, 1, 1), dtype=f32, device=dev) if gL is not None else None
-    kinds = [field_kind(x) for x in values]
-    val_arr = (C.c_void_p * J)(*[_ptr(x, x.dtype, "values").value for x in values])
-    per_row = (C.c_int * J)(*[1 if x.dim() == 1 else 0 for x in values])
-    kind_arr = (C.c_int * J)(*kinds)
-    field_arr = (C.c_int * J)(*[int(f) for f in fields])
-    dW_arr = (C.c_void_p * J)(*[dW[j].data_ptr() for j in range(J)]) if dW is not None else None
-    dw1_arr = (C.c_void_p * J)(*[dw1[j].data_ptr() for j in range(J)]) if dw1 is not None else None
-    nbytes = _lib.load().rc_numeric_field_grads_workspace_bytes(n, J, d)
+    arrays, dW, dW_arr, dw1, dw1_arr = _numeric_arrays(values, fields, dev, d if gV is not None else None, want_dw1=gL is not None)
+    nbytes = _lib.load().rc_numeric_field_grads_workspace_bytes(B * n_cand, J, d)
     ws = workspace(nbytes, dev, "numeric_fields")
-    _lib.call("rc_numeric_field_grads", _ptr(gV, f32, "gV", True), _ptr(gL, f32, "gL", True), val_arr, per_row, kind_arr, field_arr, J,
+    _lib.call("rc_numeric_field_grads", _ptr(gV, f32, "gV", True), _ptr(gL, f32, "gL", True), *arrays, J,
               int(n_fields), B, int(n_cand), int(d), dW_arr, dw1_arr, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
     return (None if dW is None else [dW[j] for j in range(J)]), (None if dw1 is None else [dw1[j] for j in range(J)])
 
@@ -2191,7 +2158,7 @@ CTR_HEAD_ONE_WG_MAX = 65536   # rows the one-workgroup head (rc_ctr_head_fwd_bwd
 
 def ctr_head_sums(bias, lin, term1, term2, label, full=False):
     """ctr_head in one workgroup that also forms the loss mean and sum gz: -> (p [n], sums [2] = (loss, sum gz), gz [n]).
-    full=True (rc_ctr_head_fwd_full): the same launch leaves the backward fan-out for a seed gradient of exactly one --
+    full=True (g_lin / g_bias / bump given): the same launch leaves the backward fan-out for a seed gradient of exactly one --
     -> (p, sums, gz, g_lin [n, F], g_bias [1]) -- and takes a pending deferred counter increment along (Adam's step count)"""
     n, F = lin.shape
     f32 = torch.float32
@@ -2199,23 +2166,20 @@ def ctr_head_sums(bias, lin, term1, term2, label, full=False):
     loss_vec = torch.empty(n, dtype=f32, device=lin.device)
     gz = torch.empty(n, dtype=f32, device=lin.device)
     sums = torch.empty(2, dtype=f32, device=lin.device)
+    g_lin = g_bias = bump = None
     if full:
         g_lin = torch.empty((n, F), dtype=f32, device=lin.device)
         g_bias = torch.empty(1, dtype=f32, device=lin.device)
         bump = pending_deferred()
         if bump is not None and bump.device != lin.device:
             bump = None
-        _lib.call("rc_ctr_head_fwd_full", _ptr(bias, f32, "bias"), _ptr(lin, f32, "lin"), int(F), _ptr(term1, f32, "term1", True),
-                  _ptr(term2, f32, "term2", True), _ptr(label, torch.int64, "label"), n, _ptr(p, f32, "p"), _ptr(loss_vec, f32, "loss_vec"),
-                  _ptr(gz, f32, "gz"), _ptr(sums, f32, "sums"), _ptr(g_lin, f32, "g_lin"), _ptr(g_bias, f32, "g_bias"),
-                  _ptr(bump, torch.int64, "bump", True), _stream())
-        if bump is not None:
-            fold_deferred(bump)
-        return p, sums, gz, g_lin, g_bias
     _lib.call("rc_ctr_head_fwd_bwd_sums", _ptr(bias, f32, "bias"), _ptr(lin, f32, "lin"), int(F), _ptr(term1, f32, "term1", True),
               _ptr(term2, f32, "term2", True), _ptr(label, torch.int64, "label"), n, _ptr(p, f32, "p"), _ptr(loss_vec, f32, "loss_vec"),
-              _ptr(gz, f32, "gz"), _ptr(sums, f32, "sums"), _stream())
-    return p, sums, gz
+              _ptr(gz, f32, "gz"), _ptr(sums, f32, "sums"), _ptr(g_lin, f32, "g_lin", True), _ptr(g_bias, f32, "g_bias", True),
+              _ptr(bump, torch.int64, "bump", True), _stream())
+    if bump is not None:
+        fold_deferred(bump)
+    return (p, sums, gz, g_lin, g_bias) if full else (p, sums, gz)
 
 
 def ctr_head_bwd(gz, sums, g_loss, F):

@@ -266,7 +266,7 @@ def fm_second_order(V):
 class _FmTapFn(torch.autograd.Function):
     """the FM pairwise term AND the flattened field vectors for a second consumer (DeepFM's deep tower, models/context/DeepFM.py:
     19-28) as one autograd node: its backward forms d fm2 / dV on top of the gradient the second consumer sends back in ONE pass
-    (rc_fm_second_order_bwd_add) -- as two nodes autograd writes both gradients out and adds them (three more passes over
+    (rc_fm_second_order_bwd with add) -- as two nodes autograd writes both gradients out and adds them (three more passes over
     [B, C, F, d])."""
 
     @staticmethod
@@ -318,7 +318,8 @@ class _FieldGatherFn(torch.autograd.Function):
         _FieldGatherFn._last_cid = None
         hit = (last is not None and len(last[0]) == len(ids_c) and all(a is b for a, b in zip(last[0], ids_c))
                and last[1] == tuple(x._version for x in ids_c) and last[2] == n_cand and last[3] == offs_now)
-        out, cid, offs = engine.gather_fields([t.detach() for t in tables], ids_c, n_cand, want_cid=not hit)
+        res = engine.gather_fields([t.detach() for t in tables], ids_c, n_cand, want_cid=not hit)
+        out, cid, offs = res.out, res.cid, res.offsets
         if hit:
             cid = last[4]
         else:
@@ -366,11 +367,11 @@ def gather_fields(tables, ids, n_cand):
 
 class _FieldGatherPairFn(torch.autograd.Function):
     """the TWO table families the FM models gather with the same ids (models/context/FM.py:44-57: field vectors [vocab, d] and
-    first-order weights [vocab, 1]) as one autograd node: one gather launch forward (rc_gather_fields_pair); backward, ONE
-    grouping of the composite (field, id) keys serves both dense gradients -- the small route's plan (rc_small_row_sums +
-    rc_small_row_sums_again on one zero-filled buffer), or one sort -- instead of one per family.
+    first-order weights [vocab, 1]) as one autograd node: one gather launch forward (rc_gather_fields with tables1); backward, ONE
+    grouping of the composite (field, id) keys serves both dense gradients -- the small route's plan (rc_small_row_sums, then
+    rc_small_row_sums_planned where the second does not ride, on one zero-filled buffer), or one sort -- instead of one per family.
     Numeric fields (kinds[f] != 0; FM.py:38-41,47-48: Linear(1, d) / Linear(1, 1) on the feature's value) ride in the same gather
-    launch (rc_gather_fields_mixed: their "row" is x * W[:, 0]); they own no row of the concatenated table, their occurrences
+    launch (rc_gather_fields' kind: their "row" is x * W[:, 0]); they own no row of the concatenated table, their occurrences
     take no part in the grouping, and their weight gradients are one weighted column sum (rc_numeric_field_grads)."""
 
     @staticmethod
@@ -401,15 +402,10 @@ class _FieldGatherPairFn(torch.autograd.Function):
         # launch (rc_gather_fields_fused) instead of as a launch of its own in front of the row sums
         plan = bool(fusable and cat and ctx.route == "small" and any(ctx.needs_input_grad) and engine.small_route_ok(n, n_rows, d))
         fm_here = bool(want_fm and fusable)
-        S = fm = plan_ws = None
-        if plan or fm_here:
-            V, L, cid, offs, fm, S, plan_ws = engine.gather_fields([t.detach() for t in tables], ids, n_cand, want_cid=True,
-                                                                   tables1=[t.detach() for t in tables1], mark=mark, kinds=kinds,
-                                                                   numeric_key=numeric_key, fm=fm_here, plan=plan, bump=bump)
-        else:
-            V, L, cid, offs = engine.gather_fields([t.detach() for t in tables], ids, n_cand, want_cid=True,
-                                                   tables1=[t.detach() for t in tables1], mark=mark,
-                                                   kinds=kinds if num else None, numeric_key=numeric_key)
+        V, L, cid, offs, fm, S, plan_ws = engine.gather_fields([t.detach() for t in tables], ids, n_cand, want_cid=True,
+                                                               tables1=[t.detach() for t in tables1], mark=mark, kinds=kinds,
+                                                               numeric_key=numeric_key, fm=fm_here, plan=plan,
+                                                               bump=bump if (plan or fm_here) else None)
         if want_fm and fm is None:
             fm = engine.fm_second_order(V)      # (a width without the float4 lane-group tiling: its own launch)
         ctx.rows_opt = rows_opt if mark is not None else None
@@ -436,7 +432,7 @@ class _FieldGatherPairFn(torch.autograd.Function):
         small = ctx.route == "small" and n_rows > 0 and d % 4 == 0 and engine.small_route_ok(n, n_rows, d)
         planned = small and ctx.plan_ws is not None and gL is not None
         # the FM term's backward: added to the tower's gradient rows where the row sums read them (planned small route: never
-        # written out), else one pass of its own (rc_fm_second_order_bwd_add)
+        # written out), else one pass of its own (rc_fm_second_order_bwd with add)
         tap = None
         if ctx.want_fm and g_fm is not None:
             saved = ctx.saved_tensors

@@ -10,7 +10,7 @@ sort + segmented sum over the composite (field, id) key.  The pairwise-interacti
     0.5 * sum_k ((sum_f v_fk)^2 - sum_f v_fk^2)
 is one kernel pair (rc_fm_second_order_fwd / _bwd) over the stacked field vectors.  Numeric
 fields (:38-41: Linear(1, d, bias=False) on the feature's value, e.g. MIND's c_day_f) keep the
-reference's parameters and ride in the same gather launch (rc_gather_fields_mixed: the field's
+reference's parameters and ride in the same gather launch (rc_gather_fields' kind: the field's
 "row" is x * W[:, 0]); their weight gradients are one weighted column sum (rc_numeric_field_grads).
 """
 import torch

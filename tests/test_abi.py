@@ -130,6 +130,77 @@ def test_segmented_update_entry_points_refuse_bad_arguments(lib):
         assert msg.startswith(name.encode() + b":") and text in msg, (i, name, msg)
 
 
+def test_context_model_entry_points_refuse_bad_arguments(lib):
+    """The context-model path has one entry point per launch sequence; an argument subset is a NULL or a zero.  The refusals that
+    guard a kernel precondition carry the surviving entry point's name.  Nothing can launch on the made-up pointers below: field 1
+    of every gather has a null table, ws_bytes = 0 in every row-sums and sort call, and the CTR head gets a null bias."""
+    p = C.c_void_p(64)      # non-null and 16-byte aligned; never dereferenced
+    INVALID, WORKSPACE = -1, -2
+    ptrs = lambda *v: (C.c_void_p * len(v))(*v)
+    ints = lambda *v: (C.c_int * len(v))(*v)
+    tabs, tabs1, ids, per_row, offs = ptrs(64, None), ptrs(64, 64), ptrs(64, 64), ints(0, 0), (C.c_int64 * 2)(0, 10)
+
+    def gather(tables1=None, out1=None, kind=None, row_flags=None, step_dev=None, F=2, fused=None):
+        args = [tabs, tables1, ids, per_row, kind, -1, offs, F, 4, 1, 16, p, out1, None, row_flags, step_dev, 1]
+        if fused is None:
+            return lib.rc_gather_fields(*args, None)
+        return lib.rc_gather_fields_fused(*args, *fused, None)      # fused = (fm_out, fm_sum, plan_ws, plan_ws_bytes, bump)
+
+    num = (ptrs(64), ints(1), ints(1), ints(0))     # values, per_row, kind (RC_FIELD_F32), field of ONE numeric field
+    no_num = (None, None, None, None)
+    n, F, B = 96, 3, 32
+
+    def sums(src1=None, out1=None, arrays=no_num, n_numeric=0, F=F, B=B, d=16, dW=None, dw1=None):
+        return lib.rc_small_row_sums(p, n, 10, p, d, p, src1, out1, *arrays, n_numeric, F, B, 1, dW, dw1, p, 0, None)
+
+    def planned(src1=None, out1=None, d=16, fm=(None, None, None), F=0, B=0):
+        return lib.rc_small_row_sums_planned(n, 10, p, d, p, src1, out1, *no_num, 0, F, B, 1, None, None, *fm, p, 0, None)
+
+    def head(n=100, g_lin=None, g_bias=None):
+        return lib.rc_ctr_head_fwd_bwd_sums(None, p, 3, None, None, p, n, p, p, p, p, g_lin, g_bias, None, None)
+
+    def sort(ids_b=None, n_b=0, key_offset_b=0, key_range=10):
+        return lib.rc_sort_ids(p, 100, ids_b, n_b, key_offset_b, key_range, p, p, p, 0, None)
+    one = ptrs(64)
+    table = [
+        ("rc_gather_fields", gather, INVALID, b"null table / ids for field 1"),                     # (what stops every valid case below)
+        ("rc_gather_fields", lambda: gather(tables1=tabs1), INVALID, b"come together"),
+        ("rc_gather_fields", lambda: gather(out1=p), INVALID, b"come together"),
+        ("rc_gather_fields", lambda: gather(row_flags=p), INVALID, b"row flags"),
+        ("rc_gather_fields", lambda: gather(kind=ints(7, 0)), INVALID, b"kind[0] = 7"),
+        ("rc_gather_fields", lambda: gather(F=0), INVALID, b"F must be in [1, 48]"),
+        ("rc_gather_fields", lambda: gather(F=49), INVALID, b"F must be in [1, 48]"),
+        ("rc_gather_fields_fused", lambda: gather(fused=(None, None, None, 0, None)), INVALID, b"neither"),
+        ("rc_gather_fields_fused", lambda: gather(fused=(p, None, None, 0, None)), INVALID, b"come together"),
+        ("rc_gather_fields_fused", lambda: gather(row_flags=p, step_dev=p, fused=(p, p, None, 0, p)), INVALID, b"cannot be the counter"),
+        ("rc_gather_fields_fused", lambda: gather(tables1=tabs1, out1=p, fused=(p, p, None, 0, None)), INVALID, b"null table / ids for field 1"),
+        ("rc_small_row_sums", sums, WORKSPACE, b"workspace 0 <"),
+        ("rc_small_row_sums", lambda: sums(src1=p, out1=p), WORKSPACE, b"workspace 0 <"),
+        ("rc_small_row_sums", lambda: sums(src1=p), INVALID, b"src1 / out1 together"),
+        ("rc_small_row_sums", lambda: sums(src1=p, out1=p, n_numeric=1), INVALID, b"null pointer (numeric fields)"),
+        ("rc_small_row_sums", lambda: sums(arrays=num, n_numeric=1, dW=one, dw1=one), INVALID, b"null pointer (numeric fields)"),
+        ("rc_small_row_sums", lambda: sums(src1=p, out1=p, arrays=num, n_numeric=5, F=8, B=12, dW=one, dw1=one), INVALID, b"5 numeric fields"),
+        ("rc_small_row_sums", lambda: sums(src1=p, out1=p, arrays=num, n_numeric=1, B=B - 1, dW=one, dw1=one), INVALID, b"bad shape"),
+        ("rc_small_row_sums", lambda: sums(arrays=num, n_numeric=1, d=4, dW=one, dw1=one), INVALID, b"bad shape"),
+        ("rc_small_row_sums", lambda: sums(src1=p, out1=p, arrays=num, n_numeric=1, dW=one, dw1=one), WORKSPACE, b"workspace 0 <"),
+        ("rc_small_row_sums_planned", lambda: planned(d=4), WORKSPACE, b"workspace 0 <"),         # another source on the same grouping, any width
+        ("rc_small_row_sums_planned", lambda: planned(src1=p, out1=p, fm=(p, p, None), F=F, B=B), INVALID, b"come together"),
+        ("rc_small_row_sums_planned", lambda: planned(d=4, fm=(p, p, p), F=F, B=B), INVALID, b"bad shape"),
+        ("rc_small_row_sums_planned", lambda: planned(src1=p, out1=p, fm=(p, p, p), F=F, B=B), WORKSPACE, b"workspace 0 <"),
+        ("rc_ctr_head_fwd_bwd_sums", head, INVALID, b"null pointer"),
+        ("rc_ctr_head_fwd_bwd_sums", lambda: head(g_lin=p), INVALID, b"g_lin and g_bias come together"),
+        ("rc_ctr_head_fwd_bwd_sums", lambda: head(n=65537), INVALID, b"n=65537"),
+        ("rc_sort_ids", sort, WORKSPACE, b"workspace 0 <"),
+        ("rc_sort_ids", lambda: sort(n_b=5), INVALID, b"null pointer"),
+        ("rc_sort_ids", lambda: sort(ids_b=p, n_b=5, key_offset_b=10), INVALID, b"out of range"),
+    ]
+    for i, (name, call, code, text) in enumerate(table):
+        got = call()
+        msg = lib.rc_last_error_string()
+        assert got == code, (i, name, got, msg)
+        assert msg.startswith(name.encode() + b":") and text in msg, (i, name, msg)
+
+
 def test_sasrec_shape_envelope(lib):
     """rc_sasrec_supported is host logic: d in {32, 64}, 1..4 blocks, heads | d, history_max <= 64 on every route; 65..128 with ONE
     block and 1 / 2 / 4 heads (the batch encoder's one-row path).  engine.sasrec_supported adds: no training-mode dropout there."""

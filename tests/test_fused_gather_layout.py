@@ -62,7 +62,7 @@ def test_field_major_chunks_enumerate_every_occurrence_once(n_rows, F, C, numeri
             seen[pos] = key
             assert last_pos.get(key, -1) < pos      # the overflow path emits a key's positions in scan order: they must ascend
             last_pos[key] = pos
-    # what the gather writes into cid for the same occurrences (rc_gather_fields_mixed: cid[r, f] = row_offset[f] + id)
+    # what the gather writes into cid for the same occurrences (rc_gather_fields: cid[r, f] = row_offset[f] + id)
     want = {r * F + f: int(row_offset[f] + ids[f][r // C if per_row[f] else r]) for r in range(n_rows) for f in range(F) if f not in numeric}
     assert seen == want
 

@@ -276,7 +276,7 @@ def _numeric_values(rng, dtype, shape):
 
 @pytest.mark.parametrize("d,B,C", [(64, 48, 1), (16, 33, 5), (6, 7, 3), (32, 1024, 1), (64, 3000, 1), (32, 700, 4), (128, 9000, 2)])
 def test_numeric_fields_ride_in_the_gather_and_get_linear_gradients(d, B, C, cuda, monkeypatch):
-    """rc_gather_fields_mixed / rc_numeric_field_grads: a field list with numeric features (nn.Linear(1, d) / nn.Linear(1, 1) on
+    """rc_gather_fields with kinds / rc_numeric_field_grads: a field list with numeric features (nn.Linear(1, d) / nn.Linear(1, 1) on
     the value, models/context/FM.py:38-41,47-48,51-52) in int64 / float32 / float64, per row and per candidate, against torch's
     own Embedding / Linear ops in float64 -- one gather launch, one weighted column sum, every grouping route (small plan,
     sort with the numeric tail, more than one chunk of 1,024 rows)"""
@@ -294,9 +294,9 @@ def test_numeric_fields_ride_in_the_gather_and_get_linear_gradients(d, B, C, cud
             else _numeric_values(rng, dt[k], (B,) if pr else (B, C))).to(cuda) for k, v, pr in spec]
     kinds = [k for k, _, _ in spec]
     assert [engine.FIELD_IDS if k == engine.FIELD_IDS else engine.field_kind(x) for k, x in zip(kinds, ids)] == kinds
-    names = []
+    calls = []
     real = _lib.call
-    monkeypatch.setattr(_lib, "call", lambda fn, *a: names.append(fn) or real(fn, *a))
+    monkeypatch.setattr(_lib, "call", lambda fn, *a: calls.append((fn, a)) or real(fn, *a))
     V, L = hnn.gather_fields_pair(vec, lin, ids, C, kinds=kinds)
     wv, wl = torch.randn_like(V), torch.randn_like(L)
     ((V * wv).sum() + (L * wl).sum()).backward()
@@ -304,10 +304,13 @@ def test_numeric_fields_ride_in_the_gather_and_get_linear_gradients(d, B, C, cud
     # the Linear weights' gradients: riding in the small route's row-sums launch, or rc_numeric_field_grads on its own (large batches)
     rides = B * C * F <= 8192 and d in (16, 32, 64, 128)
     # small batches: the grouping of the composite keys runs inside the gather's launch (rc_gather_fields_fused), the backward is ONE launch
-    assert names.count("rc_gather_fields_fused" if rides else "rc_gather_fields_mixed") == 1
+    # -- exactly one gather launch, the fused one or the plain one, with both table families and the field kinds in its arguments
+    names = [fn for fn, _ in calls]
+    gathers = [(fn, a) for fn, a in calls if fn.startswith("rc_gather_fields")]
+    assert [fn for fn, _ in gathers] == ["rc_gather_fields_fused" if rides else "rc_gather_fields"], names
+    assert gathers[0][1][1] is not None and list(gathers[0][1][4]) == kinds          # tables1, kind
     assert names.count("rc_small_row_sums_planned") == (1 if rides else 0) and names.count("rc_numeric_field_grads") == (0 if rides else 1), names
-    assert not any(n in names for n in ("rc_gather_fields", "rc_gather_fields_pair", "rc_gather_rows", "rc_small_row_sums_pair_numeric",
-                                        "rc_small_row_sums_pair", "rc_small_row_sums")), names
+    assert not any(n in names for n in ("rc_gather_rows", "rc_small_row_sums")), names
     assert V.shape == (B, C, F, d) and L.shape == (B, C, F, 1)
     # what the reference computes, field by field (FM.py:47-55), in float64 from the same fp32 inputs
     bc = lambda t: t if t.dim() == 3 else t.unsqueeze(-2).expand(-1, C, -1)
@@ -343,7 +346,7 @@ def test_numeric_fields_ride_in_the_gather_and_get_linear_gradients(d, B, C, cud
 def test_fm_term_and_plan_inside_the_gather_launch(d, B, C, numeric, tower, cuda, monkeypatch):
     """rc_gather_fields_fused / rc_small_row_sums_planned: the FM pairwise term (models/context/FM.py:61) formed in the gather's
     launch is rc_fm_second_order_fwd's value bit for bit; its backward folded into the row sums (on the grouping the gather's launch
-    left behind) gives the gradients of the three-launch route -- rc_fm_second_order_bwd_add, grouping, row sums -- bit for bit,
+    left behind) gives the gradients of the three-launch route -- rc_fm_second_order_bwd with add, grouping, row sums -- bit for bit,
     and both agree with torch's own ops in float64.  tower: a second consumer of the field vectors (DeepFM) sends a gradient too."""
     from rechorus_amd import _lib, engine, nn as hnn
     rng = np.random.default_rng(d * 7919 + B + C)
@@ -358,9 +361,9 @@ def test_fm_term_and_plan_inside_the_gather_launch(d, B, C, numeric, tower, cuda
     ids = [(torch.from_numpy(rng.integers(0, v, size=(B,) if pr else (B, C)).astype(np.int64)) if k == engine.FIELD_IDS
             else _numeric_values(rng, dt[k], (B,) if pr else (B, C))).to(cuda) for k, v, pr in spec]
     kinds = [k for k, _, _ in spec] if numeric else None
-    names = []
+    calls = []
     real = _lib.call
-    monkeypatch.setattr(_lib, "call", lambda fn, *a: names.append(fn) or real(fn, *a))
+    monkeypatch.setattr(_lib, "call", lambda fn, *a: calls.append((fn, a)) or real(fn, *a))
     V, L, fm = hnn.gather_fields_pair(vec, lin, ids, C, kinds=kinds, fm=True)
     wv, wl, wf = torch.randn_like(V) * (1.0 if tower else 0.0), torch.randn_like(L), torch.randn_like(fm)
     loss = (L * wl).sum() + (fm * wf).sum()
@@ -369,15 +372,18 @@ def test_fm_term_and_plan_inside_the_gather_launch(d, B, C, numeric, tower, cuda
     loss.backward()
     monkeypatch.undo()
     small, lanes = B * C * F <= 8192, d in (16, 32, 64, 128)
+    names = [fn for fn, _ in calls]
     if lanes:
         assert names.count("rc_gather_fields_fused") == 1 and "rc_fm_second_order_fwd" not in names, names
     else:
         assert names.count("rc_fm_second_order_fwd") == 1 and "rc_gather_fields_fused" not in names, names
     if small and lanes:     # one launch forward, one launch backward
-        assert names.count("rc_small_row_sums_planned") == 1 and "rc_fm_second_order_bwd" not in names and "rc_fm_second_order_bwd_add" not in names, names
+        assert names.count("rc_small_row_sums_planned") == 1 and "rc_fm_second_order_bwd" not in names, names
         assert not any(n.startswith("rc_small_row_sums") and n != "rc_small_row_sums_planned" and not n.endswith("_bytes") and not n.endswith("_supported") for n in names), names
     else:
-        assert names.count("rc_fm_second_order_bwd_add" if tower else "rc_fm_second_order_bwd") == 1, names
+        bwd = [a for fn, a in calls if fn == "rc_fm_second_order_bwd"]
+        assert len(bwd) == 1, names
+        assert bool(bwd[0][5].value) == tower, "the tower's gradient rides as `add` exactly when there is a tower"
     got = {"vec": [t.grad.clone() for t in vec], "lin": [t.grad.clone() for t in lin]}
     # ---- the separate kernels on the same inputs: bit for bit
     assert torch.equal(fm, engine.fm_second_order(V.detach())), "FM term differs from rc_fm_second_order_fwd"
@@ -394,13 +400,14 @@ def test_fm_term_and_plan_inside_the_gather_launch(d, B, C, numeric, tower, cuda
         assert torch.equal(got["vec"][f], vec[f].grad), f"field {f}: vector gradient differs from the separate kernels"
         assert torch.equal(got["lin"][f], lin[f].grad), f"field {f}: first-order gradient differs from the separate kernels"
     if small and lanes:
-        # ---- the grouping the gather's launch leaves behind against the plan launch of rc_small_row_sums_pair(_numeric)
+        # ---- the grouping the gather's launch leaves behind against the plan launch of rc_small_row_sums
         kd = [k for k, _, _ in spec]
         num = [f for f in range(F) if kd[f] != engine.FIELD_IDS]
         with torch.no_grad():
-            Vd, Ld, cid, offs, _, _, ws = engine.gather_fields([t.detach() for t in vec], ids, C, tables1=[t.detach() for t in lin], kinds=kd,
-                                                              numeric_key=-1, plan=True)
-            n, n_rows = cid.numel(), offs[-1]
+            res = engine.gather_fields([t.detach() for t in vec], ids, C, tables1=[t.detach() for t in lin], kinds=kd, numeric_key=-1, plan=True)
+            assert res.fm_term is None and res.fm_sum is None and res.out1 is not None
+            cid, ws = res.cid, res.plan_ws
+            n, n_rows = cid.numel(), res.offsets[-1]
             gv, gl = torch.randn(n, d, device=cuda), torch.randn(n, 1, device=cuda)
             riding = ([ids[f] for f in num], num, F, C) if num else None
             a = engine.small_row_sums_planned(ws, n, n_rows, gv, gl, d, (F, B, C), numeric=riding)
@@ -452,8 +459,8 @@ def test_numeric_field_model_path_uses_no_torch_stack_or_cat(cuda, monkeypatch):
     assert "loss" in out, "the one-kernel CTR head did not run"
     # (B = 48: the small route -- the gather's launch also forms the FM term and groups the keys, ONE row-sums launch backward)
     assert names.count("rc_gather_fields_fused") == 1 and names.count("rc_small_row_sums_planned") == 1, names
-    assert not any(n in names for n in ("rc_numeric_field_grads", "rc_fm_second_order_fwd", "rc_fm_second_order_bwd", "rc_fm_second_order_bwd_add",
-                                        "rc_small_row_sums_pair_numeric", "rc_gather_fields_mixed")), names
+    assert not any(n in names for n in ("rc_numeric_field_grads", "rc_fm_second_order_fwd", "rc_fm_second_order_bwd", "rc_small_row_sums",
+                                        "rc_gather_fields")), names
     assert any(n.startswith("rc_ctr_head_fwd_bwd") for n in names), names
     assert_close(out["loss"].item(), g["loss"], what="loss", rtol=2e-5)
 
@@ -488,8 +495,8 @@ def test_two_table_families_share_keys_and_grouping(cuda, monkeypatch):
         wv, wl = torch.randn_like(V), torch.randn_like(L)
         ((V * wv).sum() + (L * wl).sum()).backward()
         monkeypatch.undo()
-        assert names.count("rc_gather_fields_fused") == 1 and "rc_gather_fields" not in names and "rc_gather_fields_pair" not in names
-        assert names.count("rc_small_row_sums_planned") == 1 and "rc_small_row_sums" not in names and "rc_small_row_sums_pair" not in names, names
+        assert names.count("rc_gather_fields_fused") == 1 and "rc_gather_fields" not in names
+        assert names.count("rc_small_row_sums_planned") == 1 and "rc_small_row_sums" not in names, names
         got = [t.grad.clone() for t in vec + lin]
         for t in vec + lin:
             t.grad = None

@@ -173,16 +173,16 @@ def ctx_root(tmp_path_factory):
 CTX_CASES = [
     # (name, mode[:f = the dataset with numeric features], flags, entry points that must run, entry points that must NOT, CTR head)
     ("DeepFM", "CTR", ["--emb_size", "16", "--layers", "[32,16]", "--dropout", "0.2"], {"rc_gather_fields_fused", "rc_small_row_sums_planned"},
-     {"rc_fm_second_order_fwd", "rc_fm_second_order_bwd", "rc_fm_second_order_bwd_add", "rc_gather_fields_pair"}, r"rc_ctr_head_fwd_bwd(_sums)?"),
+     {"rc_fm_second_order_fwd", "rc_fm_second_order_bwd", "rc_gather_fields"}, r"rc_ctr_head_fwd_bwd(_sums)?"),
     ("DeepFM", "TopK", ["--emb_size", "16", "--layers", "[32]", "--dropout", "0"], {"rc_gather_fields_fused", "rc_small_row_sums_planned"},
-     {"rc_fm_second_order_fwd", "rc_fm_second_order_bwd_add"}, None),
+     {"rc_fm_second_order_fwd", "rc_fm_second_order_bwd"}, None),
     ("FM", "CTR", ["--emb_size", "16"], {"rc_gather_fields_fused", "rc_small_row_sums_planned"}, {"rc_fm_second_order_fwd", "rc_fm_second_order_bwd"},
      r"rc_ctr_head_fwd_bwd(_sums)?"),
     ("WideDeep", "CTR", ["--emb_size", "16", "--layers", "[32]", "--dropout", "0.1"], {"rc_gather_fields_fused", "rc_small_row_sums_planned"}, set(),
      r"rc_ctr_head_fwd_bwd(_sums)?"),
     # the same heads over a field list with numeric features (Linear(1, d) on c_day_f / i_age_f, as models/context/FM.py:38-41 does)
     ("DeepFM", "CTR:f", ["--emb_size", "16", "--layers", "[32,16]", "--dropout", "0.2"], {"rc_gather_fields_fused", "rc_small_row_sums_planned"},
-     {"rc_numeric_field_grads", "rc_fm_second_order_bwd_add", "rc_gather_fields_mixed"}, r"rc_ctr_head_fwd_bwd(_sums)?"),
+     {"rc_numeric_field_grads", "rc_fm_second_order_bwd", "rc_gather_fields"}, r"rc_ctr_head_fwd_bwd(_sums)?"),
     ("FM", "TopK:f", ["--emb_size", "16"], {"rc_gather_fields_fused", "rc_small_row_sums_planned"}, {"rc_numeric_field_grads", "rc_fm_second_order_fwd"}, None),
 ]
 

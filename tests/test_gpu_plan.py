@@ -552,6 +552,40 @@ def test_small_embedding_dense_backward(n, n_rows, d, hot, cuda, eng, monkeypatc
         assert np.all(np.abs(got - out[False].cpu().numpy()) <= 2 * tol)
 
 
+@pytest.mark.parametrize("n,n_rows,hot", [(777, 1000, 0), (8192, 40, 7000)])
+def test_small_row_sums_of_two_narrow_sources_share_one_grouping(n, n_rows, hot, cuda, eng, monkeypatch):
+    """two sources [n, 4] and [n, 1] with the same ids, neither of which can ride in the other's launch: small_row_sums_pair
+    (rc_small_row_sums, then rc_small_row_sums_planned on its workspace) == two embedding_dense_backward calls that each group the
+    ids == one that groups them and one with small_again=True on the same workspace -- the same kernels on the same grouping, so
+    bit for bit (the float64 correctness of these widths: test_small_embedding_dense_backward)"""
+    from rechorus_amd import _lib
+    rng = np.random.default_rng(n + 4)
+    ids = rng.integers(0, n_rows, size=n).astype(np.int64)
+    if hot:
+        ids[rng.permutation(n)[:hot]] = n_rows // 2
+    ids_d = torch.from_numpy(ids).to(cuda)
+    src_a = torch.from_numpy(rng.normal(size=(n, 4)).astype(np.float32)).to(cuda)
+    src_b = torch.from_numpy(rng.normal(size=(n, 1)).astype(np.float32)).to(cuda)
+    monkeypatch.setattr(eng, "_EDB_SMALL", True)
+    names = []
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda fn, *a: names.append(fn) or real(fn, *a))
+    Ga, Gb = eng.small_row_sums_pair(ids_d, n_rows, src_a, src_b)
+    assert names == ["rc_small_row_sums", "rc_small_row_sums_planned"], names
+    del names[:]
+    two = [eng.embedding_dense_backward(s, ids_d, n_rows, route="small") for s in (src_a, src_b)]
+    assert names == ["rc_small_row_sums", "rc_small_row_sums"], names
+    del names[:]
+    t = "edb_small_two_sources"
+    again = [eng.embedding_dense_backward(src_a, ids_d, n_rows, route="small", small_tag=t),
+             eng.embedding_dense_backward(src_b, ids_d, n_rows, route="small", small_again=True, small_tag=t)]
+    assert names == ["rc_small_row_sums", "rc_small_row_sums_planned"], names
+    monkeypatch.undo()
+    assert Ga.shape == (n_rows, 4) and Gb.shape == (n_rows, 1) and bool(Ga.any()) and bool(Gb.any())
+    for what, (Xa, Xb) in (("two groupings", two), ("small_again", again)):
+        assert torch.equal(Ga, Xa) and torch.equal(Gb, Xb), what
+
+
 def test_neumf_trainer_plan_on_second_stream_equals_one_stream(cuda, eng, monkeypatch):
     """NeumfTrainer builds the batch's bucket plan on a second stream beside the head kernels (large batches); same kernels, same
     inputs: three row-wise Adam steps leave every table, dense parameter and optimizer state bit-identical to the one-stream order"""
@@ -664,7 +698,7 @@ def test_hand_written_radix_sort_is_the_stable_sort(n, n_rows, cuda, eng):
 
 
 def test_two_lists_sorted_as_one(cuda, eng):
-    """rc_sort_ids2: item ids and (offset) user ids of a step as one virtual list -- the user keys form the tail"""
+    """rc_sort_ids with two lists: item ids and (offset) user ids of a step as one virtual list -- the user keys form the tail"""
     import ctypes as C
     from rechorus_amd import _lib
     rng = np.random.default_rng(7)
@@ -674,7 +708,7 @@ def test_two_lists_sorted_as_one(cuda, eng):
     keys = torch.empty(n_a + n_b, dtype=torch.int32, device=cuda)
     perm = torch.empty(n_a + n_b, dtype=torch.int32, device=cuda)
     ws = torch.empty(_lib.load().rc_sort_workspace_bytes(n_a + n_b), dtype=torch.uint8, device=cuda)
-    _lib.call("rc_sort_ids2", C.c_void_p(ad.data_ptr()), n_a, C.c_void_p(bd.data_ptr()), n_b, n_items, n_items + n_users,
+    _lib.call("rc_sort_ids", C.c_void_p(ad.data_ptr()), n_a, C.c_void_p(bd.data_ptr()), n_b, n_items, n_items + n_users,
               C.c_void_p(keys.data_ptr()), C.c_void_p(perm.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
               C.c_void_p(torch.cuda.current_stream().cuda_stream))
     joint = np.concatenate([a, n_items + b])

@@ -1,7 +1,7 @@
 """GPU: the entry points round 6 added, each against the call sequence it replaces, bit for bit --
 rc_gather_rows_pair (two rc_gather_rows + a concatenation), rc_plan_update_pair with caller-zeroed counters (the update without its
 memset) and with a block source (the same update reading both gradients from one strided block),
-rc_sasrec_batch_bwd_part (the backward pass of rc_sasrec_batch_bwd in two calls), rc_ctr_head_fwd_full (rc_ctr_head_fwd_bwd_sums
+rc_sasrec_batch_bwd_part (the backward pass of rc_sasrec_batch_bwd in two calls), rc_ctr_head_fwd_bwd_sums with g_lin / g_bias / bump (the same call without them
 + rc_ctr_head_bwd for a seed gradient of one, and the counter that rides along).  The fused field gather and the planned row sums
 have their own tests in test_gpu_deepfm.py.
 Reference semantics: models/general/NeuMF.py:39-42,61-66 (the two table families of a side), helpers/BaseRunner.py:193-206 (the

@@ -1,4 +1,4 @@
-"""HipOptimizer's rows mode (rc_gather_fields_pair_mark + rc_dense_update_rows_dev): torch.optim.Adam over the dense gradients of
+"""HipOptimizer's rows mode (rc_gather_fields with row_flags + rc_dense_update_rows_dev): torch.optim.Adam over the dense gradients of
 embedding tables (helpers/BaseRunner.py:110-114,206; the tables of models/context/FM.py:33-41) without the dense gradient: the
 rows the batch touched carry the step's stamp and a row sum, the rest take g = 0.  It must be invisible: bit-identical parameters
 and optimizer state to the dense step."""

@@ -60,7 +60,7 @@ def test_rows_mode_protocol_reproduces_dense_adam(monkeypatch):
         assert mark is not None
         flags, step_dev = mark
         assert int(step_dev.item()) == step - 1 and flags.numel() == n_rows
-        for f, x in enumerate(ids):                       # what rc_gather_fields_pair_mark does
+        for f, x in enumerate(ids):                       # what rc_gather_fields does with row_flags
             flags[offs[f] + x] = int(step_dev.item()) + 1
         # the backward pass: row sums of the touched rows into the scratch, everything else left as it was (here: NaN)
         scratch = opt.rows_scratch()

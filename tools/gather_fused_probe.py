@@ -61,8 +61,9 @@ def main():
     res["+ FM term"] = timed(lambda: engine.gather_fields(tables, ids, 1, tables1=tables1, kinds=kinds, fm=True))
     res["+ plan"] = timed(lambda: engine.gather_fields(tables, ids, 1, tables1=tables1, kinds=kinds, plan=True))
     res["+ FM term + plan"] = timed(lambda: engine.gather_fields(tables, ids, 1, tables1=tables1, kinds=kinds, fm=True, plan=True))
-    V, L, cid, offs, fm, S, ws = engine.gather_fields(tables, ids, 1, tables1=tables1, kinds=kinds, fm=True, plan=True)
-    n, n_rows = cid.numel(), offs[-1]
+    r = engine.gather_fields(tables, ids, 1, tables1=tables1, kinds=kinds, fm=True, plan=True)
+    V, S, cid, ws = r.out, r.fm_sum, r.cid, r.plan_ws
+    n, n_rows = cid.numel(), r.offsets[-1]
     gv, gl, gf = torch.randn(n, d, device=dev), torch.randn(n, 1, device=dev), torch.randn(B, device=dev)
     into = torch.empty(n_rows * (d + 1), device=dev)
     num = [f for f in range(F) if kinds[f] != engine.FIELD_IDS]
