@@ -73,8 +73,6 @@ __global__ __launch_bounds__(256) void bench_mfma_kernel(int iters, float a0, fl
   if (t == 12345.678f) sink[0] = t;   // keeps the accumulators alive
 }
 
-int device_cus();   // bucket_plan.hip
-
 }  // namespace rc
 
 using namespace rc;

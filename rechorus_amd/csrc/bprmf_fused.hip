@@ -25,6 +25,7 @@
 // rc_segment_heads on the sorted ids in the sort pipeline); rows with several occurrences are left to
 // the plan-driven row update (plan_update.hip; seg_update.hip in the sort pipeline).  The kernel body
 // lives in fused_body.hpp: small_front_kernel below runs it beside the small-batch plan workgroups.
+#include "bprmf_step.hpp"
 #include "fused_body.hpp"
 #include "small_plan.hpp"
 
@@ -296,16 +297,15 @@ extern "C" int rc_bprmf_fwd_bwd_update(const float* U, float* I, float* mI, floa
 
 namespace rc {
 // first launch of the small-batch step; the caller (train_step.hip) checked rc_bprmf_fused_supported(d, C)
-int small_front_launch(const float* U, const float* I, const int64_t* uid, const int64_t* iid, int B, int C, int d, float inv_b,
-                       float* pred, float* loss_vec, float* gpred, float* ugrad, float* ub, const SmallPlanArgs& plan,
-                       hipStream_t s) {
-  RC_REQUIRE(aligned16(U, I, ugrad, ub) && register_path_ok(d, C),
+int small_front_launch(const BprmfStep& st, float* ub, const SmallPlanArgs& plan) {
+  const int d = st.d, C = st.C;
+  RC_REQUIRE(aligned16(st.U, st.I, st.ugrad, ub) && register_path_ok(d, C),
              "small-batch step: unsupported shape or alignment (d=%d C=%d)", d, C);
   FusedCall f;
   memset(&f, 0, sizeof(f));
-  f.U = U; f.I = I; f.uid = uid; f.iid = iid; f.B = B; f.C = C; f.inv_b = inv_b;
-  f.pred = pred; f.loss_vec = loss_vec; f.gpred = gpred; f.ugrad = ugrad;
-  f.mode = MODE_NONE; f.s = s; f.small = &plan; f.ub = ub; f.who = "rc_bprmf_train_step";
+  f.U = st.U; f.I = st.I; f.uid = st.uid; f.iid = st.iid; f.B = st.B; f.C = C; f.inv_b = st.inv_b;
+  f.pred = st.pred; f.loss_vec = st.loss_vec; f.gpred = st.gpred; f.ugrad = st.ugrad;
+  f.mode = MODE_NONE; f.s = st.s; f.small = &plan; f.ub = ub; f.who = "rc_bprmf_train_step";
   bool handled = false;
   const int rc_ = run_fused(f, d, &handled);
   if (!handled) return fail(RC_ERR_UNSUPPORTED, "small-batch step: dispatch failed (d=%d C=%d)", d, C);

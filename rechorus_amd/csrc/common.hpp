@@ -88,6 +88,8 @@ constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kBlock = 256;        // default workgroup: 4 waves, one per SIMD
 constexpr int kMaxGridX = 1 << 30;
 
+int device_cus();  // compute units of the current device, asked once per process (defined in bucket_plan.hip)
+
 // ---- device helpers ----------------------------------------------------------------
 #if defined(__HIPCC__)
 

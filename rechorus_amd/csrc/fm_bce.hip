@@ -577,10 +577,8 @@ static int gather_fields_fused_launch(const FieldArgs& a, bool vec, bool mixed, 
       return fail(RC_ERR_UNSUPPORTED, "rc_gather_fields_fused: %lld keys are not a small batch (<= %d) or the LDS of this device is too small", (long long)n_keys, kSmallMaxKeys);
     if (plan_ws_bytes < rc_small_row_sums_workspace_bytes(n_keys))
       return fail(RC_ERR_WORKSPACE, "rc_gather_fields_fused: plan workspace %zu < %zu", plan_ws_bytes, rc_small_row_sums_workspace_bytes(n_keys));
-    Carver cv(plan_ws);     // the layout rc_small_row_sums_planned reads (small_step.hip)
-    p.rows = cv.take<rc_plan_row>((size_t)kSmallPlanWgs * (size_t)n_keys);
-    p.occ = cv.take<uint32_t>((size_t)kSmallPlanWgs * (size_t)n_keys);
-    p.cnt = cv.take<SmallCnt>(kSmallPlanWgs);
+    const SmallPlanWs pw = carve_small_plan_ws(plan_ws, n_keys);     // what rc_small_row_sums_planned reads (small_step.hip)
+    p.rows = pw.rows; p.occ = pw.occ; p.cnt = pw.cnt;
     p.n_a = (uint32_t)n_keys; p.n = (uint32_t)n_keys; p.base_b = 0xFFFFFFFFu;     // one list: every key is a row of it
   }
   const int64_t total = a.n * (d / 4);

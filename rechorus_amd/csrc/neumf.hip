@@ -24,6 +24,7 @@
 // neumf_reduce_partials_kernel (deterministic, no float atomics).  Table-row gradients are
 // written per occurrence ([B*C, d] x 4) and consumed by rc_segmented_update_pair (mf / mlp table of a side in one pass).
 #include "common.hpp"
+#include "neumf.hpp"
 #include "philox.hpp"
 
 namespace rc {

@@ -31,6 +31,7 @@
 // Dense gradients leave as per-workgroup partials, summed in fixed order by neumf_reduce_partials_kernel.
 #include "bpr_math.hpp"
 #include "common.hpp"
+#include "neumf.hpp"
 #include "opt_math.hpp"
 #include "philox.hpp"
 
@@ -669,10 +670,6 @@ __global__ __launch_bounds__(256) void neumf_unmark_kernel(const int64_t* __rest
   if ((uint64_t)id < n_items) multi[id] = 0;
 }
 
-// (defined in neumf.hip) out[i] = sum_w p[w][i] for the three partial arrays, fixed order
-int neumf_reduce_partials(const float* pW1, const float* pb1, const float* pwout, float* dW1, float* db1, float* dw_out, int cW, int cb,
-                          int co, int n_wg, hipStream_t s);
-
 static size_t step_lds_bytes(int d, int l1, int C) {
   const size_t k0 = 2 * (size_t)d;
   const size_t fixed = (size_t)l1 * (k0 + 4) + l1 + (d + l1) + 4 * (2 * (size_t)l1 + d);
@@ -688,8 +685,6 @@ static bool step_shape(int d, int l1) {
   if (l1 == 16) return d != 32;      // (the dW1u tiles are dealt to four waves: 16 (d / 16) / 16 tiles must be a multiple of 4)
   return false;
 }
-
-int device_cus();   // bucket_plan.hip
 
 static int step_grid(int B) {
   const int64_t rounds = ((int64_t)B + 63) / 64;

@@ -102,6 +102,8 @@ int plan_launch(const PlanArgs& a, hipStream_t s, hipEvent_t* ev_after_scatter);
 int plan_launch_front(const PlanArgs& a, bool bitmap, hipStream_t s);
 constexpr size_t kPlanBitmapWords = (size_t)kPlanMaxBuckets << (kPlanMaxShift - 5);   // capacity that fits every geometry
 int plan_launch_back(const PlanArgs& a, hipStream_t s);
+// once per device before the first plan_launch*: the dynamic-LDS limits of the plan kernels (function attributes are per device)
+int plan_prepare();
 
 // ---- consumers --------------------------------------------------------------------------------------
 struct PlanTable { float* W; float* M; float* V; };
@@ -122,8 +124,5 @@ struct PlanGrad {
   uint32_t pair_ld4;   // pair mode: row stride of src2 / src2b in float4 units (0: D / 8, two contiguous [n, D / 2] arrays) -- both
                        // halves of one [n, ld] block, e.g. the (d mf | d mlp) gradient rows a sharded NeuMF rank receives
 };
-
-
-int device_cus();
 
 }  // namespace rc

@@ -13,6 +13,7 @@
 //                       (row record + chunk list, integer atomics only) and left to:
 //   plan_chunk_kernel   one workgroup per 256-occurrence chunk, fixed LDS tree -> partial sums
 //   plan_final_kernel   chunk partials of a row combined in chunk order, optimizer, row written
+#include "bprmf_step.hpp"
 #include "plan.hpp"
 
 namespace rc {
@@ -486,39 +487,36 @@ static int launch_step_updates(const PlanUpdArgs& a, int64_t n_occ, hipStream_t 
 
 // The three update launches of a BPRMF step (train_step.hip): item rows, chunks of hot rows, user rows + hot rows
 // + loss mean.  Item-side gradients read pre-step U rows, so every read of U precedes the last launch.
-int plan_bprmf_step_updates(float* U, float* mU, float* vU, float* I, float* mI, float* vI, int d, const int64_t* uid,
-                            int C, int64_t n_i, int64_t B, const float* gpred, const float* ugrad,
-                            const rc_plan_row* rows_i, const uint32_t* n_rows_i, const rc_plan_row* rows_u,
-                            const uint32_t* n_rows_u, const uint32_t* occ, uint32_t* counters,
-                            const PlanLongWs& lw, bool long_planned,
-                            const rc_opt_hyper* h, const float* loss_vec, float loss_scale, float* loss_out,
-                            hipStream_t s, hipEvent_t* ev_items_done) {
+int plan_bprmf_step_updates(const BprmfStep& st, const rc_plan_row* rows_i, const uint32_t* n_rows_i, const rc_plan_row* rows_u,
+                            const uint32_t* n_rows_u, const uint32_t* occ, uint32_t* counters, const PlanLongWs& lw,
+                            bool long_planned, hipEvent_t* ev_items_done) {
+  const int64_t n_i = st.n_i();
+  const int d = st.d;
+  hipStream_t s = st.s;
   PlanUpdArgs a;
   memset(&a, 0, sizeof(a));
   a.long_planned = long_planned ? 1 : 0;
   a.chunk = kPlanChunk;
-  RC_TRY(fill_opt_scalars("rc_bprmf_train_step", h, &a.o));
-  const int mode = mode_of(h);
-  RC_TRY(opt_state_check("rc_bprmf_train_step", mode, mU && mI, vU && vI));
-  a.side[0].t = PlanTable{I, mI, vI};
-  a.side[0].g = PlanGrad{gpred, U, uid, C, nullptr, 0xFFFFFFFFu, nullptr, 0};
+  a.o = st.o;
+  a.side[0].t = PlanTable{st.I, st.mI, st.vI};
+  a.side[0].g = PlanGrad{st.gpred, st.U, st.uid, st.C, nullptr, 0xFFFFFFFFu, nullptr, 0};
   a.side[0].rows = rows_i;
   a.side[0].n_rows = n_rows_i;
-  a.side[1].t = PlanTable{U, mU, vU};
-  a.side[1].g = PlanGrad{nullptr, nullptr, nullptr, 1, ugrad, (uint32_t)n_i, nullptr, 0};  // user occurrence p = n_i + b -> ugrad[b]
+  a.side[1].t = PlanTable{st.U, st.mU, st.vU};
+  a.side[1].g = PlanGrad{nullptr, nullptr, nullptr, 1, st.ugrad, (uint32_t)n_i, nullptr, 0};  // user occurrence p = n_i + b -> ugrad[b]
   a.side[1].rows = rows_u;
   a.side[1].n_rows = n_rows_u;
   a.occ = occ;
   a.counters = counters;
   a.lw = lw;
-  a.loss_vec = loss_vec;
-  a.loss_n = B;
-  a.loss_scale = loss_scale;
-  a.loss_out = loss_out;
-  return dispatch_or_fail<MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_bprmf_train_step", "update mode", mode, [&](auto M) {
+  a.loss_vec = st.loss_vec;
+  a.loss_n = st.B;
+  a.loss_scale = st.inv_b;
+  a.loss_out = st.loss_out;
+  return dispatch_or_fail<MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_bprmf_train_step", "update mode", st.mode, [&](auto M) {
     constexpr int MODE = M;
     int rc = RC_OK;
-    if (dispatch_int<16, 32, 64, 128>(d, &rc, [&](auto D) { return launch_step_updates<D(), MODE>(a, n_i + B, s, ev_items_done); }))
+    if (dispatch_int<16, 32, 64, 128>(d, &rc, [&](auto D) { return launch_step_updates<D(), MODE>(a, n_i + st.B, s, ev_items_done); }))
       return rc;
     return fail(RC_ERR_UNSUPPORTED, "plan update: d=%d (16/32/64/128)", d);
   });

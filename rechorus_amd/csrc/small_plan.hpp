@@ -51,6 +51,24 @@ struct SmallPlanArgs {
   SmallCnt* cnt;          // [kSmallPlanWgs]
 };
 
+// the plan's three output arrays in a caller's workspace -- THE layout: whoever writes a small plan (small_step.hip,
+// rc_gather_fields_fused in fm_bce.hip) and whoever reads one (rc_small_row_sums_planned) carve it here
+struct SmallPlanWs {
+  rc_plan_row* rows;      // [kSmallPlanWgs][n]
+  uint32_t* occ;          // [kSmallPlanWgs][n]
+  SmallCnt* cnt;          // [kSmallPlanWgs]
+  size_t total;
+};
+inline SmallPlanWs carve_small_plan_ws(void* base, int64_t n) {
+  Carver cv(base);
+  SmallPlanWs w;
+  w.rows = cv.take<rc_plan_row>((size_t)kSmallPlanWgs * (size_t)n);
+  w.occ = cv.take<uint32_t>((size_t)kSmallPlanWgs * (size_t)n);
+  w.cnt = cv.take<SmallCnt>(kSmallPlanWgs);
+  w.total = cv.off;
+  return w;
+}
+
 #ifdef RC_X_TIMING
 #define RC_T(k) do { if (threadIdx.x == 0 && w == 0) tstamp[k] = wall_clock64(); } while (0)
 #else

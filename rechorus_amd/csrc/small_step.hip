@@ -14,15 +14,12 @@
 // Reference semantics: helpers/BaseRunner.py:193-206 around models/general/BPRMF.py:34-45, models/BaseModel.py:182-185.
 #include <mutex>
 
+#include "bprmf_step.hpp"
 #include "opt_math.hpp"
 #include "small_plan.hpp"
 #include "numeric_grads.hpp"
 
 namespace rc {
-
-int small_front_launch(const float* U, const float* I, const int64_t* uid, const int64_t* iid, int B, int C, int d, float inv_b,
-                       float* pred, float* loss_vec, float* gpred, float* ugrad, float* ub, const SmallPlanArgs& plan,
-                       hipStream_t s);
 
 struct SmallUpdArgs {
   float *I, *mI, *vI, *U, *mU, *vU;
@@ -411,50 +408,40 @@ __global__ __launch_bounds__(kBlock) void small_row_sums_narrow_kernel(SmallSumA
   }
 }
 
-// workspace of the small-batch step beyond gpred / ugrad / loss_vec
+// workspace of the small-batch step beyond gpred / ugrad / loss_vec: the user-row snapshot, then the plan
 size_t small_step_extra_bytes(int64_t n, int64_t B, int d) {
-  size_t t = 0;
-  t += align_up((size_t)B * d * sizeof(float), 256);                                   // ub
-  t += align_up((size_t)kSmallPlanWgs * (size_t)n * sizeof(rc_plan_row), 256);         // rows
-  t += align_up((size_t)kSmallPlanWgs * (size_t)n * sizeof(uint32_t), 256);            // occ
-  t += align_up((size_t)kSmallPlanWgs * sizeof(SmallCnt), 256);                       // cnt
-  return t;
+  return align_up((size_t)B * d * sizeof(float), 256) + carve_small_plan_ws(nullptr, n).total;
 }
 
 bool small_step_supported(int64_t n_i, int64_t B, int64_t n_items, int64_t n_users, int d) {
   return n_i + B <= kSmallMaxKeys && n_items + n_users < ((int64_t)1 << 32) && (d == 16 || d == 32 || d == 64 || d == 128);
 }
 
-int small_step_launch(float* U, float* I, float* mU, float* vU, float* mI, float* vI, const int64_t* uid, const int64_t* iid,
-                      int B, int C, int d, int64_t n_items, const rc_opt_hyper* h, float inv_b, float* loss_out, float* pred,
-                      float* gpred, float* ugrad, float* loss_vec, void* extra, hipStream_t s, hipEvent_t* ev_mid) {
-  const int64_t n_i = (int64_t)B * C, n = n_i + B;
+int small_step_launch(const BprmfStep& st, void* extra, hipEvent_t* ev_mid) {
+  const int64_t n_i = st.n_i(), n = n_i + st.B;
   Carver cv(extra);
-  float* ub = cv.take<float>((size_t)B * d);
-  rc_plan_row* rows = cv.take<rc_plan_row>((size_t)kSmallPlanWgs * (size_t)n);
-  uint32_t* occ = cv.take<uint32_t>((size_t)kSmallPlanWgs * (size_t)n);
-  SmallCnt* cnt = cv.take<SmallCnt>(kSmallPlanWgs);
+  float* ub = cv.take<float>((size_t)st.B * st.d);
+  const SmallPlanWs pw = carve_small_plan_ws(cv.base + cv.off, n);
   SmallPlanArgs p;
   memset(&p, 0, sizeof(p));
-  p.ids_a = iid; p.ids_b = uid; p.n_a = (uint32_t)n_i; p.n = (uint32_t)n; p.base_b = (uint32_t)n_items;
-  p.rows = rows; p.occ = occ; p.cnt = cnt;
-  RC_TRY(small_front_launch(U, I, uid, iid, B, C, d, inv_b, pred, loss_vec, gpred, ugrad, ub, p, s));
+  p.ids_a = st.iid; p.ids_b = st.uid; p.n_a = (uint32_t)n_i; p.n = (uint32_t)n; p.base_b = (uint32_t)st.n_items;
+  p.rows = pw.rows; p.occ = pw.occ; p.cnt = pw.cnt;
+  RC_TRY(small_front_launch(st, ub, p));
   if (ev_mid) {  // two consecutive marks: [0] closes the front launch, [1] opens the update launch
-    RC_HIP(hipEventRecord(ev_mid[0], s));
-    RC_HIP(hipEventRecord(ev_mid[1], s));
+    RC_HIP(hipEventRecord(ev_mid[0], st.s));
+    RC_HIP(hipEventRecord(ev_mid[1], st.s));
   }
   SmallUpdArgs a;
   memset(&a, 0, sizeof(a));
-  RC_TRY(fill_opt_scalars("rc_bprmf_train_step", h, &a.o));
-  const int mode = mode_of(h);
-  RC_TRY(opt_state_check("rc_bprmf_train_step", mode, mU && mI, vU && vI));
-  a.I = I; a.mI = mI; a.vI = vI; a.U = U; a.mU = mU; a.vU = vU;
-  a.rows = rows; a.occ = occ; a.cnt = cnt; a.n = (uint32_t)n; a.n_a = (uint32_t)n_i; a.C = C;
-  a.gpred = gpred; a.ub = ub; a.ugrad = ugrad; a.loss_vec = loss_vec; a.B = B; a.loss_scale = inv_b; a.loss_out = loss_out;
-  return dispatch_or_fail<16, 32, 64, 128>("rc_bprmf_train_step (small step)", "d", d, [&](auto D) {
+  a.o = st.o;
+  a.I = st.I; a.mI = st.mI; a.vI = st.vI; a.U = st.U; a.mU = st.mU; a.vU = st.vU;
+  a.rows = pw.rows; a.occ = pw.occ; a.cnt = pw.cnt; a.n = (uint32_t)n; a.n_a = (uint32_t)n_i; a.C = st.C;
+  a.gpred = st.gpred; a.ub = ub; a.ugrad = st.ugrad; a.loss_vec = st.loss_vec; a.B = st.B; a.loss_scale = st.inv_b;
+  a.loss_out = st.loss_out;
+  return dispatch_or_fail<16, 32, 64, 128>("rc_bprmf_train_step (small step)", "d", st.d, [&](auto D) {
     constexpr int DD = D;
-    return dispatch_or_fail<MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_bprmf_train_step (small step)", "update mode", mode,
-                                                               [&](auto M) { return small_update_launch<DD, M()>(a, s); });
+    return dispatch_or_fail<MODE_SGD, MODE_ADAM, MODE_ADAGRAD>("rc_bprmf_train_step (small step)", "update mode", st.mode,
+                                                               [&](auto M) { return small_update_launch<DD, M()>(a, st.s); });
   });
 }
 
@@ -484,9 +471,7 @@ extern "C" int rc_small_row_sums_supported(int64_t n, int64_t n_rows, int d) {
 }
 
 extern "C" size_t rc_small_row_sums_workspace_bytes(int64_t n) {
-  if (n < 1) n = 1;
-  return align_up((size_t)kSmallPlanWgs * (size_t)n * sizeof(rc_plan_row), 256) +
-         align_up((size_t)kSmallPlanWgs * (size_t)n * sizeof(uint32_t), 256) + align_up((size_t)kSmallPlanWgs * sizeof(SmallCnt), 256);
+  return carve_small_plan_ws(nullptr, n < 1 ? 1 : n).total;
 }
 
 // Both entry points: the argument checks, [the plan launch,] the row-sums launch.  Everything that inspects only the arguments
@@ -534,16 +519,13 @@ static int small_row_sums_impl(const char* who, bool build_plan, const int64_t* 
     return fail(RC_ERR_UNSUPPORTED, "%s: n=%lld (<= %d), n_rows=%lld, d=%d (1..4, 16, 32, 64, 128) not covered",
                 who, (long long)n, kSmallMaxKeys, (long long)n_rows, d);
   hipStream_t s = as_stream(stream);
-  Carver cv(ws);
-  rc_plan_row* rows = cv.take<rc_plan_row>((size_t)kSmallPlanWgs * (size_t)n);
-  uint32_t* occ = cv.take<uint32_t>((size_t)kSmallPlanWgs * (size_t)n);
-  SmallCnt* cnt = cv.take<SmallCnt>(kSmallPlanWgs);
-  a.rows = rows; a.occ = occ; a.cnt = cnt;
+  const SmallPlanWs pw = carve_small_plan_ws(ws, n);
+  a.rows = pw.rows; a.occ = pw.occ; a.cnt = pw.cnt;
   if (build_plan) {
     SmallPlanArgs p;
     memset(&p, 0, sizeof(p));
     p.ids_a = ids; p.ids_b = nullptr; p.n_a = (uint32_t)n; p.n = (uint32_t)n; p.base_b = 0xFFFFFFFFu;   // one list: every key is a row of it
-    p.rows = rows; p.occ = occ; p.cnt = cnt;
+    p.rows = pw.rows; p.occ = pw.occ; p.cnt = pw.cnt;
     {   // function attributes are per device: once per device of the process, under a lock (callers may drive several GPUs / threads)
       static std::mutex mu;
       static bool done[64] = {};

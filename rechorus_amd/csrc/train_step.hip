@@ -13,29 +13,15 @@
 // phase_ms slots (all pipelines): [0] sort / partition (+ flags) [7] segment heads / per-bucket pass when on the caller's
 // stream [2] fused kernel [3] loss mean (0 when folded into the last update launch) [4] item-row update [5] user-row update.
 //
+// Structure: train_step_impl checks (every refusal that needs only the arguments comes before the workspace-size check,
+// and that before anything is enqueued), fills ONE BprmfStep (bprmf_step.hpp), chooses (choose_pipeline) and runs
+// step_small / step_plan / step_sort.  PhaseMarks owns the profiling events, ticket_take / ticket_issue the look-ahead.
+//
 // Ordering constraints: the item-row update reads U (pre-step values, to rebuild g*U[u]) so it runs
 // before the user rows are rewritten; the fused kernel reads both tables before either is updated.
 #include <mutex>
 
-#include "common.hpp"
-#include "plan.hpp"
-
-namespace rc {
-int plan_bprmf_step_updates(float* U, float* mU, float* vU, float* I, float* mI, float* vI, int d, const int64_t* uid,
-                            int C, int64_t n_i, int64_t B, const float* gpred, const float* ugrad,
-                            const rc_plan_row* rows_i, const uint32_t* n_rows_i, const rc_plan_row* rows_u,
-                            const uint32_t* n_rows_u, const uint32_t* occ, uint32_t* counters,
-                            const PlanLongWs& lw, bool long_planned,
-                            const rc_opt_hyper* h, const float* loss_vec, float loss_scale, float* loss_out,
-                            hipStream_t s, hipEvent_t* ev_items_done);
-int plan_prepare();
-// small batches (small_step.hip): two launches
-size_t small_step_extra_bytes(int64_t n, int64_t B, int d);
-bool small_step_supported(int64_t n_i, int64_t B, int64_t n_items, int64_t n_users, int d);
-int small_step_launch(float* U, float* I, float* mU, float* vU, float* mI, float* vI, const int64_t* uid, const int64_t* iid,
-                      int B, int C, int d, int64_t n_items, const rc_opt_hyper* h, float inv_b, float* loss_out, float* pred,
-                      float* gpred, float* ugrad, float* loss_vec, void* extra, hipStream_t s, hipEvent_t* ev_mid);
-}
+#include "bprmf_step.hpp"
 
 // The second stream of the step.  The bucket plan's per-bucket pass (row records + grouped positions) is index work
 // that only the updates need; the fused kernel needs at most the multi-occurrence bitmap.  So the step forks: the fused
@@ -193,205 +179,293 @@ extern "C" size_t rc_bprmf_step_workspace_bytes(int B, int C, int d) {
   return carve_step_ws(nullptr, B, C, d).total;
 }
 
-static bool ticket_matches(const rc_step_ticket* t, uint64_t generation, const void* ws, int device, int B, int C, int d,
-                           int64_t n_users, int64_t n_items, int flavour) {
-  return t != nullptr && generation != 0 && t->generation == generation && t->ws == reinterpret_cast<uintptr_t>(ws) &&
-         t->device == device && t->B == B && t->C == C && t->d == d && t->n_users == n_users && t->n_items == n_items &&
-         t->flavour == flavour && (t->slot == 0 || t->slot == 1);
-}
+// ---- phase marks -------------------------------------------------------------------------------------
+// Profiling mode (phase_ms != nullptr): eight hipEvents recorded on the step's stream between its phases.  Without
+// phase_ms nothing is created and mark() does nothing; the destructor destroys what was created on every return path.
+namespace {
+class PhaseMarks {
+ public:
+  static constexpr int kMarks = 8;
+  PhaseMarks() = default;
+  PhaseMarks(const PhaseMarks&) = delete;
+  PhaseMarks& operator=(const PhaseMarks&) = delete;
+  ~PhaseMarks() {
+    for (int i = 0; i < n_; ++i) (void)hipEventDestroy(ev_[i]);
+  }
+  int open(const float* phase_ms, hipStream_t s) {
+    s_ = s;
+    if (phase_ms != nullptr)
+      for (; n_ < kMarks; ++n_) RC_HIP(hipEventCreate(&ev_[n_]));
+    return RC_OK;
+  }
+  bool on() const { return n_ == kMarks; }
+  int mark(int i) {
+    if (on()) RC_HIP(hipEventRecord(ev_[i], s_));
+    return RC_OK;
+  }
+  // marks [i, ...) for a callee that records them itself (null when off)
+  hipEvent_t* at(int i) { return on() ? &ev_[i] : nullptr; }
+  // waits for the last mark; event i opens: 0 sort items, 1 mark singletons, 2 sort users, 3 fused, 4 loss mean,
+  // 5 item update, 6 user update; reported in the header's slot order
+  int report(float* phase_ms) {
+    if (!on()) return RC_OK;
+    RC_HIP(hipEventSynchronize(ev_[kMarks - 1]));
+    const int slot[7] = {0, 7, 1, 2, 3, 4, 5};
+    for (int i = 0; i < 7; ++i) RC_HIP(hipEventElapsedTime(&phase_ms[slot[i]], ev_[i], ev_[i + 1]));
+    RC_HIP(hipEventElapsedTime(&phase_ms[6], ev_[0], ev_[kMarks - 1]));
+    return RC_OK;
+  }
 
-static int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, float* vI,
-                           const int64_t* uid, const int64_t* iid, int B, int C, int d,
-                           int64_t n_users, int64_t n_items, const rc_opt_hyper* h,
-                           float inv_b, float* loss_out, float* pred, void* ws,
-                           size_t ws_bytes, rc_stream_t stream, float* phase_ms,
-                           uint64_t generation, const int64_t* next_uid, const int64_t* next_iid, uint64_t next_generation,
-                           rc_step_ticket* ticket) {
-  RC_REQUIRE(U && I && uid && iid && h && loss_out && ws, "rc_bprmf_train_step: null pointer");
-  RC_REQUIRE(B >= 1 && C >= 2 && d >= 1, "rc_bprmf_train_step: bad shape B=%d C=%d d=%d", B, C, d);
-  RC_REQUIRE((int64_t)B * C < ((int64_t)1 << 31), "rc_bprmf_train_step: B*C too large");
-  RC_REQUIRE(U != I, "rc_bprmf_train_step: user and item tables must be distinct");
-  const StepWs w = carve_step_ws(ws, B, C, d);
-  if (ws_bytes < w.total)
-    return fail(RC_ERR_WORKSPACE, "rc_bprmf_train_step: workspace %zu < %zu", ws_bytes, w.total);
-  hipStream_t s = as_stream(stream);
-  const int64_t n_i = (int64_t)B * C;
+ private:
+  hipEvent_t ev_[kMarks];
+  int n_ = 0;
+  hipStream_t s_ = nullptr;
+};
 
-  constexpr int kMarks = 8;
-  hipEvent_t ev[kMarks];
-  const bool prof = phase_ms != nullptr;
-  if (prof)
-    for (int i = 0; i < kMarks; ++i) RC_HIP(hipEventCreate(&ev[i]));
-#define RC_MARK(i)                                \
-  do {                                            \
-    if (prof) RC_HIP(hipEventRecord(ev[i], s));   \
-  } while (0)
+// ---- pipeline choice ---------------------------------------------------------------------------------
+enum StepPipeline { STEP_SMALL, STEP_PLAN, STEP_SORT };
+struct StepChoice {
+  StepPipeline pipeline;
+  PlanGeom geom;
+  bool fused_upd;     // the fused kernel updates single-occurrence item rows itself
+  bool two_streams;   // bucket plan: its per-bucket pass (and the look-ahead) on the side stream
+  int flavour;        // what a prepared plan contains: 1 = bitmap + multi rows, 2 = every row listed
+};
 
+StepChoice choose_pipeline(const BprmfStep& st, bool side_ok) {
+  const int mode = step_pipeline();
+  const int64_t n_i = st.n_i();
+  const bool fused_ok = rc_bprmf_fused_supported(st.d, st.C) != 0;
+  StepChoice c;
   // The singleton fast path (update single-occurrence item rows inside the fused kernel) pays for
   // SGD only: with optimizer state the m/v rows have to be fetched at the kernel's tail, where nothing
   // hides their latency (measured at config 2, Adam: 2.98 ms/step fused vs 2.31 ms through the
   // segmented update, which already streams 6 row-units per touched row at the HBM rate).
   // (a hashed plan geometry -- very wide / sparse id spaces -- has no id-indexed bitmap: every row is listed then)
-  const bool want_bitmap = rc_bprmf_fused_supported(d, C) != 0 && h->opt == RC_OPT_SGD;   // -> id-range buckets if at all possible
-  const PlanGeom geom = plan_geometry(n_i, B, n_items, n_users, want_bitmap ? 0 : -1);
+  const bool want_bitmap = fused_ok && st.h->opt == RC_OPT_SGD;   // -> id-range buckets if at all possible
+  c.geom = plan_geometry(n_i, st.B, st.n_items, st.n_users, want_bitmap ? 0 : -1);
   // (narrow geometry = dense batch, several occurrences per row of the table: hardly any row occurs once, the singleton
   //  fast path has nothing to win there)
-  const bool fused_upd = rc_bprmf_fused_supported(d, C) != 0 && h->opt == RC_OPT_SGD && !geom.hashed && !geom.narrow;
-  // what a prepared plan contains: 1 = bitmap + multi rows, 2 = every row listed
-  const int flavour = fused_upd ? 1 : 2;
-
-  // A plan prepared ahead by an earlier call (rc_step_ticket, caller-owned): usable when it was made for exactly this
-  // batch -- the caller's generation id, not a pointer, says so -- workspace, geometry and plan flavour.  In every case
-  // the side stream's writes into the workspace have to be finished before this call touches the plan buffers.
-  int device = 0;
-  StepSide* side = step_side(&device);
-  bool ahead_hit = false;
-  int slot = 0;
-  if (ticket != nullptr && ticket->generation != 0) {
-    RC_REQUIRE(ticket->device == device, "rc_bprmf_train_step_ahead: the ticket was prepared on device %d, current device %d",
-               ticket->device, device);
-    RC_REQUIRE(side != nullptr, "rc_bprmf_train_step_ahead: side stream unavailable on device %d", device);
-    ahead_hit = ticket_matches(ticket, generation, ws, device, B, C, d, n_users, n_items, flavour);
-    if (ahead_hit) slot = ticket->slot;
-    RC_HIP(hipStreamWaitEvent(s, side->front_done, 0));
-    ticket->generation = 0;
-  }
-
-  // Pipeline choice: the bucket plan (bucket_plan.hip + plan_update.hip) where the register-resident
-  // fused kernel exists and the joint id space fits one bucket level; otherwise (and in pipeline mode 1)
-  // the round-1 pipeline: joint radix sort -> segment heads -> fused -> segmented updates.
-  const bool force_sort = step_pipeline() == 1;
-  const bool fused_ok = rc_bprmf_fused_supported(d, C) != 0;
+  c.fused_upd = want_bitmap && !c.geom.hashed && !c.geom.narrow;
+  c.flavour = c.fused_upd ? 1 : 2;
+  c.two_streams = (mode == 0 || mode == 3) && side_ok;
   // Small batches (<= 32,768 row ids, e.g. the reference's default B = 256 with K = 99): two launches (small_step.hip).
-  if (step_pipeline() == 0 && fused_ok && small_step_supported(n_i, B, n_items, n_users, d) &&
-      reinterpret_cast<uintptr_t>(U) % 16 == 0 && reinterpret_cast<uintptr_t>(I) % 16 == 0) {
-    RC_MARK(0);
-    RC_MARK(1);
-    RC_MARK(2);
-    RC_MARK(3);
-    RC_TRY(small_step_launch(U, I, mU, vU, mI, vI, uid, iid, B, C, d, n_items, h, inv_b, loss_out, pred, w.gpred, w.ugrad,
-                             w.loss_vec, w.small_extra, s, prof ? &ev[4] : nullptr));  // marks 4, 5
-    RC_MARK(6);
-    RC_MARK(7);
-  } else
-  if (!force_sort && geom.ok && fused_ok && (d == 16 || d == 32 || d == 64 || d == 128)) {
-    RC_TRY(plan_prepare());
-    const PlanArgs pa = slot_plan_args(w, slot, uid, iid, n_i, B, n_users, n_items, geom, fused_upd);
-    const bool two_streams = (step_pipeline() == 0 || step_pipeline() == 3) && side != nullptr;
-    // Look-ahead: the WHOLE plan of the next batch (partition, bitmap, row records, grouped positions) into the other
-    // slot, on the side stream.  Not under stream capture (the next call's wait on front_done would cross graphs).
-    // (Also in profiling mode: a profiled step is then exactly a step of the steady state, the next plan beside it.)
-    bool look_ahead = two_streams && ticket != nullptr && next_generation != 0 && next_uid != nullptr && next_iid != nullptr;
-    if (look_ahead) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      look_ahead = hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
-    }
-    RC_MARK(0);
-    if (ahead_hit) {
-      // the plan is complete (prepared beside the previous step): this step starts with its fused kernel
-      RC_MARK(1);
-    } else if (two_streams) {
-      // caller's stream: partition (+ bitmap when the fused kernel updates singleton rows) -> fused kernel
-      // side stream:     per-bucket pass (row records, grouped positions), joined before the updates
-      // (without the singleton fast path the fused kernel needs nothing from the plan: all of it runs on the side stream)
-      if (fused_upd) RC_TRY(plan_launch_front(pa, true, s));
-      RC_MARK(1);
-      RC_HIP(hipEventRecord(side->fork, s));
-      RC_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-      if (!fused_upd) RC_TRY(plan_launch_front(pa, false, side->stream));
-      RC_TRY(plan_launch_back(pa, side->stream));
-      RC_HIP(hipEventRecord(side->join, side->stream));
-    } else {
-      RC_TRY(plan_launch_front(pa, fused_upd, s));
-      RC_MARK(1);   // after the partition (+ bitmap), before the bucket kernel
-      RC_TRY(plan_launch_back(pa, s));
-    }
-    // The look-ahead is forked here, in front of the fused kernel: the plan's chain of latency-bound kernels stretches
-    // about 2.5 x beside the bandwidth-bound row kernels and needs the whole step as its window (0.988 -> 0.945 ms/step
-    // at config 2 against a fork behind the fused kernel, profiles/r03d_ab_overlap.txt).
-    if (look_ahead) {
-      PlanArgs pn = slot_plan_args(w, 1 - slot, next_uid, next_iid, n_i, B, n_users, n_items, geom, fused_upd);
-      RC_HIP(hipEventRecord(side->fork2, s));
-      RC_HIP(hipStreamWaitEvent(side->stream, side->fork2, 0));
-      // a plan prepared as a whole: the bucket kernel writes the multi-occurrence bitmap from the counts it holds anyway
-      // (the separate bitmap launch zeroes and counts every bucket a second time: 0.06 ms beside the row kernels)
-      pn.bitmap_in_bucket = fused_upd ? 1 : 0;   // (fused_upd implies an id-range geometry: neither hashed nor narrow)
-      RC_TRY(plan_launch_front(pn, false, side->stream));
-      RC_TRY(plan_launch_back(pn, side->stream));
-      RC_HIP(hipEventRecord(side->front_done, side->stream));
-      ticket->generation = next_generation;
-      ticket->ws = reinterpret_cast<uintptr_t>(ws);
-      ticket->slot = 1 - slot; ticket->device = device; ticket->B = B; ticket->C = C; ticket->d = d;
-      ticket->flavour = flavour; ticket->n_users = n_users; ticket->n_items = n_items;
-    }
-    RC_MARK(2);
-    RC_MARK(3);
-    if (fused_upd)
-      RC_TRY(rc_bprmf_fwd_bwd_update(U, I, mI, vI, uid, iid, nullptr, w.slot[slot].bitmap, B, C, d, inv_b, h, pred, w.loss_vec,
-                                     w.gpred, w.ugrad, stream));
-    else
-      RC_TRY(rc_bprmf_fwd_bwd(U, I, uid, iid, B, C, d, inv_b, pred, w.loss_vec, w.gpred, w.ugrad, stream));
-    if (two_streams && !ahead_hit) RC_HIP(hipStreamWaitEvent(s, side->join, 0));
-    RC_MARK(4);
-    RC_MARK(5);  // (the loss mean is one workgroup of the last update launch)
-    RC_TRY(plan_bprmf_step_updates(U, mU, vU, I, mI, vI, d, uid, C, n_i, B, w.gpred, w.ugrad, pa.rows_a, pa.n_rows_a,
-                                   pa.rows_b, pa.n_rows_b, pa.occ, pa.w.counters, pa.lw, true, h, w.loss_vec, inv_b,
-                                   loss_out, s, prof ? &ev[6] : nullptr));
-    RC_MARK(7);
-  } else {
-  RC_MARK(0);
-  // one joint radix sort: keys = item id | n_items + user id (all user keys sort after all item keys)
-  RC_REQUIRE(n_items + n_users <= ((int64_t)1 << 32), "rc_bprmf_train_step: n_items + n_users exceeds 2^32");
-  RC_TRY(rc_sort_ids(iid, n_i, uid, B, n_items, n_items + n_users, w.keys_i, w.perm_i, w.sort_ws,
-                      w.sort_ws_bytes, stream));
-  RC_MARK(1);
-  if (fused_upd)
-    RC_TRY(rc_segment_heads(w.keys_i, w.perm_i, n_i, 1, w.single, w.heads_i, w.n_heads_i, stream));
-  RC_MARK(2);
-  RC_MARK(3);  // (the user ids were sorted with the item ids)
-  if (fused_upd)
-    RC_TRY(rc_bprmf_fwd_bwd_update(U, I, mI, vI, uid, iid, w.single, nullptr, B, C, d, inv_b, h, pred,
-                                   w.loss_vec, w.gpred, w.ugrad, stream));
+  // Otherwise the bucket plan (bucket_plan.hip + plan_update.hip) where the register-resident fused kernel exists and
+  // the joint id space fits one bucket level; otherwise (and in pipeline mode 1) the round-1 pipeline: joint radix
+  // sort -> segment heads -> fused -> segmented updates.
+  if (mode == 0 && fused_ok && small_step_supported(n_i, st.B, st.n_items, st.n_users, st.d) && aligned16(st.U, st.I))
+    c.pipeline = STEP_SMALL;
+  else if (mode != 1 && c.geom.ok && fused_ok && (st.d == 16 || st.d == 32 || st.d == 64 || st.d == 128))
+    c.pipeline = STEP_PLAN;
   else
-    RC_TRY(rc_bprmf_fwd_bwd(U, I, uid, iid, B, C, d, inv_b, pred, w.loss_vec, w.gpred, w.ugrad,
-                            stream));
-  RC_MARK(4);
-  RC_TRY(rc_reduce_sum(w.loss_vec, B, inv_b, loss_out, stream));
-  RC_MARK(5);
-  // item rows: grad_r = sum_{(b,c): iid[b,c]=r} g[b,c] * U[uid[b]]
-  RC_TRY(rc_segmented_update(I, mI, vI, d, w.keys_i, w.perm_i, n_i, w.gpred, U, uid, C, nullptr, n_i,
-                             /*key_base=*/0, /*occ_base=*/0, h, nullptr, fused_upd ? w.heads_i : nullptr,
-                             fused_upd ? w.n_heads_i : nullptr,
-                             fused_upd ? RC_SEG_SKIP_SINGLETONS : 0, w.seg_ws, w.seg_ws_bytes,
-                             stream));
-  RC_MARK(6);
-  // user rows: grad_r = sum_{b: uid[b]=r} ugrad[b]
-  RC_TRY(rc_segmented_update(U, mU, vU, d, w.keys_u, w.perm_u, B, nullptr, w.ugrad, nullptr, 1, nullptr, B,
-                             /*key_base=*/n_items, /*occ_base=*/n_i, h, nullptr, nullptr, nullptr, 0,
-                             w.seg_ws, w.seg_ws_bytes, stream));
-  RC_MARK(7);
-  }
-#undef RC_MARK
+    c.pipeline = STEP_SORT;
+  return c;
+}
 
-  if (prof) {
-    RC_HIP(hipEventSynchronize(ev[kMarks - 1]));
-    // event i opens: 0 sort items, 1 mark singletons, 2 sort users, 3 fused, 4 loss mean,
-    // 5 item update, 6 user update; reported in the header's slot order
-    const int slot[7] = {0, 7, 1, 2, 3, 4, 5};
-    for (int i = 0; i < 7; ++i) RC_HIP(hipEventElapsedTime(&phase_ms[slot[i]], ev[i], ev[i + 1]));
-    RC_HIP(hipEventElapsedTime(&phase_ms[6], ev[0], ev[kMarks - 1]));
-    for (int i = 0; i < kMarks; ++i) RC_HIP(hipEventDestroy(ev[i]));
-  }
+// ---- look-ahead tickets ------------------------------------------------------------------------------
+// What rc_bprmf_train_step_ahead adds to the plain step (ticket == nullptr: the plain step), the device and side
+// stream the call runs with, and what ticket_take found.
+struct StepAhead {
+  rc_step_ticket* ticket;
+  uint64_t generation;
+  const int64_t* next_uid;
+  const int64_t* next_iid;
+  uint64_t next_generation;
+  int device;
+  StepSide* side;
+  bool hit;   // the ticket held the plan of exactly this batch ...
+  int slot;   // ... in this plan slot (0 without a hit: the step plans into slot 0)
+};
+
+bool ticket_matches(const rc_step_ticket* t, uint64_t generation, const void* ws, int device, const BprmfStep& st, int flavour) {
+  return t != nullptr && generation != 0 && t->generation == generation && t->ws == reinterpret_cast<uintptr_t>(ws) &&
+         t->device == device && t->B == st.B && t->C == st.C && t->d == st.d && t->n_users == st.n_users &&
+         t->n_items == st.n_items && t->flavour == flavour && (t->slot == 0 || t->slot == 1);
+}
+
+// A plan prepared ahead by an earlier call (rc_step_ticket, caller-owned): usable when it was made for exactly this
+// batch -- the caller's generation id, not a pointer, says so -- workspace, geometry and plan flavour.  In every case
+// the side stream's writes into the workspace have to be finished before this call touches the plan buffers.
+int ticket_take(StepAhead& ah, const void* ws, const BprmfStep& st, int flavour) {
+  ah.hit = false;
+  ah.slot = 0;
+  rc_step_ticket* t = ah.ticket;
+  if (t == nullptr || t->generation == 0) return RC_OK;
+  RC_REQUIRE(t->device == ah.device, "rc_bprmf_train_step_ahead: the ticket was prepared on device %d, current device %d",
+             t->device, ah.device);
+  RC_REQUIRE(ah.side != nullptr, "rc_bprmf_train_step_ahead: side stream unavailable on device %d", ah.device);
+  ah.hit = ticket_matches(t, ah.generation, ws, ah.device, st, flavour);
+  if (ah.hit) ah.slot = t->slot;
+  RC_HIP(hipStreamWaitEvent(st.s, ah.side->front_done, 0));
+  t->generation = 0;
   return RC_OK;
 }
+
+// the plan of the next batch has been enqueued into `slot` on the side stream
+void ticket_issue(const StepAhead& ah, const void* ws, int slot, const BprmfStep& st, int flavour) {
+  rc_step_ticket* t = ah.ticket;
+  t->generation = ah.next_generation;
+  t->ws = reinterpret_cast<uintptr_t>(ws);
+  t->slot = slot; t->device = ah.device; t->B = st.B; t->C = st.C; t->d = st.d;
+  t->flavour = flavour; t->n_users = st.n_users; t->n_items = st.n_items;
+}
+
+// ---- the three pipelines -----------------------------------------------------------------------------
+inline rc_stream_t as_rc_stream(hipStream_t s) { return reinterpret_cast<rc_stream_t>(s); }
+
+int step_small(const BprmfStep& st, const StepWs& w, PhaseMarks& pm) {
+  for (int i = 0; i < 4; ++i) RC_TRY(pm.mark(i));
+  RC_TRY(small_step_launch(st, w.small_extra, pm.at(4)));  // marks 4, 5
+  RC_TRY(pm.mark(6));
+  return pm.mark(7);
+}
+
+int step_plan(const BprmfStep& st, const StepWs& w, void* ws, const StepChoice& ch, const StepAhead& ah, PhaseMarks& pm) {
+  hipStream_t s = st.s;
+  StepSide* side = ah.side;
+  const int64_t n_i = st.n_i();
+  const bool fused_upd = ch.fused_upd, two_streams = ch.two_streams;
+  RC_TRY(plan_prepare());
+  const PlanArgs pa = slot_plan_args(w, ah.slot, st.uid, st.iid, n_i, st.B, st.n_users, st.n_items, ch.geom, fused_upd);
+  // Look-ahead: the WHOLE plan of the next batch (partition, bitmap, row records, grouped positions) into the other
+  // slot, on the side stream.  Not under stream capture (the next call's wait on front_done would cross graphs).
+  // (Also in profiling mode: a profiled step is then exactly a step of the steady state, the next plan beside it.)
+  bool look_ahead = two_streams && ah.ticket != nullptr && ah.next_generation != 0 && ah.next_uid != nullptr && ah.next_iid != nullptr;
+  if (look_ahead) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    look_ahead = hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
+  }
+  RC_TRY(pm.mark(0));
+  if (ah.hit) {
+    // the plan is complete (prepared beside the previous step): this step starts with its fused kernel
+    RC_TRY(pm.mark(1));
+  } else if (two_streams) {
+    // caller's stream: partition (+ bitmap when the fused kernel updates singleton rows) -> fused kernel
+    // side stream:     per-bucket pass (row records, grouped positions), joined before the updates
+    // (without the singleton fast path the fused kernel needs nothing from the plan: all of it runs on the side stream)
+    if (fused_upd) RC_TRY(plan_launch_front(pa, true, s));
+    RC_TRY(pm.mark(1));
+    RC_HIP(hipEventRecord(side->fork, s));
+    RC_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
+    if (!fused_upd) RC_TRY(plan_launch_front(pa, false, side->stream));
+    RC_TRY(plan_launch_back(pa, side->stream));
+    RC_HIP(hipEventRecord(side->join, side->stream));
+  } else {
+    RC_TRY(plan_launch_front(pa, fused_upd, s));
+    RC_TRY(pm.mark(1));   // after the partition (+ bitmap), before the bucket kernel
+    RC_TRY(plan_launch_back(pa, s));
+  }
+  // The look-ahead is forked here, in front of the fused kernel: the plan's chain of latency-bound kernels stretches
+  // about 2.5 x beside the bandwidth-bound row kernels and needs the whole step as its window (0.988 -> 0.945 ms/step
+  // at config 2 against a fork behind the fused kernel, profiles/r03d_ab_overlap.txt).
+  if (look_ahead) {
+    PlanArgs pn = slot_plan_args(w, 1 - ah.slot, ah.next_uid, ah.next_iid, n_i, st.B, st.n_users, st.n_items, ch.geom, fused_upd);
+    RC_HIP(hipEventRecord(side->fork2, s));
+    RC_HIP(hipStreamWaitEvent(side->stream, side->fork2, 0));
+    // a plan prepared as a whole: the bucket kernel writes the multi-occurrence bitmap from the counts it holds anyway
+    // (the separate bitmap launch zeroes and counts every bucket a second time: 0.06 ms beside the row kernels)
+    pn.bitmap_in_bucket = fused_upd ? 1 : 0;   // (fused_upd implies an id-range geometry: neither hashed nor narrow)
+    RC_TRY(plan_launch_front(pn, false, side->stream));
+    RC_TRY(plan_launch_back(pn, side->stream));
+    RC_HIP(hipEventRecord(side->front_done, side->stream));
+    ticket_issue(ah, ws, 1 - ah.slot, st, ch.flavour);
+  }
+  RC_TRY(pm.mark(2));
+  RC_TRY(pm.mark(3));
+  if (fused_upd)
+    RC_TRY(rc_bprmf_fwd_bwd_update(st.U, st.I, st.mI, st.vI, st.uid, st.iid, nullptr, w.slot[ah.slot].bitmap, st.B, st.C, st.d,
+                                   st.inv_b, st.h, st.pred, st.loss_vec, st.gpred, st.ugrad, as_rc_stream(s)));
+  else
+    RC_TRY(rc_bprmf_fwd_bwd(st.U, st.I, st.uid, st.iid, st.B, st.C, st.d, st.inv_b, st.pred, st.loss_vec, st.gpred, st.ugrad,
+                            as_rc_stream(s)));
+  if (two_streams && !ah.hit) RC_HIP(hipStreamWaitEvent(s, side->join, 0));
+  RC_TRY(pm.mark(4));
+  RC_TRY(pm.mark(5));  // (the loss mean is one workgroup of the last update launch)
+  RC_TRY(plan_bprmf_step_updates(st, pa.rows_a, pa.n_rows_a, pa.rows_b, pa.n_rows_b, pa.occ, pa.w.counters, pa.lw, true, pm.at(6)));
+  return pm.mark(7);
+}
+
+int step_sort(const BprmfStep& st, const StepWs& w, bool fused_upd, PhaseMarks& pm) {
+  const rc_stream_t stream = as_rc_stream(st.s);
+  const int64_t n_i = st.n_i();
+  RC_TRY(pm.mark(0));
+  // one joint radix sort: keys = item id | n_items + user id (all user keys sort after all item keys)
+  RC_TRY(rc_sort_ids(st.iid, n_i, st.uid, st.B, st.n_items, st.n_items + st.n_users, w.keys_i, w.perm_i, w.sort_ws, w.sort_ws_bytes,
+                     stream));
+  RC_TRY(pm.mark(1));
+  if (fused_upd) RC_TRY(rc_segment_heads(w.keys_i, w.perm_i, n_i, 1, w.single, w.heads_i, w.n_heads_i, stream));
+  RC_TRY(pm.mark(2));
+  RC_TRY(pm.mark(3));  // (the user ids were sorted with the item ids)
+  if (fused_upd)
+    RC_TRY(rc_bprmf_fwd_bwd_update(st.U, st.I, st.mI, st.vI, st.uid, st.iid, w.single, nullptr, st.B, st.C, st.d, st.inv_b, st.h,
+                                   st.pred, st.loss_vec, st.gpred, st.ugrad, stream));
+  else
+    RC_TRY(rc_bprmf_fwd_bwd(st.U, st.I, st.uid, st.iid, st.B, st.C, st.d, st.inv_b, st.pred, st.loss_vec, st.gpred, st.ugrad, stream));
+  RC_TRY(pm.mark(4));
+  RC_TRY(rc_reduce_sum(st.loss_vec, st.B, st.inv_b, st.loss_out, stream));
+  RC_TRY(pm.mark(5));
+  // item rows: grad_r = sum_{(b,c): iid[b,c]=r} g[b,c] * U[uid[b]]
+  RC_TRY(rc_segmented_update(st.I, st.mI, st.vI, st.d, w.keys_i, w.perm_i, n_i, st.gpred, st.U, st.uid, st.C, nullptr, n_i,
+                             /*key_base=*/0, /*occ_base=*/0, st.h, nullptr, fused_upd ? w.heads_i : nullptr,
+                             fused_upd ? w.n_heads_i : nullptr, fused_upd ? RC_SEG_SKIP_SINGLETONS : 0, w.seg_ws, w.seg_ws_bytes,
+                             stream));
+  RC_TRY(pm.mark(6));
+  // user rows: grad_r = sum_{b: uid[b]=r} ugrad[b]
+  RC_TRY(rc_segmented_update(st.U, st.mU, st.vU, st.d, w.keys_u, w.perm_u, st.B, nullptr, st.ugrad, nullptr, 1, nullptr, st.B,
+                             /*key_base=*/st.n_items, /*occ_base=*/n_i, st.h, nullptr, nullptr, nullptr, 0, w.seg_ws,
+                             w.seg_ws_bytes, stream));
+  return pm.mark(7);
+}
+
+// check -> choose -> run.  Everything that inspects only the arguments is refused before the workspace-size check, and
+// that before anything is enqueued.  `ah`: ticket / generations / next batch of rc_bprmf_train_step_ahead, zeroes otherwise.
+int train_step_impl(float* U, float* I, float* mU, float* vU, float* mI, float* vI, const int64_t* uid, const int64_t* iid, int B,
+                    int C, int d, int64_t n_users, int64_t n_items, const rc_opt_hyper* h, float inv_b, float* loss_out, float* pred,
+                    void* ws, size_t ws_bytes, rc_stream_t stream, float* phase_ms, StepAhead ah) {
+  static const char* who = "rc_bprmf_train_step";
+  RC_REQUIRE(U && I && uid && iid && h && loss_out && ws, "%s: null pointer", who);
+  RC_REQUIRE(B >= 1 && C >= 2 && d >= 1, "%s: bad shape B=%d C=%d d=%d", who, B, C, d);
+  RC_REQUIRE((int64_t)B * C < ((int64_t)1 << 31), "%s: B*C too large", who);
+  RC_REQUIRE(U != I, "%s: user and item tables must be distinct", who);
+  const StepWs w = carve_step_ws(ws, B, C, d);
+  BprmfStep st;
+  memset(&st, 0, sizeof(st));
+  RC_TRY(fill_opt_scalars(who, h, &st.o));
+  st.mode = mode_of(h);
+  RC_TRY(opt_state_check(who, st.mode, mU && mI, vU && vI));
+  st.U = U; st.I = I; st.mU = mU; st.vU = vU; st.mI = mI; st.vI = vI; st.uid = uid; st.iid = iid;
+  st.B = B; st.C = C; st.d = d; st.n_users = n_users; st.n_items = n_items;
+  st.h = h; st.inv_b = inv_b; st.loss_out = loss_out; st.pred = pred;
+  st.gpred = w.gpred; st.ugrad = w.ugrad; st.loss_vec = w.loss_vec;
+  st.s = as_stream(stream);
+
+  ah.side = step_side(&ah.device);
+  const StepChoice ch = choose_pipeline(st, ah.side != nullptr);
+  if (ch.pipeline == STEP_SORT)
+    RC_REQUIRE(n_items + n_users <= ((int64_t)1 << 32), "%s: n_items + n_users exceeds 2^32", who);
+  if (ws_bytes < w.total) return fail(RC_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, w.total);
+
+  PhaseMarks pm;
+  RC_TRY(pm.open(phase_ms, st.s));
+  RC_TRY(ticket_take(ah, ws, st, ch.flavour));
+  switch (ch.pipeline) {
+    case STEP_SMALL: RC_TRY(step_small(st, w, pm)); break;
+    case STEP_PLAN: RC_TRY(step_plan(st, w, ws, ch, ah, pm)); break;
+    case STEP_SORT: RC_TRY(step_sort(st, w, ch.fused_upd, pm)); break;
+  }
+  return pm.report(phase_ms);
+}
+}  // namespace
 
 extern "C" int rc_bprmf_train_step(float* U, float* I, float* mU, float* vU, float* mI, float* vI,
                                    const int64_t* uid, const int64_t* iid, int B, int C, int d,
                                    int64_t n_users, int64_t n_items, const rc_opt_hyper* h,
                                    float inv_b, float* loss_out, float* pred, void* ws,
                                    size_t ws_bytes, rc_stream_t stream, float* phase_ms) {
+  StepAhead none;
+  memset(&none, 0, sizeof(none));
   return train_step_impl(U, I, mU, vU, mI, vI, uid, iid, B, C, d, n_users, n_items, h, inv_b, loss_out, pred, ws, ws_bytes, stream,
-                         phase_ms, 0, nullptr, nullptr, 0, nullptr);
+                         phase_ms, none);
 }
 
 extern "C" int rc_bprmf_train_step_ahead(float* U, float* I, float* mU, float* vU, float* mI, float* vI,
@@ -401,8 +475,11 @@ extern "C" int rc_bprmf_train_step_ahead(float* U, float* I, float* mU, float* v
                                          const rc_opt_hyper* h, float inv_b, float* loss_out, float* pred, void* ws,
                                          size_t ws_bytes, rc_stream_t stream, float* phase_ms) {
   RC_REQUIRE(ticket != nullptr, "rc_bprmf_train_step_ahead: ticket missing (caller-owned rc_step_ticket, zero-initialised)");
+  StepAhead ah;
+  memset(&ah, 0, sizeof(ah));
+  ah.ticket = ticket; ah.generation = generation; ah.next_uid = next_uid; ah.next_iid = next_iid; ah.next_generation = next_generation;
   return train_step_impl(U, I, mU, vU, mI, vI, uid, iid, B, C, d, n_users, n_items, h, inv_b, loss_out, pred, ws, ws_bytes, stream,
-                         phase_ms, generation, next_uid, next_iid, next_generation, ticket);
+                         phase_ms, ah);
 }
 
 // Forget a prepared plan (the owner of the workspace goes away or re-allocates it): `stream` is made to wait for the

@@ -130,6 +130,62 @@ def test_segmented_update_entry_points_refuse_bad_arguments(lib):
         assert msg.startswith(name.encode() + b":") and text in msg, (i, name, msg)
 
 
+def test_bprmf_train_step_refuses_bad_arguments_before_the_workspace_check(lib):
+    """rc_bprmf_train_step / _ahead: everything that inspects only the arguments -- null pointers, shape, distinct tables, the
+    optimizer and its state tensors -- is refused in the entry point, before the workspace-size check and so before anything is
+    enqueued (the optimizer used to be validated inside the launch sequences, behind the first kernel).  ws_bytes = 0 in every
+    case: a lost check ends in RC_ERR_WORKSPACE instead of a launch on the made-up pointers below.  Both entry points report as
+    rc_bprmf_train_step; only the ticket messages carry _ahead."""
+    p, r = C.c_void_p(64), C.c_void_p(128)      # non-null, 16-byte aligned, distinct; never dereferenced
+    B, Cn, d = 8, 4, 32
+
+    def hyper(opt, step=1):
+        return C.byref(_lib.OptHyper(opt=opt, lr=0.1, beta1=0.9, beta2=0.999, eps=1e-8, step=step))
+    sgd, adam, adagrad, adadelta = (hyper(o) for o in (_lib.RC_OPT_SGD, _lib.RC_OPT_ADAM, _lib.RC_OPT_ADAGRAD, _lib.RC_OPT_ADADELTA))
+    ticket = _lib.StepTicket()
+
+    def plain(U=p, I=r, m=None, v=None, h=sgd, C_=Cn):
+        return lib.rc_bprmf_train_step(U, I, m, v, m, v, p, p, B, C_, d, 100, 1000, h, 1.0 / B, p, None, p, 0, None, None)
+
+    def ahead(U=p, I=r, m=None, v=None, h=sgd, C_=Cn, t=C.byref(ticket)):
+        return lib.rc_bprmf_train_step_ahead(U, I, m, v, m, v, p, p, 0, None, None, 0, t, B, C_, d, 100, 1000, h, 1.0 / B, p, None,
+                                             p, 0, None, None)
+    INVALID, WORKSPACE = -1, -2
+    table = []
+    for call in (plain, ahead):
+        table += [
+            (lambda call=call: call(h=adam), INVALID, b"Adam needs m and v"),
+            (lambda call=call: call(h=adam, m=p), INVALID, b"Adam needs m and v"),
+            (lambda call=call: call(h=adagrad), INVALID, b"Adagrad needs m"),
+            (lambda call=call: call(h=adadelta, m=p, v=p), INVALID, b"dense steps only"),
+            (lambda call=call: call(h=hyper(_lib.RC_OPT_ADAM, step=0), m=p, v=p), INVALID, b"step >= 1"),
+            (lambda call=call: call(I=p), INVALID, b"distinct"),
+            (lambda call=call: call(C_=1), INVALID, b""),
+            (lambda call=call: call(h=None), INVALID, b""),
+            (call, WORKSPACE, b"workspace 0 <"),
+            (lambda call=call: call(h=adam, m=p, v=p), WORKSPACE, b"workspace 0 <"),
+            (lambda call=call: call(h=adagrad, m=p), WORKSPACE, b"workspace 0 <"),
+        ]
+    table.append((lambda: ahead(t=None), INVALID, b"ticket missing"))
+    for i, (call, code, text) in enumerate(table):
+        got = call()
+        msg = lib.rc_last_error_string()
+        assert got == code, (i, got, msg)
+        assert msg.startswith(b"rc_bprmf_train_step") and text in msg, (i, msg)
+    assert ticket.generation == 0
+
+
+def test_step_and_small_plan_workspace_sizes(lib):
+    """The byte counts callers allocate by (the small plan's layout is carved in one place; these are the sizes of the layout as it
+    was when five copies of it agreed)."""
+    for (B, Cn, d), want in (((8, 4, 32), 8495616), ((3, 5, 32), 8494080), ((256, 100, 64), 66634752), ((300, 100, 64), 78087680),
+                             ((2048, 100, 64), 30142976), ((65536, 100, 64), 701639168), ((500, 4, 128), 9052672)):
+        assert lib.rc_bprmf_step_workspace_bytes(B, Cn, d) == want, (B, Cn, d)
+    for n, want in ((1, 4608), (1000, 2562048), (8192, 20973568), (32768, 83888128), (32769, 83890688)):
+        assert lib.rc_small_row_sums_workspace_bytes(n) == want, n
+    assert lib.rc_small_row_sums_workspace_bytes(0) == 4608      # n < 1 is sized as n = 1
+
+
 def test_context_model_entry_points_refuse_bad_arguments(lib):
     """The context-model path has one entry point per launch sequence; an argument subset is a NULL or a zero.  The refusals that
     guard a kernel precondition carry the surviving entry point's name.  Nothing can launch on the made-up pointers below: field 1

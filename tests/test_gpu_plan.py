@@ -408,6 +408,55 @@ def test_ticket_is_matched_by_generation_not_by_pointer(cuda, eng):
     assert C.sizeof(_lib.StepTicket) == 72
 
 
+@pytest.mark.parametrize("opt,lr,l2", [("SGD", 0.05, 1e-3), ("Adam", 1e-3, 1e-4)])
+def test_profiled_step_equals_the_plain_step(opt, lr, l2, cuda, eng):
+    """BprmfTrainer.profile_step (phase_ms given: eight hipEvents around the phases, one synchronise) in every pipeline mode:
+    tables, optimizer state and losses bit-identical to a twin that takes plain steps, and every reported phase a sane number.
+    Mode 0 takes the two-launch small step at this size (1,539 row ids); in the modes that look ahead the second profiled
+    step is a step of the steady state (its plan was prepared beside the first, the third batch's plan runs beside it)."""
+    import math
+    from rechorus_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(23)
+    d, B, C, n_users, n_items = 32, 513, 2, 40, 700
+    assert B * C + B == 1539
+    U0 = torch.from_numpy(rng.normal(0, 0.01, size=(n_users, d)).astype(np.float32)).to(cuda)
+    I0 = torch.from_numpy(rng.normal(0, 0.01, size=(n_items, d)).astype(np.float32)).to(cuda)
+    batches = [(torch.from_numpy(_zipf(rng, n_users, B)).to(cuda),
+                torch.from_numpy(np.concatenate([_zipf(rng, n_items, (B, 1)), rng.integers(1, n_items, size=(B, C - 1))], axis=1)).to(cuda))
+               for _ in range(3)]
+    names = ["sort_items", "sort_users", "fused_fwd_bwd", "loss_mean", "item_update", "user_update", "total", "segment_heads"]
+    prev = lib.rc_bprmf_step_pipeline(-1)
+    try:
+        for mode in (0, 1, 2, 3):
+            lib.rc_bprmf_step_pipeline(mode)
+            res = {}
+            for profiled in (False, True):
+                U, I = U0.clone(), I0.clone()
+                tr = eng.BprmfTrainer(U, I, opt=opt, lr=lr, l2=l2)
+                losses, phases = [], []
+                for k in range(2):
+                    if profiled:
+                        phases.append(tr.profile_step(*batches[k], next_batch=batches[k + 1]))
+                        losses.append(tr.loss.clone())
+                    else:
+                        losses.append(tr.step(*batches[k]).clone())
+                torch.cuda.synchronize()
+                res[profiled] = (U, I, tr.mU, tr.vU, tr.mI, tr.vI, torch.cat(losses))
+                for ph in phases:
+                    assert list(ph) == names, (mode, list(ph))
+                    for n, ms in ph.items():
+                        assert math.isfinite(ms) and ms >= 0.0, (mode, n, ms)
+                    assert ph["total"] > 0.0 and ph["fused_fwd_bwd"] > 0.0, (mode, ph)
+                del tr      # (forgets a prepared plan before its workspace goes away)
+            for name, x, y in zip(("U", "I", "mU", "vU", "mI", "vI", "loss"), res[False], res[True]):
+                assert (x is None) == (y is None), (mode, name)
+                if x is not None:
+                    assert torch.equal(x, y), (mode, name)
+    finally:
+        lib.rc_bprmf_step_pipeline(prev)
+
+
 @pytest.mark.parametrize("case", ["uniform_wide", "zipf_hot", "all_same", "small_range", "many_buckets", "huge_bucket"])
 def test_multi_bitmap_matches_numpy(case, cuda, eng):
     """rc_bucket_multi_bitmap: bit (id) = 1 iff the row occurs at least twice -- for every id of the batch"""
