@@ -64,6 +64,42 @@ def workspace(nbytes, device, tag="default"):
     return buf
 
 
+def new_opt_state(t, opt):
+    """the row-wise optimizers' state of one tensor: {} (SGD), {"m"} (Adagrad's sum of squares) or {"m", "v"} (Adam's moments)"""
+    st = {"m": torch.zeros_like(t)} if opt in ("Adam", "Adagrad") else {}
+    if opt == "Adam":
+        st["v"] = torch.zeros_like(t)
+    return st
+
+
+# ---- the argument runs of the row-update entry points ---------------------------------------------------------------------------
+
+def _table_args(W, m, v, need_W=False, tag=""):
+    """(W, m, v) of one table (all null in dense-gradient mode), or of two where W, m and v are (table a, table b) pairs"""
+    if isinstance(W, tuple):
+        return _table_args(W[0], m[0], v[0], need_W, "_a") + _table_args(W[1], m[1], v[1], need_W, "_b")
+    f32 = torch.float32
+    return _ptr(W, f32, "W" + tag, not need_W), _ptr(m, f32, "m" + tag, True), _ptr(v, f32, "v" + tag, True)
+
+
+def _source_args(coef, src, src_index, div, src2, n_split, default=None, need_src=True, need_src2=False):
+    """(coef, src, src_index, div, src2, n_split): occurrence o < n_split brings coef[o] * src[src_index[o / div]] (no coef: 1, no
+    src_index: row o / div), occurrence o >= n_split the plain row src2[o - n_split].  default: what an omitted n_split means
+    to the caller -- the conventions differ, so every call site states its own"""
+    f32 = torch.float32
+    return (_ptr(coef, f32, "coef", True), _ptr(src, f32, "src", not need_src), _ptr(src_index, torch.int64, "src_index", True),
+            int(div), _ptr(src2, f32, "src2", not need_src2), int(default if n_split is None else n_split))
+
+
+def _ws_args(ws):
+    """the tail of every entry point with a workspace: (scratch pointer, its size, torch's current stream)"""
+    return C.c_void_p(ws.data_ptr()), ws.numel(), _stream()
+
+
+def _hyper_ref(hyper):
+    return C.byref(hyper) if hyper is not None else None
+
+
 # ---- forward ---------------------------------------------------------------------------
 
 def gather_rows(W, ids):
@@ -166,7 +202,7 @@ def sort_ids(ids, n_rows):
     ws = workspace(nbytes, dev, "sort")
     _lib.call("rc_sort_ids", _ptr(ids_flat, torch.int64, "ids"), n, None, 0, 0, int(n_rows),
               _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     return keys, perm
 
 
@@ -196,7 +232,7 @@ def bucket_plan(ids_a, range_a, ids_b=None, range_b=0, list_single_a=True):
               C.c_void_p(single.data_ptr()) if single is not None else None,
               C.c_void_p(rows_a.data_ptr()), C.c_void_p(cnt.data_ptr()),
               C.c_void_p(rows_b.data_ptr()), C.c_void_p(cnt[1:].data_ptr()),
-              C.c_void_p(occ.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              C.c_void_p(occ.data_ptr()), *_ws_args(ws))
     na, nb = (int(x) for x in cnt.tolist())
     return {"rows_a": rows_a[:na], "rows_b": rows_b[:nb], "occ": occ[:n_a + n_b],
             "single": None if single is None else single[:n_a]}
@@ -211,7 +247,7 @@ def bucket_multi_bitmap(ids, n_rows):
     bm = torch.empty(max(lib.rc_bucket_bitmap_bytes(int(n_rows)) // 4, 1), dtype=torch.int32, device=a.device)
     ws = workspace(lib.rc_bucket_plan_workspace_bytes(n, 0), a.device, "plan")
     _lib.call("rc_bucket_multi_bitmap", _ptr(a, torch.int64, "ids") if n else None, n, int(n_rows), C.c_void_p(bm.data_ptr()),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     return bm
 
 
@@ -250,6 +286,7 @@ class Plan:
                   None if list_single_a else p(buf[o_single:]),
                   p(self.rows_a), p(self.cnt), p(self.rows_b), p(self.cnt[4:]), p(self.occ), p(ws), ws.numel(), _stream())
         self._ws = ws
+        self.upd_counters = None    # prezero_update_counters: {side: counters zero-filled ahead for that side's next update_pair}
         if _PLAN_CHECK:     # RC_PLAN_CHECK=1: every plan reads its status word back (a host sync per plan: debugging only)
             self.check()
 
@@ -273,15 +310,9 @@ class Plan:
         n = self.n_a + self.n_b
         if n == 0:
             return out
-        rows, cnt, _ = self._side(side)
-        if n_split is None:
-            n_split = n if src2 is None else 0
         ws = workspace(_lib.load().rc_plan_update_workspace_bytes(n, d), out.device, self.tag + ".upd")
-        f32 = torch.float32
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _lib.call("rc_plan_row_sums", _ptr(out, f32, "out"), d, p(rows), p(cnt), p(self.occ), n, _ptr(coef, f32, "coef", True),
-                  _ptr(src, f32, "src", True), _ptr(src_index, torch.int64, "src_index", True), int(div),
-                  _ptr(src2, f32, "src2", True), int(n_split), p(ws), ws.numel(), _stream())
+        _lib.call("rc_plan_row_sums", _ptr(out, torch.float32, "out"), d, *self._records(side),
+                  *self._sources(coef, src, src_index, div, src2, n_split), *_ws_args(ws))
         return out
 
     def distinct(self, side):
@@ -298,6 +329,17 @@ class Plan:
     def _side(self, side):
         return (self.rows_a, self.cnt, 0) if side == "a" else (self.rows_b, self.cnt[4:], self.n_a)
 
+    def _records(self, side):
+        """(row records of list `side`, their count, the occurrence list, its length) as the update entry points take them"""
+        rows, cnt, _ = self._side(side)
+        return C.c_void_p(rows.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(self.occ.data_ptr()), self.n_a + self.n_b
+
+    def _sources(self, coef, src, src_index, div, src2, n_split):
+        """gradient sources as in segmented_update2 (positions of list b start at n_a).  An omitted n_split: every occurrence takes
+        `src` -- or, where only src2 is given, every occurrence takes src2"""
+        return _source_args(coef, src, src_index, div, src2, n_split, default=self.n_a + self.n_b if src2 is None else 0,
+                            need_src=False)
+
     def update_pair(self, side, Wa, Wb, src_a, src_b, hyper, ma=None, va=None, mb=None, vb=None, ws_tag=""):
         """rc_plan_update_pair on list `side` ('a' | 'b'): two tables sharing the ids, per-occurrence gradient rows.
         ws_tag: suffix of the scratch buffer's cache key -- two updates that run at the same time on two streams need two.
@@ -311,19 +353,16 @@ class Plan:
             srcs = (C.c_void_p(src_a.data_ptr()), None, int(src_a.stride(0)))
         else:
             srcs = (_ptr(src_a, f32, "src_a"), _ptr(src_b, f32, "src_b"), 0)
-        n = self.n_a + self.n_b
-        rows, cnt, base = self._side(side)
-        ws = workspace(_lib.load().rc_plan_update_workspace_bytes(n, 2 * d), Wa.device, self.tag + ".upd" + ws_tag)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        base = self._side(side)[2]
+        ws = workspace(_lib.load().rc_plan_update_workspace_bytes(self.n_a + self.n_b, 2 * d), Wa.device, self.tag + ".upd" + ws_tag)
         # ticket counters that were zero-filled with the plan (prezero_update_counters: beside other work, on the plan's stream);
         # one use each -- the memset in front of the update, a launch on the step's critical path, is left out
-        zc = getattr(self, "upd_counters", None)
+        zc = self.upd_counters
         c = zc.pop(side) if (zc is not None and side in zc) else None
         if c is not None:
             c.record_stream(torch.cuda.current_stream(c.device))
-        _lib.call("rc_plan_update_pair", _ptr(Wa, f32, "W_a"), _ptr(ma, f32, "m_a", True), _ptr(va, f32, "v_a", True),
-                  _ptr(Wb, f32, "W_b"), _ptr(mb, f32, "m_b", True), _ptr(vb, f32, "v_b", True), d, p(rows), p(cnt), p(self.occ), n,
-                  *srcs, base, C.byref(hyper), p(c) if c is not None else None, p(ws), ws.numel(), _stream())
+        _lib.call("rc_plan_update_pair", *_table_args((Wa, Wb), (ma, mb), (va, vb), need_W=True), d, *self._records(side),
+                  *srcs, base, C.byref(hyper), C.c_void_p(c.data_ptr()) if c is not None else None, *_ws_args(ws))
 
     def prezero_update_counters(self):
         """zero-fill the ticket counters of one later update_pair per side NOW, on the current stream (the plan's: beside the work the
@@ -332,19 +371,11 @@ class Plan:
         self.upd_counters = {"a": z[:8], "b": z[8:]}
 
     def update(self, side, W, hyper, m=None, v=None, coef=None, src=None, src_index=None, div=1, src2=None, n_split=None):
-        """rc_plan_update on list `side`: gradient sources as in segmented_update2 (positions of list b start at n_a)"""
+        """rc_plan_update on list `side`: the optimizer step of every listed row from its summed gradient row"""
         d = W.shape[1]
-        n = self.n_a + self.n_b
-        rows, cnt, _ = self._side(side)
-        if n_split is None:
-            n_split = n if src2 is None else 0
-        ws = workspace(_lib.load().rc_plan_update_workspace_bytes(n, d), W.device, self.tag + ".upd")
-        f32 = torch.float32
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _lib.call("rc_plan_update", _ptr(W, f32, "W"), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d, p(rows), p(cnt),
-                  p(self.occ), n, _ptr(coef, f32, "coef", True), _ptr(src, f32, "src", True),
-                  _ptr(src_index, torch.int64, "src_index", True), int(div), _ptr(src2, f32, "src2", True), int(n_split),
-                  C.byref(hyper), p(ws), ws.numel(), _stream())
+        ws = workspace(_lib.load().rc_plan_update_workspace_bytes(self.n_a + self.n_b, d), W.device, self.tag + ".upd")
+        _lib.call("rc_plan_update", *_table_args(W, m, v, need_W=True), d, *self._records(side),
+                  *self._sources(coef, src, src_index, div, src2, n_split), C.byref(hyper), *_ws_args(ws))
 
 
 def plan_supported(n_a, n_b, range_a, range_b):
@@ -401,22 +432,13 @@ def segmented_update(keys, perm, src, hyper=None, W=None, m=None, v=None, coef=N
     n_split (with src2): occurrences >= n_split take plain rows src2[o - n_split]."""
     n_occ = keys.numel()
     d = src.shape[-1]
-    dev = keys.device
-    lib = _lib.load()
-    ws = workspace(lib.rc_segmented_workspace_bytes(n_occ, d), dev, "seg")
-    hp = C.byref(hyper) if hyper is not None else None
-    _lib.call("rc_segmented_update",
-              _ptr(W, torch.float32, "W", allow_none=True),
-              _ptr(m, torch.float32, "m", allow_none=True),
-              _ptr(v, torch.float32, "v", allow_none=True), d,
-              _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
-              _ptr(coef, torch.float32, "coef", allow_none=True), _ptr(src, torch.float32, "src"),
-              _ptr(src_index, torch.int64, "src_index", allow_none=True), int(div),
-              _ptr(src2, torch.float32, "src2", allow_none=n_split is None), n_occ if n_split is None else int(n_split), 0, 0, hp,
-              _ptr(dense_grad, torch.float32, "dense_grad", allow_none=True),
+    ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, d), keys.device, "seg")
+    # an omitted n_split: every occurrence takes `src`; a given one needs its src2.  (0, 0: key_base, occ_base)
+    _lib.call("rc_segmented_update", *_table_args(W, m, v), d, _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
+              *_source_args(coef, src, src_index, div, src2, n_split, default=n_occ, need_src2=n_split is not None), 0, 0,
+              _hyper_ref(hyper), _ptr(dense_grad, torch.float32, "dense_grad", allow_none=True),
               _ptr(heads, torch.int32, "heads", True), _ptr(n_heads, torch.int32, "n_heads", True),
-              _lib.RC_SEG_SKIP_SINGLETONS if skip_singletons else 0,
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              _lib.RC_SEG_SKIP_SINGLETONS if skip_singletons else 0, *_ws_args(ws))
 
 
 def segmented_update_pair(keys, perm, src_a, src_b, hyper=None, W=(None, None), m=(None, None), v=(None, None),
@@ -427,13 +449,11 @@ def segmented_update_pair(keys, perm, src_a, src_b, hyper=None, W=(None, None), 
     d = src_a.shape[-1]
     f32 = torch.float32
     ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, 2 * d), keys.device, "seg")
-    _lib.call("rc_segmented_update_pair", _ptr(W[0], f32, "W_a", True), _ptr(m[0], f32, "m_a", True), _ptr(v[0], f32, "v_a", True),
-              _ptr(W[1], f32, "W_b", True), _ptr(m[1], f32, "m_b", True), _ptr(v[1], f32, "v_b", True), d,
+    _lib.call("rc_segmented_update_pair", *_table_args(tuple(W), tuple(m), tuple(v)), d,
               _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ, _ptr(src_a, f32, "src_a"),
-              _ptr(src_b, f32, "src_b"), C.byref(hyper) if hyper is not None else None,
+              _ptr(src_b, f32, "src_b"), _hyper_ref(hyper),
               _ptr(dense_grad[0], f32, "dense_grad_a", True), _ptr(dense_grad[1], f32, "dense_grad_b", True),
-              _ptr(heads, torch.int32, "heads", True), _ptr(n_heads, torch.int32, "n_heads", True),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              _ptr(heads, torch.int32, "heads", True), _ptr(n_heads, torch.int32, "n_heads", True), *_ws_args(ws))
 
 
 def segmented_pair_supported(d):
@@ -511,7 +531,7 @@ def embedding_dense_backward(grad_out, ids, n_rows, route=None, presorted=None, 
     n_ids = flat.numel()
     if route == "small" and small_route_ok(n_ids, n_rows, d):
         ws = workspace(_lib.load().rc_small_row_sums_workspace_bytes(n_ids), go.device, small_tag)
-        src, out, ws_args = _ptr(go, torch.float32, "grad_out"), _ptr(G, torch.float32, "G"), (C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+        src, out, ws_args = _ptr(go, torch.float32, "grad_out"), _ptr(G, torch.float32, "G"), _ws_args(ws)
         if small_again:
             _lib.call("rc_small_row_sums_planned", n_ids, int(n_rows), src, d, out, *_NO_PAIR, *_NO_NUMERIC, None, None, None, *ws_args)
         else:
@@ -573,7 +593,7 @@ def small_row_sums_pair(cid, n_rows, src_a, src_b, into=None, numeric=None):
     G = torch.zeros(n_rows * (d_a + d_b), dtype=f32, device=src_a.device) if into is None else into
     Ga, Gb = G[:n_rows * d_a].view(n_rows, d_a), G[n_rows * d_a:].view(n_rows, d_b)
     ws = workspace(_lib.load().rc_small_row_sums_workspace_bytes(n), src_a.device, "edb_small_pair")
-    ws_args = (C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+    ws_args = _ws_args(ws)
     rides = d_b == 1 and d_a >= 16      # the one-float-wide table rides in the vectors' row-sums launch
     if numeric is not None and not rides:
         raise ValueError("small_row_sums_pair: the numeric fields ride with d in 16 .. 128 beside a one-float-wide second source")
@@ -668,11 +688,8 @@ class BprmfTrainer:
         self.d = U.shape[1]
         self.opt = opt
         self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
-        self.mU = self.vU = self.mI = self.vI = None
-        if opt in ("Adam", "Adagrad"):
-            self.mU, self.mI = torch.zeros_like(U), torch.zeros_like(I)
-        if opt == "Adam":
-            self.vU, self.vI = torch.zeros_like(U), torch.zeros_like(I)
+        sU, sI = new_opt_state(U, opt), new_opt_state(I, opt)
+        self.mU, self.vU, self.mI, self.vI = sU.get("m"), sU.get("v"), sI.get("m"), sI.get("v")
         self.loss = torch.zeros(1, dtype=torch.float32, device=U.device)
         self._ws = None
         self._ws_shape = None
@@ -751,7 +768,7 @@ class BprmfTrainer:
                   C.byref(self._ticket), B, Cn, self.d,
                   self.U.shape[0], self.I.shape[0], C.byref(self.hyper), float(inv_b),
                   _ptr(self.loss, f32, "loss"), _ptr(pred, f32, "pred", True),
-                  C.c_void_p(ws.data_ptr()), ws.numel(), _stream(),
+                  *_ws_args(ws),
                   phase_ms if phase_ms is not None else None)
         return self.loss
 
@@ -866,7 +883,7 @@ def neumf_bwd(P, uid, iid, gpred, drop_p=0.0, seed=None):
               _ptr(gpred, f32, "gpred"), B, Cn, d, l1, *_drop_args(drop_p, seed),
               *[_ptr(rows[k], f32, k) for k in ("g_mf_u", "g_mf_i", "g_mlp_u", "g_mlp_i")],
               _ptr(dense["W1"], f32, "dW1"), _ptr(dense["b1"], f32, "db1"), _ptr(dense["w_out"], f32, "dw_out"),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     return rows, dense
 
 
@@ -874,11 +891,17 @@ def neumf_train_step_supported(Cn, d, l1):
     return bool(_lib.load().rc_neumf_train_step_supported(int(Cn), int(d), int(l1)))
 
 
+def neumf_head_kernel_selected(Cn, d, l1):
+    """the one-kernel NeuMF head (forward + BPR loss + backward: rc_neumf_train_step, rc_neumf_head_fwd_bwd) is switched on and
+    has an instance for Cn candidates per tuple"""
+    return bool(_NEUMF_FUSED and Cn >= 2 and neumf_train_step_supported(Cn, d, l1))
+
+
 def neumf_fused_step_selected(Cn, d, l1, opt="SGD"):
     """would NeumfTrainer.step take the one-kernel step (rc_neumf_train_step) for Cn candidates per tuple?  Everything its
-    selection tests except the batch's plan geometry (known only with the batch)"""
-    return bool(_USE_PLAN and _NEUMF_FUSED and opt in ("SGD", "Adam", "Adagrad") and Cn >= 2 and segmented_pair_supported(d)
-                and neumf_train_step_supported(Cn, d, l1))
+    selection tests except the batch's plan geometry (known only with the batch).  (Its table updates are pair updates from the
+    bucket plan; every width the kernel exists for has one.)"""
+    return bool(_USE_PLAN and opt in ("SGD", "Adam", "Adagrad") and neumf_head_kernel_selected(Cn, d, l1))
 
 
 def neumf_mark_rows(iid, n_items, marks, unmark=False):
@@ -908,7 +931,7 @@ def neumf_train_step(P, state, uid, iid, hyper, marks, out, inv_b=None, pred=Non
     tail = [_ptr(out["loss_vec"], f32, "loss_vec"), _ptr(pred, f32, "pred", True),
             _ptr(out["g_mf_i"], f32, "g_mf_i"), _ptr(out["g_mlp_i"], f32, "g_mlp_i"), _ptr(out["gu_mf"], f32, "gu_mf"),
             _ptr(out["gu_mlp"], f32, "gu_mlp"), _ptr(out["W1"], f32, "dW1"), _ptr(out["b1"], f32, "db1"),
-            _ptr(out["w_out"], f32, "dw_out"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()]
+            _ptr(out["w_out"], f32, "dw_out"), *_ws_args(ws)]
     inv = float(1.0 / B if inv_b is None else inv_b)
     _lib.call("rc_neumf_train_step", *head, 1 if marked else 0, C.byref(hyper), inv, *_drop_args(drop_p, seed), *tail)
 
@@ -939,7 +962,7 @@ def neumf_head_fwd_bwd(urows, irows, W1, b1, w_out, B, Cn, inv_b, want_pred=Fals
               _ptr(ids[1], torch.int64, "iid"), B, Cn, d, l1, float(inv_b), _ptr(loss_vec, f32, "loss_vec"),
               _ptr(pred, f32, "pred", True), off(gi, 0), off(gi, d), d2, off(gu, 0), off(gu, d), d2,
               _ptr(dense["W1"], f32, "dW1"), _ptr(dense["b1"], f32, "db1"), _ptr(dense["w_out"], f32, "dw_out"),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     return loss_vec, gu, gi, dense, pred
 
 
@@ -970,7 +993,7 @@ def neumf_zhead(urows, irows, W1, b1, w_out, B, Cn, inv_b, want_pred=False):
     _lib.call("rc_neumf_zhead_fwd_bwd", _ptr(urows, f32, "urows"), 2 * d, _ptr(zu, f32, "zu"), _ptr(irows, f32, "irows"), d + l1,
               _ptr(w_out, f32, "w_out"), B, Cn, d, l1, float(inv_b), _ptr(loss_vec, f32, "loss_vec"), _ptr(pred, f32, "pred", True),
               _ptr(gi, f32, "gi"), d + l1, _ptr(gu, f32, "gu"), 2 * d, _ptr(dzu, f32, "dzu"), _ptr(dw_out, f32, "dw_out"),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     dmlp_u, dW1u, db1 = linear_bwd(mlp_u, W1u, None, dzu, ws_tag="zhead_bwd")
     gu[:, d:] = dmlp_u
     return loss_vec, gu, gi, {"W1u": dW1u, "b1": db1, "w_out": dw_out}, pred
@@ -996,6 +1019,11 @@ class _PhaseTimer:
             self.t.setdefault(self.name, []).append((self.a, b))
 
 
+def _step_hypers(tr):
+    """(the hyper-parameters of trainer tr's current step, the same without weight decay: parameters named 'bias')"""
+    return make_hyper(tr.opt, lr=tr.lr, l2=tr.l2, step=tr.step_count), make_hyper(tr.opt, lr=tr.lr, l2=0.0, step=tr.step_count)
+
+
 def phases_ms(trainer):
     """MEDIAN milliseconds per phase of the steps recorded since trainer.timing = {} (synchronises).  (The mean until round 6: one
     eager step of twenty that meets an allocation on a side stream -- 68 ms once -- made a 0.05 ms phase read 3.4 ms.)"""
@@ -1013,25 +1041,24 @@ class NeumfTrainer:
     -> dense optimizer step of W1, b1, w_out.  P as in neumf_fwd; updated in place.
     dropout > 0: hidden-layer dropout with a fresh mask per step (device seed counter, bumped every step)."""
 
+    _n_trainers = 0
+    PAIRS = {"a": ("mf_i", "mlp_i"), "b": ("mf_u", "mlp_u")}    # bucket-plan list -> the two tables that share its ids
+
     def __init__(self, P, opt="Adam", lr=1e-3, l2=0.0, rowwise=True, dropout=0.0, seed=0):
         self.P, self.opt, self.lr, self.l2, self.rowwise = P, opt, lr, l2, rowwise
         self.dropout = float(dropout)
         self.seed = torch.tensor([seed], dtype=torch.int64, device=P["W1"].device) if self.dropout > 0 else None
-        self.state = {}
-        for k, t in P.items():
-            st = {}
-            if opt in ("Adam", "Adagrad"):
-                st["m"] = torch.zeros_like(t)
-            if opt == "Adam":
-                st["v"] = torch.zeros_like(t)
-            self.state[k] = st
+        self.state = {k: new_opt_state(t, opt) for k, t in P.items()}
         self.step_count = 0
         self.loss = None
-        self._side = None
+        self.timing = None                  # {} switches the per-phase events on (_PhaseTimer, phases_ms)
+        self._side = self._side2 = None     # streams of the steps that run on more than one (created with the first such step)
+        self._sum_idx = (None, None, None)  # three-kernel step: (B, C, device), positions and ones of the per-tuple user sums
+        self._marks = None                  # fused step: two flag buffers, this batch's and (prepared beside this step's updates) the next one's
+        self._fused_out = (None, None)      # ((B, C, device), the kernel's output buffers)
+        self._ahead = None                  # what the previous step prepared for an announced batch (_prepare_next)
         NeumfTrainer._n_trainers += 1
         self._serial = NeumfTrainer._n_trainers     # plan workspaces are cached by tag: one set per trainer
-
-    _n_trainers = 0
 
     def __del__(self):
         try:
@@ -1049,26 +1076,51 @@ class NeumfTrainer:
         """next_batch = (uid, iid) of the FOLLOWING call (the very tensors it will bring, unmodified until then): the fused step
         builds their bucket plan beside this step's table updates, off the critical path."""
         P = self.P
-        B, Cn = iid.shape
+        Cn = iid.shape[1]
+        d, l1 = P["mf_u"].shape[1], P["W1"].shape[0]
         self.step_count += 1
         if self.seed is not None:
             step_increment(self.seed)
-        pair_ok = segmented_pair_supported(P["mf_u"].shape[1])
-        n_u, n_i = P["mf_u"].shape[0], P["mf_i"].shape[0]
-        use_plan = self.rowwise and pair_ok and _USE_PLAN and plan_supported(iid.numel(), uid.numel(), n_i, n_u)
-        # the bucket plan needs only the ids: on a second stream it runs beside the head kernels (large batches; a small step is
-        # bound by the host's launch rate and the stream switches cost more than they return)
-        if (use_plan and _NEUMF_FUSED and self.opt in ("SGD", "Adam", "Adagrad") and Cn >= 2
-                and neumf_train_step_supported(Cn, P["mf_u"].shape[1], P["W1"].shape[0])):
+        # (every width a NeuMF kernel exists for -- 32, 64, 128 -- has a pair update kernel: no width test here)
+        use_plan = self.rowwise and _USE_PLAN and plan_supported(iid.numel(), uid.numel(), P["mf_i"].shape[0], P["mf_u"].shape[0])
+        if use_plan and neumf_fused_step_selected(Cn, d, l1, self.opt):
             return self._step_fused(uid, iid, next_batch)
-        if not neumf_supported(P["mf_u"].shape[1], P["W1"].shape[0]):
+        if not neumf_supported(d, l1):
             # (a tower that exists only inside the one-kernel step, e.g. hidden 16: say why this call cannot take it instead of
             # failing with RC_ERR_UNSUPPORTED inside rc_neumf_fwd)
             raise RuntimeError("NeumfTrainer: emb_size {} / hidden {} is a shape of the one-kernel step (rc_neumf_train_step) only, which this call "
                                "cannot take: {} candidates per tuple (needs >= 2 and the kernel's LDS budget: rc_neumf_train_step_supported), "
                                "plan {} (RC_TABLE_UPDATE, row-wise updates, a plan geometry for {} + {} ids), RC_NEUMF_FUSED={} -- use --engine "
-                               "dense for this configuration".format(P["mf_u"].shape[1], P["W1"].shape[0], Cn, "on" if use_plan else "off",
+                               "dense for this configuration".format(d, l1, Cn, "on" if use_plan else "off",
                                                                       iid.numel(), uid.numel(), int(_NEUMF_FUSED)))
+        return self._step_three_kernels(uid, iid, use_plan)
+
+    def _new_plan(self, uid, iid, buf=None):
+        """the bucket plan of both id lists (items: list a); buf: for the fused step, which updates single-occurrence item rows
+        itself -- they are flagged, not listed -- and alternates between two sets of plan buffers"""
+        n_i, n_u = self.P["mf_i"].shape[0], self.P["mf_u"].shape[0]
+        if buf is None:
+            return Plan(iid, n_i, uid, n_u, tag="neumf")
+        return Plan(iid, n_i, uid, n_u, tag="neumf%d.%d" % (self._serial, buf), list_single_a=False)
+
+    def _update_pair(self, plan, side, ga, gb, h, ws_tag=""):
+        """the row-wise step of the two tables behind plan list `side` from their per-occurrence gradient rows"""
+        ta, tb = self.PAIRS[side]
+        sa, sb = self.state[ta], self.state[tb]
+        plan.update_pair(side, self.P[ta], self.P[tb], ga, gb, h, ma=sa.get("m"), va=sa.get("v"), mb=sb.get("m"), vb=sb.get("v"),
+                         ws_tag=ws_tag)
+
+    def _dense_step(self, grads, h, h0):
+        with _PhaseTimer(self, "dense_update"):
+            dense_update_multi([(self.P[k], grads[k], h0 if k == "b1" else h, self.state[k].get("m"), self.state[k].get("v"))
+                                for k in ("W1", "b1", "w_out")], self.opt)
+
+    def _step_three_kernels(self, uid, iid, use_plan):
+        """rc_neumf_fwd, rc_bpr_loss_fwd_bwd, rc_neumf_bwd, then the table updates from the bucket plan (use_plan) or behind a sort"""
+        P = self.P
+        B, Cn = iid.shape
+        # the bucket plan needs only the ids: on a second stream it runs beside the head kernels (large batches; a small step is
+        # bound by the host's launch rate and the stream switches cost more than they return)
         overlap = use_plan and _NEUMF_OVERLAP and iid.is_cuda and iid.numel() >= _SAS_OVERLAP_MIN
         plan = plan_done = main = None
         if overlap:
@@ -1077,7 +1129,7 @@ class NeumfTrainer:
             main, side = torch.cuda.current_stream(iid.device), self._side
             side.wait_stream(main)   # the batch is ready; last step's readers of the plan buffers are done
             with torch.cuda.stream(side):
-                plan = Plan(iid, n_i, uid, n_u, tag="neumf")
+                plan = self._new_plan(uid, iid)
                 plan_done = side.record_event()
         with _PhaseTimer(self, "head_fwd"):
             pred = neumf_fwd(P, uid, iid, self.dropout, self.seed)
@@ -1085,36 +1137,54 @@ class NeumfTrainer:
             self.loss, _, gpred = bpr_loss(pred)
         with _PhaseTimer(self, "head_bwd"):
             rows, dense = neumf_bwd(P, uid, iid, gpred, self.dropout, self.seed)
-        h = make_hyper(self.opt, lr=self.lr, l2=self.l2, step=self.step_count)
-        h0 = make_hyper(self.opt, lr=self.lr, l2=0.0, step=self.step_count)  # 'bias' params: no weight decay
+        h, h0 = _step_hypers(self)
         if use_plan:
             # ONE bucket plan of both id lists (round 3: hashed buckets where the id space is wide and sparse -- 0.33 M item
             # lookups over 10 M - 100 M rows -- so the cost follows the keys, not the id range; round 2's id-range
             # buckets cost as much as the radix sort here and the sort stayed), then one pair update per side: the
-            # mf / mlp tables of a side share ids, records and positions.  The user side is planned per TUPLE: the head
-            # kernel's per-candidate user gradients are summed over a tuple's candidates first (fixed order c = 0..C-1), so
-            # a hot user contributes B_u occurrences, not C * B_u.
+            # mf / mlp tables of a side share ids, records and positions.
             with _PhaseTimer(self, "sort"):
                 if overlap:
                     main.wait_event(plan_done)
                 else:
-                    plan = Plan(iid, n_i, uid, n_u, tag="neumf")
+                    plan = self._new_plan(uid, iid)
             with _PhaseTimer(self, "table_update"):
+                # The user side is planned per TUPLE: the head kernel's per-candidate user gradients are summed over a tuple's
+                # candidates first (fixed order c = 0..C-1), so a hot user contributes B_u occurrences, not C * B_u.
                 key = (B, Cn, str(uid.device))
-                if getattr(self, "_sum_idx", (None,))[0] != key:
+                if self._sum_idx[0] != key:
                     self._sum_idx = (key, torch.arange(B * Cn, device=uid.device).view(B, Cn), torch.ones((B, Cn), device=uid.device))
                 _, pos, ones = self._sum_idx
                 gu_a, gu_b = weighted_row_sum(rows["g_mf_u"], pos, ones), weighted_row_sum(rows["g_mlp_u"], pos, ones)
-                for side, ta, tb, ga, gb in (("b", "mf_u", "mlp_u", gu_a, gu_b), ("a", "mf_i", "mlp_i", rows["g_mf_i"], rows["g_mlp_i"])):
-                    sa, sb = self.state[ta], self.state[tb]
-                    plan.update_pair(side, P[ta], P[tb], ga, gb, h, ma=sa.get("m"), va=sa.get("v"),
-                                     mb=sb.get("m"), vb=sb.get("v"))
+                self._update_pair(plan, "b", gu_a, gu_b, h)
+                self._update_pair(plan, "a", rows["g_mf_i"], rows["g_mlp_i"], h)
         else:
-            self._step_tables_sorted(P, uid.repeat_interleave(Cn), iid, rows, h, pair_ok)
-        with _PhaseTimer(self, "dense_update"):
-            dense_update_multi([(P[k], dense[k], h0 if k == "b1" else h, self.state[k].get("m"), self.state[k].get("v"))
-                                for k in ("W1", "b1", "w_out")], self.opt)
+            self._step_tables_sorted(uid.repeat_interleave(Cn), iid, rows, h)
+        self._dense_step(dense, h, h0)
         return self.loss
+
+    def _step_tables_sorted(self, uid_occ, iid, rows, h):
+        """the table updates behind a radix sort (dense-gradient mode = the reference's exact optimizer semantics, id spaces no
+        plan geometry covers)"""
+        P = self.P
+        with _PhaseTimer(self, "sort"):
+            ku, pu = sort_ids(uid_occ, P["mf_u"].shape[0])
+            ki, pi = sort_ids(iid, P["mf_i"].shape[0])
+            # the mf / mlp tables of a side share ids: one sort, ONE head list and ONE update pass serve both
+            _, hu, nhu = segment_heads(ku, pu, want_single=False)
+            _, hi, nhi = segment_heads(ki, pi, want_single=False)
+        with _PhaseTimer(self, "table_update"):
+            for side, ga, gb, keys, perm, hd, nh in (("b", "g_mf_u", "g_mlp_u", ku, pu, hu, nhu), ("a", "g_mf_i", "g_mlp_i", ki, pi, hi, nhi)):
+                ta, tb = self.PAIRS[side]
+                sa, sb = self.state[ta], self.state[tb]
+                if self.rowwise:
+                    segmented_update_pair(keys, perm, rows[ga], rows[gb], hyper=h, W=(P[ta], P[tb]), m=(sa.get("m"), sb.get("m")),
+                                          v=(sa.get("v"), sb.get("v")), heads=hd, n_heads=nh)
+                else:
+                    G = (torch.zeros_like(P[ta]), torch.zeros_like(P[tb]))
+                    segmented_update_pair(keys, perm, rows[ga], rows[gb], dense_grad=G, heads=hd, n_heads=nh)
+                    dense_update(P[ta], G[0], h, sa.get("m"), sa.get("v"))
+                    dense_update(P[tb], G[1], h, sb.get("m"), sb.get("v"))
 
     @staticmethod
     def _batch_key(uid, iid):
@@ -1128,151 +1198,130 @@ class NeumfTrainer:
         only; user side: one gradient row per tuple) on two streams.  The fused kernel leaves no register for a co-resident wave,
         so a plan built beside it would wait for its workgroups to retire: the plan of the NEXT batch is built beside this
         step's table updates instead (next_batch), the batch's own plan only when nobody announced it."""
-        P = self.P
-        B, Cn = iid.shape
+        B = iid.shape[0]
         dev = iid.device
-        d = P["mf_u"].shape[1]
-        n_u, n_i = P["mf_u"].shape[0], P["mf_i"].shape[0]
-        if getattr(self, "_marks", None) is None:   # two buffers: this batch's flags and, prepared beside this step's updates, the next batch's
-            nbytes = max(int(_lib.load().rc_neumf_train_step_marks_bytes(n_i)), 1)
-            self._marks = [torch.zeros(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
-        key = (B, Cn, str(dev))
-        if getattr(self, "_fused_out", (None,))[0] != key:
-            e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            self._fused_out = (key, {"loss_vec": e(B), "g_mf_i": e(B * Cn, d), "g_mlp_i": e(B * Cn, d), "gu_mf": e(B, d), "gu_mlp": e(B, d),
-                                     "W1": torch.empty_like(P["W1"]), "b1": torch.empty_like(P["b1"]), "w_out": torch.empty_like(P["w_out"])})
-        out = self._fused_out[1]
+        out = self._fused_buffers(*iid.shape, dev)
         two_streams = _NEUMF_OVERLAP and iid.numel() >= _SAS_OVERLAP_MIN
         main = torch.cuda.current_stream(dev)
         if two_streams and self._side is None:
             self._side, self._side2 = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-        ahead = getattr(self, "_ahead", None)
-        self._ahead = None
-        plan = plan_done = marks_done = None
-        # which of the two flag buffers / plan workspaces this step uses travels WITH the announcement (not with step_count:
-        # a non-fused step in between, or a second trainer, must not shift it); with nothing pending both buffers are clean
-        buf = 0
-        if ahead is not None and ahead["key"] == self._batch_key(uid, iid):
-            plan, plan_done, marks_done, buf = ahead["plan"], ahead["plan_done"], ahead["marks_done"], ahead["buf"]
-        elif ahead is not None:
-            # a batch was announced and another one came: its prepared flags have to go before that buffer is marked again
-            with torch.cuda.stream(self._side):
-                neumf_mark_rows(ahead["iid"], n_i, self._marks[ahead["buf"]], unmark=True)
-            main.wait_stream(self._side)
-        ahead = None    # (drops the reference to the announced id tensors kept for the side stream's reads)
-        tag = lambda k: "neumf%d.%d" % (self._serial, k)
+        plan, plan_done, marks_done, buf = self._claim_ahead(uid, iid, main)
         if plan is None and two_streams:
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                plan = Plan(iid, n_i, uid, n_u, tag=tag(buf), list_single_a=False)
-                plan.prezero_update_counters()
-                plan_done = self._side.record_event()
-            iid.record_stream(self._side)
-            uid.record_stream(self._side)
-        h = make_hyper(self.opt, lr=self.lr, l2=self.l2, step=self.step_count)
-        h0 = make_hyper(self.opt, lr=self.lr, l2=0.0, step=self.step_count)
-        with _PhaseTimer(self, "fused_step"):
-            if marks_done is not None:      # flags prepared beside the previous step's updates
-                main.wait_event(marks_done)
-                neumf_train_step(P, self.state, uid, iid, h, self._marks[buf], out, marked=True, drop_p=self.dropout, seed=self.seed)
-            else:
-                neumf_train_step(P, self.state, uid, iid, h, self._marks[buf], out, drop_p=self.dropout, seed=self.seed)
-        if marks_done is not None and not two_streams:
-            # prepared flags are ALWAYS cleared by the step that consumed them -- also a short step (a ragged last batch of an
-            # epoch announced by a large one) that runs on one stream: a flag left behind would make a later single occurrence
-            # of that row look like a multiple one, and its update would be dropped
-            neumf_mark_rows(iid, n_i, self._marks[buf], unmark=True)
+            plan, plan_done = self._plan_on_side(uid, iid, buf, main)
+        h, h0 = _step_hypers(self)
+        self._fused_kernel(uid, iid, h, buf, out, marks_done, main, two_streams)
         loss_done = None
         if two_streams:
-            self._side.wait_stream(main)    # behind the fused kernel: beside the updates below
-            with torch.cuda.stream(self._side):
-                # the batch mean of the per-tuple losses (one workgroup) FIRST on the plan's stream: nothing of this step waits for it
-                # (main joins it at the very end), and the streams that carry the two table updates start those at once.  (Round 5
-                # had it in front of the user-side update: 28 us on the critical path of the step.)
-                self.loss = reduce_sum(out["loss_vec"], 1.0 / B)
-                loss_done = self._side.record_event()
-        if two_streams and (next_batch is not None or marks_done is not None):
-            with torch.cuda.stream(self._side):
-                if marks_done is not None:
-                    neumf_mark_rows(iid, n_i, self._marks[buf], unmark=True)
-                    iid.record_stream(self._side)   # the runner drops the batch when step() returns; the allocator must not
-                                                    # hand its block out while the side stream still reads it
-                if next_batch is not None:
-                    # the following batch's flags and plan; their buffers alternate with this batch's
-                    nu, ni = next_batch
-                    neumf_mark_rows(ni, n_i, self._marks[buf ^ 1])
-                    nmarks_done = self._side.record_event()
-                    nplan = Plan(ni, n_i, nu, n_u, tag=tag(buf ^ 1), list_single_a=False)
-                    nplan.prezero_update_counters()
-                    ni.record_stream(self._side)
-                    nu.record_stream(self._side)
-                    self._ahead = {"key": self._batch_key(nu, ni), "plan": nplan, "plan_done": self._side.record_event(),
-                                   "marks_done": nmarks_done, "iid": ni, "buf": buf ^ 1}
-        if two_streams:
+            loss_done = self._side_stream_work(iid, next_batch, buf, marks_done is not None, out, main)
             self._side2.wait_stream(main)
         else:
             with _PhaseTimer(self, "loss"):
                 self.loss = reduce_sum(out["loss_vec"], 1.0 / B)
         with _PhaseTimer(self, "sort"):
             if plan is None:
-                plan = Plan(iid, n_i, uid, n_u, tag=tag(buf), list_single_a=False)
+                plan = self._new_plan(uid, iid, buf)
             elif plan_done is not None:
                 main.wait_event(plan_done)
         with _PhaseTimer(self, "table_update"):
-            sides = (("a", "mf_i", "mlp_i", out["g_mf_i"], out["g_mlp_i"]), ("b", "mf_u", "mlp_u", out["gu_mf"], out["gu_mlp"]))
-
-            def upd(side_, ta, tb, ga, gb):
-                sa, sb = self.state[ta], self.state[tb]
-                plan.update_pair(side_, P[ta], P[tb], ga, gb, h, ma=sa.get("m"), va=sa.get("v"), mb=sb.get("m"), vb=sb.get("v"), ws_tag=side_)
-            if two_streams:   # item tables and user tables are disjoint: the two updates run side by side
-                if plan_done is not None:
-                    self._side2.wait_event(plan_done)
-                with torch.cuda.stream(self._side2):
-                    upd(*sides[1])
-                upd(*sides[0])
-                main.wait_stream(self._side2)
-            else:
-                upd(*sides[0])
-                upd(*sides[1])
-        with _PhaseTimer(self, "dense_update"):
-            dense_update_multi([(P[k], out[k], h0 if k == "b1" else h, self.state[k].get("m"), self.state[k].get("v"))
-                                for k in ("W1", "b1", "w_out")], self.opt)
+            self._fused_table_updates(plan, plan_done, out, h, main, two_streams)
+        self._dense_step(out, h, h0)
         if loss_done is not None:
             main.wait_event(loss_done)      # (long complete: the caller reads the loss on this stream)
         return self.loss
 
-    def _step_tables_sorted(self, P, uid_occ, iid, rows, h, pair_ok):
-        """the table updates behind a radix sort (dense-gradient mode = the reference's exact optimizer semantics, widths
-        without a pair kernel, id spaces no plan geometry covers)"""
-        with _PhaseTimer(self, "sort"):
-            ku, pu = sort_ids(uid_occ, P["mf_u"].shape[0])
-            ki, pi = sort_ids(iid, P["mf_i"].shape[0])
-            # the mf / mlp tables of a side share ids: one sort, ONE head list and ONE update pass serve both
-            _, hu, nhu = segment_heads(ku, pu, want_single=False)
-            _, hi, nhi = segment_heads(ki, pi, want_single=False)
-        _upd = _PhaseTimer(self, "table_update")
-        _upd.__enter__()
-        for ta, tb, ga, gb, keys, perm, hd, nh in (("mf_u", "mlp_u", "g_mf_u", "g_mlp_u", ku, pu, hu, nhu),
-                                                   ("mf_i", "mlp_i", "g_mf_i", "g_mlp_i", ki, pi, hi, nhi)):
-            sa, sb = self.state[ta], self.state[tb]
-            G = (torch.zeros_like(P[ta]), torch.zeros_like(P[tb])) if not self.rowwise else (None, None)
-            if pair_ok and self.rowwise:
-                segmented_update_pair(keys, perm, rows[ga], rows[gb], hyper=h, W=(P[ta], P[tb]), m=(sa.get("m"), sb.get("m")),
-                                      v=(sa.get("v"), sb.get("v")), heads=hd, n_heads=nh)
-            elif pair_ok:
-                segmented_update_pair(keys, perm, rows[ga], rows[gb], dense_grad=G, heads=hd, n_heads=nh)
-            else:
-                for k, (tab, grad) in enumerate(((ta, ga), (tb, gb))):
-                    st = self.state[tab]
-                    if self.rowwise:
-                        segmented_update(keys, perm, rows[grad], hyper=h, W=P[tab], m=st.get("m"), v=st.get("v"), heads=hd,
-                                         n_heads=nh)
-                    else:
-                        segmented_update(keys, perm, rows[grad], dense_grad=G[k], heads=hd, n_heads=nh)
-            if not self.rowwise:
-                dense_update(P[ta], G[0], h, sa.get("m"), sa.get("v"))
-                dense_update(P[tb], G[1], h, sb.get("m"), sb.get("v"))
-        _upd.__exit__()
+    def _fused_buffers(self, B, Cn, dev):
+        """the flag buffers (once) and the fused kernel's outputs (per batch shape) -> the outputs"""
+        P = self.P
+        d = P["mf_u"].shape[1]
+        if self._marks is None:
+            nbytes = max(int(_lib.load().rc_neumf_train_step_marks_bytes(P["mf_i"].shape[0])), 1)
+            self._marks = [torch.zeros(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        key = (B, Cn, str(dev))
+        if self._fused_out[0] != key:
+            e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            self._fused_out = (key, {"loss_vec": e(B), "g_mf_i": e(B * Cn, d), "g_mlp_i": e(B * Cn, d), "gu_mf": e(B, d), "gu_mlp": e(B, d),
+                                     "W1": torch.empty_like(P["W1"]), "b1": torch.empty_like(P["b1"]), "w_out": torch.empty_like(P["w_out"])})
+        return self._fused_out[1]
+
+    def _claim_ahead(self, uid, iid, main):
+        """-> (plan, plan_done, marks_done, buf) prepared for THIS batch by the previous step, or (None, None, None, 0).
+        Which of the two flag buffers / plan workspaces this step uses travels WITH the announcement (not with step_count:
+        a non-fused step in between, or a second trainer, must not shift it); with nothing pending both buffers are clean."""
+        ahead, self._ahead = self._ahead, None
+        if ahead is None:
+            return None, None, None, 0
+        if ahead["key"] == self._batch_key(uid, iid):
+            return ahead["plan"], ahead["plan_done"], ahead["marks_done"], ahead["buf"]
+        # a batch was announced and another one came: its prepared flags have to go before that buffer is marked again
+        with torch.cuda.stream(self._side):
+            neumf_mark_rows(ahead["iid"], self.P["mf_i"].shape[0], self._marks[ahead["buf"]], unmark=True)
+        main.wait_stream(self._side)
+        return None, None, None, 0    # (the announced id tensors, kept for the side stream's reads, go with `ahead`)
+
+    def _plan_on_side(self, uid, iid, buf, main):
+        """this batch's plan, which nobody prepared, on the side stream beside the fused kernel -> (plan, event: plan complete)"""
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side):
+            plan = self._new_plan(uid, iid, buf)
+            plan.prezero_update_counters()
+            plan_done = self._side.record_event()
+        iid.record_stream(self._side)
+        uid.record_stream(self._side)
+        return plan, plan_done
+
+    def _fused_kernel(self, uid, iid, h, buf, out, marks_done, main, two_streams):
+        """rc_neumf_train_step on flag buffer `buf`, whose flags the kernel itself or -- marks_done -- the previous step set"""
+        with _PhaseTimer(self, "fused_step"):
+            if marks_done is not None:      # flags prepared beside the previous step's updates
+                main.wait_event(marks_done)
+            neumf_train_step(self.P, self.state, uid, iid, h, self._marks[buf], out, marked=marks_done is not None, drop_p=self.dropout,
+                             seed=self.seed)
+        if marks_done is not None and not two_streams:
+            # prepared flags are ALWAYS cleared by the step that consumed them -- also a short step (a ragged last batch of an
+            # epoch announced by a large one) that runs on one stream: a flag left behind would make a later single occurrence
+            # of that row look like a multiple one, and its update would be dropped
+            neumf_mark_rows(iid, self.P["mf_i"].shape[0], self._marks[buf], unmark=True)
+
+    def _side_stream_work(self, iid, next_batch, buf, clear_marks, out, main):
+        """on the side stream, beside this step's table updates: the loss, the prepared flags this step consumed cleared
+        (clear_marks), the announced batch's flags and plan (kept in self._ahead for the step that brings it) -> event: loss complete"""
+        n_i = self.P["mf_i"].shape[0]
+        self._side.wait_stream(main)    # behind the fused kernel: beside the updates below
+        with torch.cuda.stream(self._side):
+            # the batch mean of the per-tuple losses (one workgroup) FIRST on the plan's stream: nothing of this step waits for it
+            # (main joins it at the very end), and the streams that carry the two table updates start those at once.  (Round 5
+            # had it in front of the user-side update: 28 us on the critical path of the step.)
+            self.loss = reduce_sum(out["loss_vec"], 1.0 / iid.shape[0])
+            loss_done = self._side.record_event()
+            if clear_marks:
+                neumf_mark_rows(iid, n_i, self._marks[buf], unmark=True)
+                iid.record_stream(self._side)   # the runner drops the batch when step() returns; the allocator must not
+                                                # hand its block out while the side stream still reads it
+            if next_batch is not None:
+                # the following batch's flags and plan; their buffers alternate with this batch's
+                nu, ni = next_batch
+                neumf_mark_rows(ni, n_i, self._marks[buf ^ 1])
+                nmarks_done = self._side.record_event()
+                nplan = self._new_plan(nu, ni, buf ^ 1)
+                nplan.prezero_update_counters()
+                ni.record_stream(self._side)
+                nu.record_stream(self._side)
+                self._ahead = {"key": self._batch_key(nu, ni), "plan": nplan, "plan_done": self._side.record_event(),
+                               "marks_done": nmarks_done, "iid": ni, "buf": buf ^ 1}
+        return loss_done
+
+    def _fused_table_updates(self, plan, plan_done, out, h, main, two_streams):
+        """item side: the multi-occurrence rows (the fused kernel updated the others); user side: one gradient row per tuple"""
+        if two_streams:   # item tables and user tables are disjoint: the two updates run side by side
+            if plan_done is not None:
+                self._side2.wait_event(plan_done)
+            with torch.cuda.stream(self._side2):
+                self._update_pair(plan, "b", out["gu_mf"], out["gu_mlp"], h, ws_tag="b")
+            self._update_pair(plan, "a", out["g_mf_i"], out["g_mlp_i"], h, ws_tag="a")
+            main.wait_stream(self._side2)
+        else:
+            self._update_pair(plan, "a", out["g_mf_i"], out["g_mlp_i"], h, ws_tag="a")
+            self._update_pair(plan, "b", out["gu_mf"], out["gu_mlp"], h, ws_tag="b")
 
 
 # ---- dense layers (csrc/mlp.hip) -------------------------------------------------------------------------
@@ -1286,7 +1335,7 @@ def linear_fwd(X, W, b=None, relu=False, drop_p=0.0, seed=None, site=0):
     Y = torch.empty((M, N), dtype=f32, device=X.device)
     ws = workspace(_lib.load().rc_linear_fwd_workspace_bytes(M, N, K), X.device, "linear_fwd")   # split-K planes of a small batch
     _lib.call("rc_linear_fwd", _ptr(X, f32, "X"), _ptr(W, f32, "W"), _ptr(b, f32, "b", True), M, N, K, 1 if relu else 0,
-              *_drop_args(drop_p, seed), C.c_uint32(int(site)), _ptr(Y, f32, "Y"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_drop_args(drop_p, seed), C.c_uint32(int(site)), _ptr(Y, f32, "Y"), *_ws_args(ws))
     return Y
 
 
@@ -1306,7 +1355,7 @@ def linear_bwd(X, W, Y, dY, drop_p=0.0, need_dx=True, need_db=True, x_act=False,
     ws = workspace(_lib.load().rc_linear_bwd_workspace_bytes(M, N, K), dev, ws_tag)
     _lib.call("rc_linear_bwd", _ptr(X, f32, "X"), _ptr(W, f32, "W"), _ptr(Y, f32, "Y", True), _ptr(dY, f32, "dY"), M, N, K,
               C.c_float(float(drop_p)), 1 if (x_act and need_dx) else 0, C.c_float(float(x_drop_p)), _ptr(dX, f32, "dX", True),
-              _ptr(dW, f32, "dW", True), _ptr(db, f32, "db", True), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              _ptr(dW, f32, "dW", True), _ptr(db, f32, "db", True), *_ws_args(ws))
     return dX, dW, db
 
 
@@ -1348,7 +1397,7 @@ def tower_tail_bwd(X, W2, w3, H2, dz, drop_p=0.0, need_dx=True, x_act=False, x_d
     _lib.call("rc_tower_tail_bwd", _ptr(X, f32, "X"), _ptr(W2, f32, "W2"), _ptr(w3, f32, "w3"), _ptr(H2, f32, "H2"), _ptr(dz, f32, "dz"), M, K, N2,
               C.c_float(float(drop_p)), 1 if (x_act and need_dx) else 0, C.c_float(float(x_drop_p)), _ptr(dX, f32, "dX", True),
               _ptr(dW2, f32, "dW2"), _ptr(db2, f32, "db2", True), _ptr(dW3, f32, "dw3"), _ptr(db3, f32, "db3", True),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     return dX, dW2, db2, dW3, db3
 
 
@@ -1438,14 +1487,14 @@ def sasrec_fwd(item_emb, pos_emb, layers, n_heads, hist, lengths, save=False, im
         _lib.call("rc_sasrec_batch_fwd", _ptr(item_emb, f32, "item_emb"), _ptr(pos_emb, f32, "pos_emb"),
                   _sas_ptr_table(layers), len(layers), int(n_heads), _ptr(hist, torch.int64, "hist"),
                   _ptr(lengths, torch.int64, "lengths"), B, L, d, *_drop_args(drop_p, seed), _ptr(hv, f32, "hv"),
-                  _ptr(state, f32, "state"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+                  _ptr(state, f32, "state"), *_ws_args(ws))
         return hv, (SasSaved("batch", state, B, len(layers), L, d) if save else None)
     xsave = torch.empty((B, len(layers), L, d), dtype=f32, device=dev) if save else None
     ws = workspace(lib.rc_sasrec_workspace_bytes(B, d, len(layers)), dev, "sasrec")
     _lib.call("rc_sasrec_fwd", _ptr(item_emb, f32, "item_emb"), _ptr(pos_emb, f32, "pos_emb"),
               _sas_ptr_table(layers), len(layers), int(n_heads), _ptr(hist, torch.int64, "hist"),
               _ptr(lengths, torch.int64, "lengths"), B, L, d, _ptr(hv, f32, "hv"),
-              _ptr(xsave, f32, "xsave", True), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              _ptr(xsave, f32, "xsave", True), *_ws_args(ws))
     return hv, (SasSaved("sequence", xsave, B, len(layers), L, d) if save else None)
 
 
@@ -1492,7 +1541,7 @@ def sasrec_bwd(layers, n_heads, lengths, saved, dhv, drop_p=0.0, seed=None, spli
         ws = workspace(lib.rc_sasrec_workspace_bytes(B, d, n_layers), dev, "sasrec")
         _lib.call("rc_sasrec_bwd", _sas_ptr_table(layers), n_layers, int(n_heads), _ptr(lengths, torch.int64, "lengths"),
                   B, L, d, _ptr(saved.data, f32, "xsave"), _ptr(dhv, f32, "dhv"), _ptr(g_hist, f32, "g_hist"),
-                  _ptr(dense, f32, "dense"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+                  _ptr(dense, f32, "dense"), *_ws_args(ws))
     if split:
         return g_hist, _sas_dense_views(dense, n_layers, d), (lambda: None)
     return g_hist, _sas_dense_views(dense, n_layers, d)
@@ -1505,7 +1554,7 @@ def sasrec_pos_grad(g_hist, lengths, n_pos):
     out = torch.empty((n_pos, d), dtype=torch.float32, device=g_hist.device)
     ws = workspace(_lib.load().rc_sasrec_pos_grad_workspace_bytes(B, L, d), g_hist.device, "sasrec_pos")
     _lib.call("rc_sasrec_pos_grad", _ptr(g_hist, torch.float32, "g_hist"), _ptr(lengths, torch.int64, "lengths"), B, L, d,
-              int(n_pos), _ptr(out, torch.float32, "grad_pos"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              int(n_pos), _ptr(out, torch.float32, "grad_pos"), *_ws_args(ws))
     return out
 
 
@@ -1611,7 +1660,7 @@ def seq_add_layernorm_bwd(dY, xhat, rstd, w, off, L, drop_p=0.0, seed=None, site
     ws = workspace(_lib.load().rc_seq_add_layernorm_bwd_workspace_bytes(d), dY.device, "seq_ln_bwd")
     _lib.call("rc_seq_add_layernorm_bwd", _ptr(dY, f32, "dY"), _ptr(xhat, f32, "xhat"), _ptr(rstd, f32, "rstd"), _ptr(w, f32, "w"),
               _ptr(off, torch.int32, "off", True), rows, int(L), d, *_drop_args(drop_p, seed), C.c_uint32(int(site)), _ptr(dA, f32, "dA", True),
-              _ptr(dR, f32, "dR", True), _ptr(dw, f32, "dw"), _ptr(db, f32, "db"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              _ptr(dR, f32, "dR", True), _ptr(dw, f32, "dw"), _ptr(db, f32, "db"), *_ws_args(ws))
     return dA, dR, dw, db
 
 
@@ -1633,12 +1682,10 @@ def segmented_update2(keys, perm, src, src2, n_split, hyper=None, W=None, m=None
     if seg_rows_route(n_occ, n_rows, d):
         # every row collects many occurrences (a small catalogue under a large batch): one wave per table row
         ws = workspace(_lib.load().rc_segmented_rows_workspace_bytes(n_rows, n_occ, d), keys.device, "seg_rows")
-        _lib.call("rc_segmented_update_rows", _ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), d,
-                  n_rows, _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
-                  _ptr(coef, f32, "coef", True), _ptr(src, f32, "src"), _ptr(src_index, torch.int64, "src_index", True),
-                  int(div), _ptr(src2, f32, "src2"), int(n_split), C.byref(hyper) if hyper is not None else None,
-                  _ptr(step_dev, torch.int64, "step_dev", True), _ptr(dense_grad, f32, "dense_grad", True),
-                  C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+        _lib.call("rc_segmented_update_rows", *_table_args(W, m, v), d, n_rows, _ptr(keys, torch.int32, "keys"),
+                  _ptr(perm, torch.int32, "perm"), n_occ, *_source_args(coef, src, src_index, div, src2, n_split, need_src2=True),
+                  _hyper_ref(hyper), _ptr(step_dev, torch.int64, "step_dev", True), _ptr(dense_grad, f32, "dense_grad", True),
+                  *_ws_args(ws))
         return
     if step_dev is not None:
         raise RuntimeError("segmented_update2(step_dev=...): the device-side step count is carried by the one-wave-per-row "
@@ -1669,17 +1716,14 @@ class RowsPlan:
             _rows_plan_zeroed.add(self.ws.data_ptr())
         L = ids_b.shape[-1] if (ids_b is not None and lengths_b is not None) else 1
         _lib.call("rc_rows_plan_build", _ptr(ids_a, torch.int64, "ids_a"), self.n_a, _ptr(ids_b, torch.int64, "ids_b", True), self.n_b,
-                  _ptr(lengths_b, torch.int64, "lengths_b", True), int(L), self.n_rows, self.d, C.c_void_p(self.ws.data_ptr()),
-                  self.ws.numel(), _stream())
+                  _ptr(lengths_b, torch.int64, "lengths_b", True), int(L), self.n_rows, self.d, *_ws_args(self.ws))
 
     def update(self, src, hyper=None, W=None, m=None, v=None, coef=None, src_index=None, div=1, src2=None, dense_grad=None,
                step_dev=None):
-        f32 = torch.float32
-        _lib.call("rc_rows_plan_update", _ptr(W, f32, "W", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True), self.d, self.n_rows,
-                  self.n_occ, _ptr(coef, f32, "coef", True), _ptr(src, f32, "src"), _ptr(src_index, torch.int64, "src_index", True),
-                  int(div), _ptr(src2, f32, "src2", True), self.n_a, C.byref(hyper) if hyper is not None else None,
-                  _ptr(step_dev, torch.int64, "step_dev", True), _ptr(dense_grad, f32, "dense_grad", True),
-                  C.c_void_p(self.ws.data_ptr()), self.ws.numel(), _stream())
+        # (occurrences from n_a on -- the second id tensor's -- take src2; the plan's own workspace, not a cached one)
+        _lib.call("rc_rows_plan_update", *_table_args(W, m, v), self.d, self.n_rows, self.n_occ,
+                  *_source_args(coef, src, src_index, div, src2, self.n_a), _hyper_ref(hyper),
+                  _ptr(step_dev, torch.int64, "step_dev", True), _ptr(dense_grad, torch.float32, "dense_grad", True), *_ws_args(self.ws))
 
     def views(self):
         """(keys, perm, start, end, status) as int32 tensors copied out of the workspace (tests)"""
@@ -1689,6 +1733,14 @@ class RowsPlan:
         words = self.ws.view(torch.int32)
         sizes = [self.n_occ + 1, self.n_occ + 1, self.n_rows, self.n_rows, 1]
         return tuple(words[(p.value - base) // 4:(p.value - base) // 4 + n].clone() for p, n in zip(ptrs, sizes))
+
+
+class _SortedRows(collections.namedtuple("_SortedRows", "keys perm n_split")):
+    """RowsPlan.update's call shape on the sorted route: (keys, perm) of sort_ids over candidate + history ids, and n_split, the
+    occurrence the history rows (src2) begin at"""
+
+    def update(self, src, src2=None, **kw):
+        segmented_update2(self.keys, self.perm, src, src2, self.n_split, **kw)
 
 
 class SasrecTrainer:
@@ -1723,16 +1775,13 @@ class SasrecTrainer:
                                  "step count as a kernel argument)")
             self._step_dev = torch.zeros(1, dtype=torch.int64, device=P["item_emb"].device)
         self._graphs, self._graph_seen = {}, {}
+        self.timing = None      # {} switches the per-phase events on (_PhaseTimer, phases_ms); a timed step is not replayed
+        self._rows_by = {}      # (B, device) -> arange(B): the "user" row of every candidate tuple in _score_loss
 
     def _st(self, t):
         st = self.state.get(t.data_ptr())
         if st is None:
-            st = {}
-            if self.opt in ("Adam", "Adagrad"):
-                st["m"] = torch.zeros_like(t)
-            if self.opt == "Adam":
-                st["v"] = torch.zeros_like(t)
-            self.state[t.data_ptr()] = st
+            st = self.state[t.data_ptr()] = new_opt_state(t, self.opt)
         return st
 
     def _side_stream(self, dev):
@@ -1750,7 +1799,7 @@ class SasrecTrainer:
         return seg_rows_route(iid.numel() + hist.numel(), I.shape[0], I.shape[1])
 
     def step(self, hist, lengths, iid):
-        if not (self.graph and hist.is_cuda) or getattr(self, "timing", None) is not None \
+        if not (self.graph and hist.is_cuda) or self.timing is not None \
                 or (self._step_dev is not None and not self._dev_step_route(hist, iid)):
             return self._step(hist, lengths, iid)
         from . import graph as hgraph
@@ -1806,34 +1855,32 @@ class SasrecTrainer:
         hid.scatter_(0, first_pad, hist.reshape(-1).gather(0, first_pad))   # (tensor-indexed assignment would read the index back: a host sync)
         return sort_ids(torch.cat([iid.reshape(-1), hid]), n_items + 1)
 
-    def _item_table_update(self, sorted_ids, rows_plan, hv, gpred, g_hist, h, step_dev, B, Cn):
-        """candidate occurrences (g * hv, rebuilt on the fly) + history occurrences (g_hist rows) of the item table, grouped by
-        `sorted_ids` (a RowsPlan, or (keys, perm) of the sort): row-wise optimizer step, or dense gradient + dense step"""
+    def _group_ids(self, hist, lengths, iid, rows_plan):
+        """the batch's candidate + history occurrences grouped by item row -> an object whose update(src, ...) runs the item
+        table's step on that grouping: a RowsPlan (counting sort of the id tensors) or the sorted ids behind its call shape"""
         I = self.P["item_emb"]
-        d = I.shape[1]
-        st = self._st(I)
         if rows_plan:
-            src = dict(coef=gpred.reshape(-1), div=Cn, src2=g_hist.view(-1, d))
-            if self.rowwise:
-                sorted_ids.update(hv, hyper=h, W=I, m=st.get("m"), v=st.get("v"), step_dev=step_dev, **src)
-            else:
-                G = torch.zeros_like(I)
-                sorted_ids.update(hv, dense_grad=G, **src)
-                dense_update(I, G, h, st.get("m"), st.get("v"))
-        elif self.rowwise:
-            keys, perm = sorted_ids
-            segmented_update2(keys, perm, hv, g_hist.view(-1, d), B * Cn, hyper=h, W=I, m=st.get("m"), v=st.get("v"),
-                              coef=gpred.reshape(-1), div=Cn, step_dev=step_dev)
+            return RowsPlan(iid, hist, lengths, I.shape[0], I.shape[1], tag="sasrec_rows")
+        return _SortedRows(*self._sorted_occurrences(hist, lengths, iid), n_split=iid.numel())
+
+    def _item_table_update(self, group, hv, gpred, g_hist, h, step_dev, Cn):
+        """candidate occurrences (g * hv, rebuilt on the fly) + history occurrences (g_hist rows) of the item table, grouped by
+        `group` (_group_ids): row-wise optimizer step, or dense gradient + dense step"""
+        I = self.P["item_emb"]
+        st = self._st(I)
+        src = dict(coef=gpred.reshape(-1), div=Cn, src2=g_hist.view(-1, I.shape[1]))
+        if self.rowwise:
+            group.update(hv, hyper=h, W=I, m=st.get("m"), v=st.get("v"), step_dev=step_dev, **src)
         else:
-            keys, perm = sorted_ids
             G = torch.zeros_like(I)
-            segmented_update2(keys, perm, hv, g_hist.view(-1, d), B * Cn, coef=gpred.reshape(-1), div=Cn, dense_grad=G)
+            group.update(hv, dense_grad=G, **src)
             dense_update(I, G, h, st.get("m"), st.get("v"))
 
-    def _dense_step(self, Gp, dgrads, h, h0, step_dev):
-        """position table + every block parameter: one launch"""
+    def _dense_step(self, g_hist, lengths, dgrads, h, h0, step_dev):
+        """the position table's gradient, then position table + every block parameter in one launch"""
         P = self.P
         Pe, layers = P["pos_emb"], P["layers"]
+        Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])
         st = self._st(Pe)
         items = [(Pe, Gp, h, st.get("m"), st.get("v"))]
         for lay, g in zip(layers, dgrads):
@@ -1842,18 +1889,57 @@ class SasrecTrainer:
                 items.append((lay[name], g[name].contiguous(), h0 if name in SAS_NO_DECAY else h, st.get("m"), st.get("v")))
         dense_update_multi(items, self.opt, step_dev=step_dev, increment=False)
 
-    def _score_loss(self, hv, iid, B):
+    def _encode(self, hist, lengths):
+        P = self.P
+        return sasrec_fwd(P["item_emb"], P["pos_emb"], P["layers"], self.n_heads, hist, lengths, save=True, drop_p=self.dropout, seed=self.seed)
+
+    def _score_loss(self, hv, iid):
         # scores, BPR loss, d loss / d pred and d loss / d hv in ONE pass over the candidate rows: the fused BPRMF kernel
         # with the encoder output as the "user" row (SASRec.py:80-81, BaseModel.py:182-185); three launches and two
         # more passes over the [B, C] rows before
         # (one tensor per batch size, kept for the trainer's life: a captured step holds its ADDRESS -- replacing it when another
         #  batch size comes by, e.g. the short last batch of an epoch, would leave the graph of the first size reading freed memory)
-        rows_by = self.__dict__.setdefault("_rows_by", {})
-        key_rows = (B, str(hv.device))
-        if key_rows not in rows_by:
-            rows_by[key_rows] = torch.arange(B, device=hv.device)
-        _, loss_vec, gpred, dhv = bprmf_fwd_bwd(hv, self.P["item_emb"], rows_by[key_rows], iid, want_pred=False)
+        key_rows = (hv.shape[0], str(hv.device))
+        if key_rows not in self._rows_by:
+            self._rows_by[key_rows] = torch.arange(hv.shape[0], device=hv.device)
+        _, loss_vec, gpred, dhv = bprmf_fwd_bwd(hv, self.P["item_emb"], self._rows_by[key_rows], iid, want_pred=False)
         return loss_vec, gpred, dhv
+
+    def _step(self, hist, lengths, iid):
+        I = self.P["item_emb"]
+        self.step_count += 1
+        h, h0 = _step_hypers(self)
+        if self.seed is not None:
+            step_increment(self.seed)
+        if self._step_dev is not None:
+            step_increment(self._step_dev)
+        n_occ = iid.numel() + hist.numel()
+        # Adam under replay: the kernels read the step count from device memory where the route carries it (else this step takes
+        # the host's count -- both advance every step -- and is not captured)
+        step_dev = self._step_dev if self._dev_step_route(hist, iid) else None
+        # one wave per table row with the rows' bounds from a counting sort of the id tensors themselves (no radix sort, no glue)
+        rows_plan = (_SAS_ROWS_PLAN and hist.is_cuda and seg_rows_route(n_occ, I.shape[0], I.shape[1])
+                     and rows_plan_supported(I.shape[0], n_occ, I.shape[1]))
+        # (small batches are bound by the host's launch rate: the extra stream switches cost more than the overlap returns --
+        #  B = 256: 0.39 against 0.30 ms; B = 4096: 0.66 against 0.72 ms)
+        if hist.is_cuda and n_occ >= _SAS_OVERLAP_MIN:
+            return self._step_item_stream(hist, lengths, iid, h, h0, step_dev, rows_plan)
+        return self._step_one_stream(hist, lengths, iid, h, h0, step_dev, rows_plan)
+
+    def _step_one_stream(self, hist, lengths, iid, h, h0, step_dev, rows_plan):
+        B, Cn = iid.shape
+        with _PhaseTimer(self, "encoder_fwd"):
+            hv, xsave = self._encode(hist, lengths)
+        with _PhaseTimer(self, "score_loss"):
+            loss_vec, gpred, dhv = self._score_loss(hv, iid)
+            self.loss = reduce_sum(loss_vec, 1.0 / B)
+        with _PhaseTimer(self, "encoder_bwd"):
+            g_hist, dgrads = sasrec_bwd(self.P["layers"], self.n_heads, lengths, xsave, dhv, drop_p=self.dropout, seed=self.seed)
+        with _PhaseTimer(self, "table_update"):
+            self._item_table_update(self._group_ids(hist, lengths, iid, rows_plan), hv, gpred, g_hist, h, step_dev, Cn)
+        with _PhaseTimer(self, "dense_update"):   # position table (tiny) and the block parameters: dense gradient, dense step
+            self._dense_step(g_hist, lengths, dgrads, h, h0, step_dev)
+        return self.loss
 
     def _step_item_stream(self, hist, lengths, iid, h, h0, step_dev, rows_plan):
         """The step on two streams, one of which owns everything about the ITEM TABLE: the grouping of the batch's ids beside the
@@ -1865,75 +1951,32 @@ class SasrecTrainer:
         barrier), the item-table work the side stream.  The other way round -- the table update's kernels last on the launch stream,
         where the graph ends without waiting for another queue -- measured 0.225 against 0.219 ms per replayed step at config 3
         (profiles/r09_sasrec_two_stream_schedules.txt)."""
-        P = self.P
-        I, Pe, layers = P["item_emb"], P["pos_emb"], P["layers"]
-        B, L = hist.shape
-        Cn = iid.shape[1]
-        d = I.shape[1]
+        B, Cn = iid.shape
         enc = torch.cuda.current_stream(hist.device)
         tab = self._side_stream(hist.device)
         # the batch is ready; last step's users of the side stream's buffers are done (the step ends with a join)
         tab.wait_event(enc.record_event())
         with _PhaseTimer(self, "encoder_fwd"):
-            hv, xsave = sasrec_fwd(I, Pe, layers, self.n_heads, hist, lengths, save=True, drop_p=self.dropout, seed=self.seed)
+            hv, xsave = self._encode(hist, lengths)
         with torch.cuda.stream(tab):
-            sorted_ids = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows") if rows_plan else self._sorted_occurrences(hist, lengths, iid)
+            group = self._group_ids(hist, lengths, iid, rows_plan)
         with _PhaseTimer(self, "score_loss"):
-            loss_vec, gpred, dhv = self._score_loss(hv, iid, B)
+            loss_vec, gpred, dhv = self._score_loss(hv, iid)
         with _PhaseTimer(self, "encoder_bwd"):
-            g_hist, dgrads, finish_bwd = sasrec_bwd(layers, self.n_heads, lengths, xsave, dhv, drop_p=self.dropout, seed=self.seed, split=True)
+            g_hist, dgrads, finish_bwd = sasrec_bwd(self.P["layers"], self.n_heads, lengths, xsave, dhv, drop_p=self.dropout,
+                                                    seed=self.seed, split=True)
         ready = enc.record_event()     # g_hist, gpred, hv: what the table update reads
         with _PhaseTimer(self, "dense_update"):
             finish_bwd()               # the encoder's parameter gradients ...
-            Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])     # ... the position table's, and the dense step of both
-            self._dense_step(Gp, dgrads, h, h0, step_dev)
+            self._dense_step(g_hist, lengths, dgrads, h, h0, step_dev)     # ... the position table's, and the dense step of both
         # the batch mean of the losses last on this stream: it ends ~20 us before the item-table stream does, and 5 us in front of
         # the table update were 5 us of the step
         self.loss = reduce_sum(loss_vec, 1.0 / B)
         with torch.cuda.stream(tab):
             tab.wait_event(ready)
             with _PhaseTimer(self, "table_update"):
-                self._item_table_update(sorted_ids, rows_plan, hv, gpred, g_hist, h, step_dev, B, Cn)
+                self._item_table_update(group, hv, gpred, g_hist, h, step_dev, Cn)
         enc.wait_stream(tab)             # the step's one join
-        return self.loss
-
-    def _step(self, hist, lengths, iid):
-        P = self.P
-        I, Pe, layers = P["item_emb"], P["pos_emb"], P["layers"]
-        B, L = hist.shape
-        Cn = iid.shape[1]
-        d = I.shape[1]
-        self.step_count += 1
-        h = make_hyper(self.opt, lr=self.lr, l2=self.l2, step=self.step_count)
-        h0 = make_hyper(self.opt, lr=self.lr, l2=0.0, step=self.step_count)
-        if self.seed is not None:
-            step_increment(self.seed)
-        if self._step_dev is not None:
-            step_increment(self._step_dev)
-        n_occ = B * Cn + hist.numel()
-        # Adam under replay: the kernels read the step count from device memory where the route carries it (else this step takes
-        # the host's count -- both advance every step -- and is not captured)
-        step_dev = self._step_dev if self._dev_step_route(hist, iid) else None
-        # one wave per table row with the rows' bounds from a counting sort of the id tensors themselves (no radix sort, no glue)
-        rows_plan = (_SAS_ROWS_PLAN and hist.is_cuda and seg_rows_route(n_occ, I.shape[0], d)
-                     and rows_plan_supported(I.shape[0], n_occ, d))
-        # (small batches are bound by the host's launch rate: the extra stream switches cost more than the overlap returns --
-        #  B = 256: 0.39 against 0.30 ms; B = 4096: 0.66 against 0.72 ms)
-        if hist.is_cuda and n_occ >= _SAS_OVERLAP_MIN:
-            return self._step_item_stream(hist, lengths, iid, h, h0, step_dev, rows_plan)
-        with _PhaseTimer(self, "encoder_fwd"):
-            hv, xsave = sasrec_fwd(I, Pe, layers, self.n_heads, hist, lengths, save=True, drop_p=self.dropout, seed=self.seed)
-        with _PhaseTimer(self, "score_loss"):
-            loss_vec, gpred, dhv = self._score_loss(hv, iid, B)
-            self.loss = reduce_sum(loss_vec, 1.0 / B)
-        with _PhaseTimer(self, "encoder_bwd"):
-            g_hist, dgrads = sasrec_bwd(layers, self.n_heads, lengths, xsave, dhv, drop_p=self.dropout, seed=self.seed)
-        with _PhaseTimer(self, "table_update"):
-            sorted_ids = RowsPlan(iid, hist, lengths, I.shape[0], d, tag="sasrec_rows") if rows_plan else self._sorted_occurrences(hist, lengths, iid)
-            self._item_table_update(sorted_ids, rows_plan, hv, gpred, g_hist, h, step_dev, B, Cn)
-        with _PhaseTimer(self, "dense_update"):   # position table (tiny) and the block parameters: dense gradient, dense step
-            Gp = sasrec_pos_grad(g_hist, lengths, Pe.shape[0])
-            self._dense_step(Gp, dgrads, h, h0, step_dev)
         return self.loss
 
 
@@ -2124,7 +2167,7 @@ def numeric_field_grads(gV, gL, values, fields, n_fields, n_cand, d):
     nbytes = _lib.load().rc_numeric_field_grads_workspace_bytes(B * n_cand, J, d)
     ws = workspace(nbytes, dev, "numeric_fields")
     _lib.call("rc_numeric_field_grads", _ptr(gV, f32, "gV", True), _ptr(gL, f32, "gL", True), *arrays, J,
-              int(n_fields), B, int(n_cand), int(d), dW_arr, dw1_arr, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              int(n_fields), B, int(n_cand), int(d), dW_arr, dw1_arr, *_ws_args(ws))
     return (None if dW is None else [dW[j] for j in range(J)]), (None if dw1 is None else [dw1[j] for j in range(J)])
 
 
@@ -2316,7 +2359,7 @@ def route_by_owner(ids, world, tuple_base=None, div=1):
     _lib.call("rc_route_by_owner", _ptr(ids, i64, "ids"), n, int(world), int(tuple_base or 0), int(div),
               _ptr(order, torch.int32, "order"), _ptr(payload if packed else None, i64, "packed", True),
               _ptr(None if packed else payload, i64, "local_row", True), _ptr(counts, i64, "counts"),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              *_ws_args(ws))
     return order, counts, payload
 
 
@@ -2341,13 +2384,11 @@ def owner_backward(I, mI, vI, Uall, t32, rows, g, single, n_tuples, hyper):
     d = I.shape[1]
     f32 = torch.float32
     pug = torch.empty((n_tuples, d), dtype=f32, device=I.device)
-    lib = _lib.load()
-    ws = workspace(lib.rc_owner_backward_workspace_bytes(n), I.device, "owner")
-    _lib.call("rc_owner_backward", _ptr(I, f32, "I"), _ptr(mI, f32, "mI", True), _ptr(vI, f32, "vI", True), d,
+    ws = workspace(_lib.load().rc_owner_backward_workspace_bytes(n), I.device, "owner")
+    _lib.call("rc_owner_backward", *_table_args(I, mI, vI, need_W=True), d,
               _ptr(Uall, f32, "Uall"), _ptr(t32, torch.int32, "t32"), _ptr(rows, torch.int64, "rows"),
               _ptr(g, f32, "g"), _ptr(single, torch.uint8, "single", True), n, int(n_tuples),
-              C.byref(hyper) if hyper is not None else None, _ptr(pug, f32, "pug"),
-              C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+              _hyper_ref(hyper), _ptr(pug, f32, "pug"), *_ws_args(ws))
     return pug
 
 

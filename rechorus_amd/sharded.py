@@ -49,6 +49,8 @@ class _SortPlan:
             self.single, _, _ = e.segment_heads(self.keys, self.perm, want_single=True, want_heads=False)
 
     def _src(self, coef, src, src_index, div, src2):
+        """engine.Plan's sources in segmented_update's terms: a lone src2 (every occurrence takes its plain row) IS the source there,
+        and segmented_update's own default keeps n_split behind the last occurrence"""
         if src2 is not None:
             return dict(src=src2)
         return dict(src=src, coef=coef, src_index=src_index, div=div)
@@ -199,7 +201,7 @@ class HipOps:
         (rc_neumf_head_fwd_bwd) -> (loss_vec, gu [B, 2d], gi [B C, 2d], dense grads), or None where the fused kernel has no
         instance (the caller then runs neumf_fwd / bpr_loss / neumf_bwd)"""
         d, l1 = urows.shape[1] // 2, P["W1"].shape[0]
-        if not self.e._NEUMF_FUSED or C < 2 or not self.e.neumf_train_step_supported(C, d, l1):
+        if not self.e.neumf_head_kernel_selected(C, d, l1):
             return None
         loss_vec, gu, gi, dense, _ = self.e.neumf_head_fwd_bwd(urows, irows, P["W1"], P["b1"], P["w_out"], B, C, inv_b)
         return loss_vec, gu, gi, dense
@@ -243,12 +245,7 @@ class HipOps:
         return self.e.make_hyper(**kw)
 
     def new_state(self, W, opt):
-        st = {}
-        if opt in ("Adam", "Adagrad"):
-            st["m"] = torch.zeros_like(W)
-        if opt == "Adam":
-            st["v"] = torch.zeros_like(W)
-        return st
+        return self.e.new_opt_state(W, opt)
 
 
 def _is_nccl(group):

@@ -68,7 +68,7 @@ def test_neumf_fused_step_at_the_bench_shape_whole_batch_vs_oracle(n_items, n_us
     tr = eng.NeumfTrainer(P, opt="SGD", lr=LR, l2=0.0, rowwise=True)
     tr.timing = None
     tr.step(*b1, next_batch=b2)
-    ahead = getattr(tr, "_ahead", None)
+    ahead = tr._ahead
     assert ahead is not None and ahead["key"] == tr._batch_key(*b2), "step 2 would not run from the prepared flags / plan"
     uid, iid = b2
     ui, inv_i = torch.unique(iid, return_inverse=True)
@@ -84,7 +84,7 @@ def test_neumf_fused_step_at_the_bench_shape_whole_batch_vs_oracle(n_items, n_us
     before = {k: P[k][probe_u if k.endswith("_u") else probe].clone() for k in ("mf_u", "mlp_u", "mf_i", "mlp_i")}
     loss = tr.step(*b2)
     torch.cuda.synchronize()
-    assert getattr(tr, "_ahead", None) is None
+    assert tr._ahead is None
     for m in tr._marks:
         assert not m[(4 * n_items + 255) // 256 * 256:].any(), "multi-occurrence flags left behind"
     for k, t in before.items():

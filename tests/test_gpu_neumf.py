@@ -524,7 +524,7 @@ def test_neumf_trainer_short_step_consumes_prepared_flags_and_clears_them(cuda, 
             tr.step(u, i, next_batch=batches[k + 1] if announce and k + 1 < len(batches) else None)
             torch.cuda.synchronize()
             if announce and k == 1:
-                assert getattr(tr, "_ahead", None) is None, "a one-stream step prepares nothing"
+                assert tr._ahead is None, "a one-stream step prepares nothing"
                 for m in tr._marks:
                     assert not m[(4 * n_items + 255) // 256 * 256:].any(), "the short step left prepared flags behind"
         res.append({k: v.clone() for k, v in P.items()})
