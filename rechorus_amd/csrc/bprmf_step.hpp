@@ -36,10 +36,11 @@ int small_step_launch(const BprmfStep& st, void* extra, hipEvent_t* ev_mid);
 // first launch of the small-batch step (bprmf_fused.hip); the caller checked rc_bprmf_fused_supported(d, C)
 int small_front_launch(const BprmfStep& st, float* ub, const SmallPlanArgs& plan);
 
-// ---- bucket plan (plan_update.hip): the three update launches behind the fused kernel ---------------
-// ev_items_done: null, or an event recorded between the item-row launch(es) and the last launch
+// ---- bucket plan (plan_update.hip): the two update launches behind the fused kernel -----------------
+// lw, med: the hot and the medium rows as the plan registered them (emit_long)
+// ev_items_done: null, or an event recorded between the item-row launch and the last launch
 int plan_bprmf_step_updates(const BprmfStep& st, const rc_plan_row* rows_i, const uint32_t* n_rows_i, const rc_plan_row* rows_u,
                             const uint32_t* n_rows_u, const uint32_t* occ, uint32_t* counters, const PlanLongWs& lw,
-                            bool long_planned, hipEvent_t* ev_items_done);
+                            const PlanMedList& med, hipEvent_t* ev_items_done);
 
 }  // namespace rc

@@ -491,6 +491,19 @@ __device__ __forceinline__ void plan_register_long(const PlanArgs& a, const rc_p
     }
 }
 
+// Medium rows (plan.hpp, PlanMedList).  A bucket reserves the slots of all its medium rows with ONE atomic beside the one that
+// reserves its row records.  (A returning atomic per medium row on one address -- 7.8 K of them at config 2 -- serialised the
+// buckets: the bucket kernel ran 187 us instead of 105, profiles/r10_medium_rows_first_cut.txt.)
+
+// -> the occurrence count above which a row of `side` is medium; without a list nothing qualifies  (block-uniform)
+__device__ __forceinline__ uint32_t plan_med_over(const PlanArgs& a, uint32_t side) {
+  return (a.emit_long && a.med.end[side] != nullptr) ? a.med.over[side] : 0xFFFFFFFFu;
+}
+__device__ __forceinline__ bool plan_is_med(uint32_t c, uint32_t over) { return c > over && c <= (uint32_t)kPlanLongSeg; }
+__device__ __forceinline__ void plan_put_med(const PlanArgs& a, uint32_t side, uint32_t slot, const rc_plan_row& e) {
+  if (slot < a.med.cap[side]) a.med.end[side][-1 - (ptrdiff_t)slot] = e;
+}
+
 // occurrences per id of one bucket into the LDS cells (all threads of the workgroup, order-free LDS atomics);
 // reads the 2-byte id stream only
 template <bool WIDE>
@@ -512,7 +525,7 @@ __device__ __forceinline__ void bucket_count_pass(const BucketCells<WIDE>& cells
 
 template <bool WIDE>
 __global__ __launch_bounds__(kBucketThreads) void plan_bucket_kernel(PlanArgs a) {
-  extern __shared__ uint32_t tab[];  // table words + 256 pad words, then 16 words of scan scratch
+  extern __shared__ uint32_t tab[];  // table words + 256 pad words, then 16 words of scan scratch (per wave: occurrences 0-3, rows 4-7, medium rows 9-12; bases 8, 13)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -555,32 +568,44 @@ __global__ __launch_bounds__(kBucketThreads) void plan_bucket_kernel(PlanArgs a)
   }
 
   // scan: counts -> cursors (listed rows) / marker (rows that are only flagged); row records
-  uint32_t my_occ = 0, my_rows = 0;
+  const uint32_t med_over = plan_med_over(a, side_b ? 1u : 0u);
+  uint32_t my_occ = 0, my_rows = 0, my_med = 0;
   for (uint32_t j = 0; j < per; ++j) {
     const uint32_t c = cells.get(tid * per + j);
     if (c != 0 && (list_all || c >= 2)) {
       my_occ += c;
       ++my_rows;
+      if (plan_is_med(c, med_over)) ++my_med;
     }
   }
   const uint32_t occ_incl = wave_inclusive_scan(my_occ, lane);
   const uint32_t rows_incl = wave_inclusive_scan(my_rows, lane);
+  const uint32_t med_incl = wave_inclusive_scan(my_med, lane);
   if (lane == 63) {
     scratch[wave] = occ_incl;
     scratch[4 + wave] = rows_incl;
+    scratch[9 + wave] = med_incl;
   }
   __syncthreads();
-  uint32_t occ_off = occ_incl - my_occ, row_at = rows_incl - my_rows, total_rows = 0;
+  uint32_t occ_off = occ_incl - my_occ, row_at = rows_incl - my_rows, med_at = med_incl - my_med, total_rows = 0, total_med = 0;
   for (int w = 0; w < kBucketThreads / 64; ++w) {
     if (w < wave) {
       occ_off += scratch[w];
       row_at += scratch[4 + w];
+      med_at += scratch[9 + w];
     }
     total_rows += scratch[4 + w];
+    total_med += scratch[9 + w];
   }
-  if (tid == 0) scratch[8] = total_rows ? atomicAdd(side_b ? a.n_rows_b : a.n_rows_a, total_rows) : 0u;
+  if (tid == 0) {
+    const uint32_t r0 = total_rows ? atomicAdd(side_b ? a.n_rows_b : a.n_rows_a, total_rows) : 0u;
+    const uint32_t m0 = total_med ? atomicAdd(&a.w.counters[PC_MED + (side_b ? 1 : 0)], total_med) : 0u;
+    scratch[8] = r0;
+    scratch[13] = m0;
+  }
   __syncthreads();
   row_at += scratch[8];
+  med_at += scratch[13];
   rc_plan_row* rows = side_b ? a.rows_b : a.rows_a;
   const uint32_t row0 = (bkt - (side_b ? a.g.nb_a : 0u)) << shift;  // table-local id of the bucket's first row
   for (uint32_t j = 0; j < per; ++j) {
@@ -595,6 +620,7 @@ __global__ __launch_bounds__(kBucketThreads) void plan_bucket_kernel(PlanArgs a)
       e.reserved = 0;
       rows[row_at++] = e;
       if (a.emit_long && c > (uint32_t)kPlanLongSeg) plan_register_long(a, e, side_b ? 1u : 0u);
+      else if (plan_is_med(c, med_over)) plan_put_med(a, side_b ? 1u : 0u, med_at++, e);
       cells.set(lid, occ_off);
       occ_off += c;
     } else {
@@ -760,32 +786,44 @@ __global__ __launch_bounds__(kBucketThreads) void plan_bucket_hash_kernel(PlanAr
 
   // scan over the slots: counts -> cursors (listed rows) / marker (rows that are only flagged); row records
   const uint32_t per = S / kBucketThreads;
-  uint32_t my_occ = 0, my_rows = 0;
+  const uint32_t med_over = plan_med_over(a, side_b ? 1u : 0u);
+  uint32_t my_occ = 0, my_rows = 0, my_med = 0;
   for (uint32_t j = 0; j < per; ++j) {
     const uint32_t c = cells[tid * per + j];
     if (c != 0 && (list_all || c >= 2)) {
       my_occ += c;
       ++my_rows;
+      if (plan_is_med(c, med_over)) ++my_med;
     }
   }
   const uint32_t occ_incl = wave_inclusive_scan(my_occ, lane);
   const uint32_t rows_incl = wave_inclusive_scan(my_rows, lane);
+  const uint32_t med_incl = wave_inclusive_scan(my_med, lane);
   if (lane == 63) {
     scratch[wave] = occ_incl;
     scratch[4 + wave] = rows_incl;
+    scratch[9 + wave] = med_incl;
   }
   __syncthreads();
-  uint32_t occ_off = occ_incl - my_occ, row_at = rows_incl - my_rows, total_rows = 0;
+  uint32_t occ_off = occ_incl - my_occ, row_at = rows_incl - my_rows, med_at = med_incl - my_med, total_rows = 0, total_med = 0;
   for (int w = 0; w < kBucketThreads / 64; ++w) {
     if (w < wave) {
       occ_off += scratch[w];
       row_at += scratch[4 + w];
+      med_at += scratch[9 + w];
     }
     total_rows += scratch[4 + w];
+    total_med += scratch[9 + w];
   }
-  if (tid == 0) scratch[8] = total_rows ? atomicAdd(side_b ? a.n_rows_b : a.n_rows_a, total_rows) : 0u;
+  if (tid == 0) {
+    const uint32_t r0 = total_rows ? atomicAdd(side_b ? a.n_rows_b : a.n_rows_a, total_rows) : 0u;
+    const uint32_t m0 = total_med ? atomicAdd(&a.w.counters[PC_MED + (side_b ? 1 : 0)], total_med) : 0u;
+    scratch[8] = r0;
+    scratch[13] = m0;
+  }
   __syncthreads();
   row_at += scratch[8];
+  med_at += scratch[13];
   rc_plan_row* rows = side_b ? a.rows_b : a.rows_a;
   for (uint32_t j = 0; j < per; ++j) {
     const uint32_t sl = tid * per + j;
@@ -799,6 +837,7 @@ __global__ __launch_bounds__(kBucketThreads) void plan_bucket_hash_kernel(PlanAr
       e.reserved = 0;
       rows[row_at++] = e;
       if (a.emit_long && c > (uint32_t)kPlanLongSeg) plan_register_long(a, e, side_b ? 1u : 0u);
+      else if (plan_is_med(c, med_over)) plan_put_med(a, side_b ? 1u : 0u, med_at++, e);
       cells[sl] = occ_off;
       occ_off += c;
     } else {
@@ -908,9 +947,13 @@ __global__ __launch_bounds__(kBucketThreads) void plan_bucket_narrow_kernel(Plan
   const uint32_t occ_incl = wave_inclusive_scan(listed ? c : 0u, lane);
   const uint64_t lm = __ballot(listed);
   const uint32_t n_listed = (uint32_t)__popcll(lm);
-  uint32_t row_base = 0;
+  const bool med = listed && plan_is_med(c, plan_med_over(a, side_b ? 1u : 0u));
+  const uint64_t mm = __ballot(med);
+  uint32_t row_base = 0, med_base = 0;
   if (lane == 0 && n_listed) row_base = atomicAdd(side_b ? a.n_rows_b : a.n_rows_a, n_listed);
+  if (lane == 0 && mm) med_base = atomicAdd(&a.w.counters[PC_MED + (side_b ? 1 : 0)], (uint32_t)__popcll(mm));
   row_base = __shfl(row_base, 0, 64);
+  med_base = __shfl(med_base, 0, 64);
   const uint32_t row0 = (bkt - (side_b ? a.g.nb_a : 0u)) << shift;  // table-local id of the bucket's first row
   if ((uint32_t)lane < ids) {
     if (listed) {
@@ -921,6 +964,7 @@ __global__ __launch_bounds__(kBucketThreads) void plan_bucket_narrow_kernel(Plan
       e.reserved = 0;
       (side_b ? a.rows_b : a.rows_a)[row_base + (uint32_t)__popcll(lm & lanes_below(lane))] = e;
       if (a.emit_long && c > (uint32_t)kPlanLongSeg) plan_register_long(a, e, side_b ? 1u : 0u);
+      else if (med) plan_put_med(a, side_b ? 1u : 0u, med_base + (uint32_t)__popcll(mm & lanes_below(lane)), e);
       tab[lane] = occ_incl - c;
     } else {
       tab[lane] = kSingle;

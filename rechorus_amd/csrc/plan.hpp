@@ -15,6 +15,8 @@ constexpr int kPlanMaxShift = 13;      // ids per bucket <= 8192 (one 32 KiB LDS
 constexpr int kPlanMinShift = 8;
 constexpr int kPlanLongSeg = 32;       // occurrences one lane-group sums sequentially
 constexpr int kPlanChunk = 256;        // occurrences per workgroup for hot rows
+constexpr int kPlanIdxOcc = 4;         // occurrences per row that plan_rows_indexed_body resolves in its index phase
+constexpr int kPlanBodyOcc = 2;        // occurrences per row that plan_rows_body requests up front
 
 struct PlanGeom {
   int ok;
@@ -44,7 +46,7 @@ constexpr int kPlanHashKeysPerBucket = 1024; // sizing target: distinct rows per
 PlanGeom plan_geometry(int64_t n_a, int64_t n_b, int64_t range_a, int64_t range_b, int want = -1);
 
 // counters (device uint32[PC_N]); zeroed by the first kernel of every plan
-enum { PC_ROWS_A = 0, PC_ROWS_B = 1, PC_LONG = 2, PC_CHUNKS = 3, PC_STATUS = 4, PC_N = 8 };
+enum { PC_ROWS_A = 0, PC_ROWS_B = 1, PC_LONG = 2, PC_CHUNKS = 3, PC_STATUS = 4, PC_MED = 5 /* + side: 5, 6 */, PC_N = 8 };
 
 struct PlanWs {            // carved from the caller's workspace
   uint32_t* hist;          // [nb][tiles] per-tile bucket counts -> exclusive prefixes
@@ -70,6 +72,18 @@ struct PlanLongWs {
 };
 PlanLongWs carve_plan_long_ws(void* base, int64_t n, int d);
 
+// medium rows: more occurrences than the row kernel of their side resolves up front (over[side]), at most kPlanLongSeg.  The
+// bucket kernel lists them a second time (counter PC_MED + side; the order of the list influences no floating-point result),
+// lane-groups of their own update them at the head of the update launches (plan_update.hip, plan_medium_body).
+// The list needs no memory of its own: it grows DOWNWARD from the end of the side's row-record array.  An array that holds one
+// record per position of the side cannot run out: with M medium rows of at least 3 occurrences each (over[] >= kPlanBodyOcc) at
+// most n - 3 M + M rows are listed from the front, so records + medium entries <= n - M.
+struct PlanMedList {
+  rc_plan_row* end[2];   // side a / b: one past the row-record array; medium entry j is end[side][-1 - j].  null: no list
+  uint32_t cap[2];       // records the array holds, row records and medium entries together
+  uint32_t over[2];      // a row is medium with more occurrences than this
+};
+
 struct PlanArgs {
   const int64_t* ids_a;
   const int64_t* ids_b;
@@ -91,6 +105,7 @@ struct PlanArgs {
   // reduce their chunks in the SAME launch as the short rows (plan_update.hip, BPRMF step); otherwise the row-update
   // kernel finds them while it walks the records
   int emit_long;
+  PlanMedList med;         // with emit_long: medium rows are listed too (med.end[side] != null)
   // the bucket kernel writes bitmap_a itself (it holds every id's count after its first pass): a plan that is prepared as a
   // whole -- the look-ahead plan of the next batch -- needs no separate bitmap launch (a second zero + count pass per bucket)
   int bitmap_in_bucket;

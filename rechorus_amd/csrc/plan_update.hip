@@ -13,6 +13,9 @@
 //                       (row record + chunk list, integer atomics only) and left to:
 //   plan_chunk_kernel   one workgroup per 256-occurrence chunk, fixed LDS tree -> partial sums
 //   plan_final_kernel   chunk partials of a row combined in chunk order, optimizer, row written
+// BPRMF step (MED instantiations): the plan lists the medium rows (plan.hpp, PlanMedList) and the hot rows itself; lane-groups
+// of their own (plan_medium_body) and the chunk / combine workgroups take the LOWEST block indices of the two launches, so
+// that their dependent-load chains start with the launch and run under the bulk of short rows.
 #include "bprmf_step.hpp"
 #include "plan.hpp"
 
@@ -47,6 +50,9 @@ struct PlanUpdArgs {
   // a 256-float row (a NeuMF table pair) has 4 lane-groups per workgroup -- 256 occurrences were 16 dependent trips (67 us for
   // the few hot rows of a NeuMF batch), 64 are four
   uint32_t chunk;
+  // MED instantiations only: the plan's medium rows and the workgroups at the head of each launch that update them
+  PlanMedList med;
+  uint32_t blocks_med;
 };
 
 template <int D>
@@ -120,7 +126,8 @@ __device__ __forceinline__ void plan_long_row(const PlanUpdArgs& a, const rc_pla
 // SIDE: which table this launch updates.  PLAN_ONLY_OTHER: additionally walk the OTHER side's rows and hand
 // its hot rows to the chunk path without updating anything (BPRMF step: user rows are updated later, but their
 // hot rows have to be planned before plan_chunk_kernel runs).
-template <int D, int MODE>
+// MED: rows with more than kPlanBodyOcc occurrences are not this body's (medium: plan_medium_body; hot: the chunk path)
+template <int D, int MODE, bool MED = false>
 __device__ __forceinline__ void plan_rows_body(const PlanUpdArgs& a, int side, bool plan_long, uint32_t first_block,
                                                uint32_t n_blocks) {
   constexpr int LPR = D / 4;
@@ -136,7 +143,7 @@ __device__ __forceinline__ void plan_rows_body(const PlanUpdArgs& a, int side, b
 #pragma unroll
     for (int h = 0; h < H; ++h) {
       e[h] = sd.rows[g0 + h < nr ? g0 + h : g0];
-      act[h] = g0 + h < nr && e[h].n <= (uint32_t)kPlanLongSeg;
+      act[h] = g0 + h < nr && e[h].n <= (uint32_t)(MED ? kPlanBodyOcc : kPlanLongSeg);
     }
     float4 w[H], acc[H], s1[H];
     PlanTable tab[H];
@@ -160,7 +167,8 @@ __device__ __forceinline__ void plan_rows_body(const PlanUpdArgs& a, int side, b
         continue;
       }
       if (e[h].n > 1) padd4(acc[h], s1[h]);
-      for (uint32_t k = 2; k < e[h].n; ++k) padd4(acc[h], plan_grad4<D>(sd.g, a.occ, e[h].start + k, l));
+      if (!MED)
+        for (uint32_t k = kPlanBodyOcc; k < e[h].n; ++k) padd4(acc[h], plan_grad4<D>(sd.g, a.occ, e[h].start + k, l));
       opt_row4<MODE>(a.o, tab[h].W, tab[h].M, tab[h].V, idx4[h], w[h], acc[h]);
     }
   }
@@ -174,13 +182,15 @@ __device__ __forceinline__ void plan_rows_body(const PlanUpdArgs& a, int side, b
 // shuffles the resolved (row, coefficients, source rows) of H rows out of the index lanes and issues the table row,
 // its optimizer state and the first two source rows of all H rows back to back (one memory latency per step).
 // Summation order per row is unchanged (ascending position: occurrence 0, 1, then the rest) => bit-identical.
-template <int D, int MODE>
+// MED: rows with more than kPlanIdxOcc occurrences are not this body's (medium: plan_medium_body; hot: the chunk path)
+template <int D, int MODE, bool MED = false>
 __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int side, bool plan_long, uint32_t first_block,
                                                        uint32_t n_blocks) {
   constexpr int LPR = D / 4;
   constexpr int GPW = 64 / LPR;   // lane-groups per wave
   constexpr int H = 2;            // rows per lane-group per step
-  constexpr uint32_t kIdxOcc = 4;   // occurrences per row resolved in the index phase
+  constexpr uint32_t kIdxOcc = kPlanIdxOcc;   // occurrences per row resolved in the index phase
+  constexpr uint32_t kMaxOcc = MED ? kPlanIdxOcc : kPlanLongSeg;   // the longest row this body updates
   const PlanSide& sd = a.side[side];
   const PlanGrad& gr = sd.g;
   const int lane = threadIdx.x & 63;
@@ -195,7 +205,7 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
     rc_plan_row e;
     e.row = 0; e.start = 0; e.n = 0; e.reserved = 0;
     if (gi < nr) e = sd.rows[gi];
-    const bool shortrow = e.n >= 1 && e.n <= (uint32_t)kPlanLongSeg;
+    const bool shortrow = e.n >= 1 && e.n <= kMaxOcc;
     // the first FOUR occurrences of the row are resolved here (64 rows' chains together); a row's fifth and later ones walk the
     // chain on their own in the data phase.  (With two, a third occurrence -- 17 % of the multi-occurrence rows of config 2, so
     // 85 % of the eight-row steps had one -- stalled its wave for three dependent loads.)
@@ -246,7 +256,7 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
         sh1[h] = shfl64(s1, sl);
         sh2[h] = shfl64(s2, sl);
         sh3[h] = shfl64(s3, sl);
-        on[h] = eh[h].n >= 1 && eh[h].n <= (uint32_t)kPlanLongSeg;
+        on[h] = eh[h].n >= 1 && eh[h].n <= kMaxOcc;
       }
       float4 w[H], m[H], v[H], u0[H], u1[H], u2[H], u3[H];
       size_t idx4[H];
@@ -288,14 +298,109 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
           padd4(acc, t);
         }
         // (the later occurrences one after the other: keeping eight of their chains in flight costs 22 registers and a wave per SIMD,
-        //  and measured 7 % SLOWER on this launch and on NeuMF's pair update -- profiles/r08_plan_rows_index_four_occurrences.txt)
-        for (uint32_t k = kIdxOcc; k < eh[h].n; ++k) padd4(acc, plan_grad4<D>(gr, a.occ, eh[h].start + k, l));
+        //  and measured 7 % SLOWER on this launch and on NeuMF's pair update -- profiles/r08_plan_rows_index_four_occurrences.txt;
+        //  where the plan lists the medium rows, MED, they are plan_medium_body's and this loop does not exist)
+        if (!MED)
+          for (uint32_t k = kIdxOcc; k < eh[h].n; ++k) padd4(acc, plan_grad4<D>(gr, a.occ, eh[h].start + k, l));
         opt_apply4<MODE>(a.o, w[h], m[h], v[h], acc);
         store_row4(reinterpret_cast<float4*>(sd.t.W) + idx4[h], w[h]);
         if (mode_has_m(MODE)) store_row4(reinterpret_cast<float4*>(sd.t.M) + idx4[h], m[h]);
         if (mode_has_v(MODE)) store_row4(reinterpret_cast<float4*>(sd.t.V) + idx4[h], v[h]);
       }
     }
+  }
+}
+
+__device__ __forceinline__ const float4* shfl_ptr4(const float4* p, int src_lane) {
+  const uint64_t x = reinterpret_cast<uint64_t>(p);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), src_lane, 64), lo = (uint32_t)__shfl((int)(uint32_t)x, src_lane, 64);
+  return reinterpret_cast<const float4*>(((uint64_t)hi << 32) | lo);
+}
+
+// Medium rows of `side` (plan.hpp, PlanMedList: more occurrences than the side's row body resolves up front, at most
+// kPlanLongSeg), one lane-group per row.  The row bodies walk such a row's later occurrences one after the other, three
+// dependent loads each (occ[] -> coefficient / source index -> source row), at the tail of a wave that has no later pass to
+// catch up in.  Here the lanes of the group fetch ALL of the row's occ[] entries at once and resolve them in parallel (source
+// row pointer + coefficient per occurrence), then the group streams the source rows kBatch at a time: ceil(n / 8) + 2 memory
+// latencies per row instead of 3 (n - 4).  Summation as in the row bodies -- coefficient times source row, added in ascending
+// position, the first one assigned -- so every row's bits are what they were (a source without coefficient is scaled by 1.0f:
+// the same bits, one expression for both sides).  No pair mode (the BPRMF step, the only producer of a medium list, has none).
+template <int D, int MODE>
+__device__ __forceinline__ void plan_medium_body(const PlanUpdArgs& a, int side, uint32_t first_block, uint32_t n_blocks) {
+  constexpr int LPR = D / 4;
+  constexpr int GPB = kBlock / LPR;
+  constexpr int PER = (kPlanLongSeg + LPR - 1) / LPR;   // occurrences per lane
+  constexpr int kBatch = 8;                             // source rows in flight
+  static_assert(LPR_OK(D), "a row's lane-group must fit a wave");
+  const PlanSide& sd = a.side[side];
+  const PlanGrad& gr = sd.g;
+  const int lane = threadIdx.x & 63;
+  const int l = lane % LPR, lane0 = lane - l;
+  const float4* src4 = reinterpret_cast<const float4*>(gr.src);
+  const float4* src2_4 = reinterpret_cast<const float4*>(gr.src2);
+  // the list grows downward from the end of the side's row-record array: never into the records themselves
+  const uint32_t n_rec = *sd.n_rows < a.med.cap[side] ? *sd.n_rows : a.med.cap[side];
+  uint32_t n_med = a.counters[PC_MED + side];
+  if (n_med > a.med.cap[side] - n_rec) n_med = a.med.cap[side] - n_rec;
+  for (uint32_t i = (blockIdx.x - first_block) * GPB + threadIdx.x / LPR; i < n_med; i += n_blocks * GPB) {
+    const rc_plan_row r = a.med.end[side][-1 - (ptrdiff_t)i];   // (uniform in the lane-group, like everything below)
+    const uint32_t n = r.n < (uint32_t)kPlanLongSeg ? r.n : (uint32_t)kPlanLongSeg;
+    const size_t idx4 = (size_t)r.row * LPR + l;
+    const float4 w = load_stream4(reinterpret_cast<const float4*>(sd.t.W) + idx4);
+    // index phase: lane l resolves occurrences l, l + LPR, ...
+    const float4* ps[PER];
+    float cf[PER];
+    uint32_t o[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const uint32_t k = (uint32_t)(l + j * LPR);
+      o[j] = k < n ? a.occ[r.start + k] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      ps[j] = nullptr;
+      cf[j] = 1.0f;
+      if ((uint32_t)(l + j * LPR) >= n) continue;
+      if (o[j] >= gr.n_split) {
+        ps[j] = src2_4 + (size_t)(o[j] - gr.n_split) * LPR;
+      } else {
+        int64_t sr = (gr.div == 1) ? (int64_t)o[j] : (int64_t)(o[j] / (uint32_t)gr.div);
+        if (gr.src_index) sr = gr.src_index[sr];
+        if (gr.coef) cf[j] = gr.coef[o[j]];
+        ps[j] = src4 + (size_t)sr * LPR;
+      }
+    }
+    // data phase: occurrence k was resolved by lane k % LPR of the group, in its slot k / LPR
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t k0 = 0; k0 < n; k0 += kBatch) {
+      float4 g[kBatch];
+      float c[kBatch];
+#pragma unroll
+      for (int q = 0; q < kBatch; ++q) {
+        const uint32_t k = k0 + q;
+        const float4* p = ps[0];
+        float cv = cf[0];
+#pragma unroll
+        for (int j = 1; j < PER; ++j)
+          if (k / LPR == (uint32_t)j) {
+            p = ps[j];
+            cv = cf[j];
+          }
+        const int sl = lane0 + (int)(k % LPR);
+        p = shfl_ptr4(p, sl);
+        c[q] = __shfl(cv, sl, 64);
+        if (k < n) g[q] = p[l];
+      }
+#pragma unroll
+      for (int q = 0; q < kBatch; ++q) {
+        if (k0 + q >= n) break;
+        float4 t = g[q];
+        t.x *= c[q]; t.y *= c[q]; t.z *= c[q]; t.w *= c[q];
+        if (k0 + q == 0) acc = t;
+        else padd4(acc, t);
+      }
+    }
+    opt_row4<MODE>(a.o, sd.t.W, sd.t.M, sd.t.V, idx4, w, acc);
   }
 }
 
@@ -323,10 +428,22 @@ __device__ __forceinline__ void plan_long_only_body(const PlanUpdArgs& a, int si
 template <int D>
 __device__ __forceinline__ void plan_chunk_body(const PlanUpdArgs& a, uint32_t first_block, uint32_t n_blocks, float4* part);
 
-template <int D, int MODE>
+// MED (the BPRMF step: medium and hot rows listed by the plan, an indexed update side): a.blocks_med workgroups of medium
+// rows, then the hot rows' chunk workgroups, then the short rows
+template <int D, int MODE, bool MED = false>
 __global__ __launch_bounds__(kBlock) void plan_rows_kernel(PlanUpdArgs a, uint32_t blocks_main, int update_side,
                                                            int plan_other, uint32_t blocks_chunk) {
   __shared__ float4 part[kBlock];   // chunk workgroups only
+  if constexpr (MED) {
+    // the only producer of a medium list, the BPRMF step, updates an indexed side (no pair mode, no second source) and plans no
+    // hot rows here: plan_other is not looked at
+    static_assert(LPR_OK(D), "MED: the update side goes through plan_rows_indexed_body");
+    const uint32_t head = a.blocks_med + blocks_chunk;
+    if (blockIdx.x < a.blocks_med) plan_medium_body<D, MODE>(a, update_side, 0, a.blocks_med);
+    else if (blockIdx.x < head) plan_chunk_body<D>(a, a.blocks_med, blocks_chunk, part);
+    else plan_rows_indexed_body<D, MODE, true>(a, update_side, false, head, blocks_main);
+    return;
+  }
   const bool plan_long = a.long_planned == 0;
   if (blockIdx.x < blocks_main) {
     if (LPR_OK(D) && plan_side_indexed(a.side[update_side])) plan_rows_indexed_body<D, MODE>(a, update_side, plan_long, 0, blocks_main);
@@ -391,22 +508,31 @@ __global__ __launch_bounds__(kBlock) void plan_chunk_kernel(PlanUpdArgs a) {
 
 // last launch: short rows of `update_side` (BPRMF step: the user table, whose pre-step rows every earlier launch
 // has finished reading), the hot rows of both sides from their chunk partials, and the loss mean
-template <int D, int MODE>
+// MED (the BPRMF step): a.blocks_med workgroups of medium rows of `update_side`, then the hot rows, then the short rows
+template <int D, int MODE, bool MED = false>
 __global__ __launch_bounds__(kBlock) void plan_final_kernel(PlanUpdArgs a, uint32_t blocks_rows, uint32_t blocks_long,
                                                            int update_side) {
   constexpr int LPR = D / 4;
   constexpr int GPB = kBlock / LPR;
   __shared__ float4 part[kBlock];
-  if (blockIdx.x < blocks_rows) {
-    if (update_side >= 0) plan_rows_body<D, MODE>(a, update_side, false, 0, blocks_rows);
+  const uint32_t long0 = MED ? a.blocks_med : blocks_rows;    // first workgroup of the hot rows ...
+  const uint32_t rows0 = MED ? long0 + blocks_long : 0u;      // ... and of the short rows
+  if constexpr (MED) {
+    if (blockIdx.x < a.blocks_med) {
+      plan_medium_body<D, MODE>(a, update_side, 0, a.blocks_med);
+      return;
+    }
+  }
+  if (blockIdx.x >= rows0 && blockIdx.x < rows0 + blocks_rows) {
+    if (update_side >= 0) plan_rows_body<D, MODE, MED>(a, update_side, false, rows0, blocks_rows);
     return;
   }
-  if (blockIdx.x < blocks_rows + blocks_long) {
+  if (blockIdx.x >= long0 && blockIdx.x < long0 + blocks_long) {
     const int l = threadIdx.x % LPR;
     const int g = threadIdx.x / LPR;
     uint32_t n_long = a.counters[PC_LONG];
     if (n_long > a.lw.long_cap) n_long = a.lw.long_cap;
-    for (uint32_t i = blockIdx.x - blocks_rows; i < n_long; i += blocks_long) {
+    for (uint32_t i = blockIdx.x - long0; i < n_long; i += blocks_long) {
       const PlanLongRow r = a.lw.lrows[i];
       float4 acc = make_float4(0, 0, 0, 0);
       for (uint32_t k = g; k < r.nchunks; k += GPB)
@@ -454,48 +580,45 @@ static int launch_side_update(const PlanUpdArgs& a_in, int64_t n_occ, hipStream_
   return RC_OK;
 }
 
+// The BPRMF step's two launches.  The plan registered the hot rows (their chunk sums ride in the first launch: they only read
+// pre-step rows and write the partial buffer, so they need no ordering against the row updates) and the medium rows; both
+// kinds of workgroups come first in their launch.
 template <int D, int MODE>
-static int launch_step_updates(const PlanUpdArgs& a, int64_t n_occ, hipStream_t s, hipEvent_t* ev_items_done) {
+static int launch_step_updates(const PlanUpdArgs& a_in, int64_t n_occ, hipStream_t s, hipEvent_t* ev_items_done) {
+  constexpr uint32_t GPB = kBlock / (D / 4);
+  PlanUpdArgs a = a_in;
   const uint32_t cus = (uint32_t)device_cus();
   // grid-stride over the rows with 4x more workgroups than fit at once: a grid of exactly "8 per CU" ran in two
   // rounds whenever the kernel's registers allowed only 7 (Adam: 72 VGPRs -> item update 2.05 instead of 1.5 ms)
   const uint32_t blocks_main = cus * 32;
-  if (a.long_planned) {
-    // hot rows came with the plan: their chunk sums ride in this launch (workgroups behind the row workgroups; they only
-    // read pre-step rows and write the partial buffer, so they need no ordering against the row updates)
-    const uint32_t blocks_chunk = n_occ > kPlanLongSeg ? 512 : 0;
-    hipLaunchKernelGGL((plan_rows_kernel<D, MODE>), dim3(blocks_main + blocks_chunk), dim3(kBlock), 0, s, a, blocks_main, 0, 0,
-                       blocks_chunk);
-    RC_LAUNCH_CHECK();
-  } else {
-    const uint32_t blocks_other = 64;
-    hipLaunchKernelGGL((plan_rows_kernel<D, MODE>), dim3(blocks_main + blocks_other), dim3(kBlock), 0, s, a, blocks_main, 0, 1, 0u);
-    RC_LAUNCH_CHECK();
-    if (n_occ > kPlanLongSeg) {  // otherwise no row can be hot
-      hipLaunchKernelGGL((plan_chunk_kernel<D>), dim3(1024), dim3(kBlock), 0, s, a);
-      RC_LAUNCH_CHECK();
-    }
-  }
+  // one workgroup per CU, fewer where the list cannot hold that many rows
+  const uint32_t med_max = (uint32_t)(n_occ / (kPlanBodyOcc + 1));   // a medium row has at least 3 occurrences
+  a.blocks_med = med_max / GPB + 1 < cus ? med_max / GPB + 1 : cus;
+  const uint32_t blocks_chunk = n_occ > kPlanLongSeg ? 512 : 0;
+  hipLaunchKernelGGL((plan_rows_kernel<D, MODE, true>), dim3(a.blocks_med + blocks_chunk + blocks_main), dim3(kBlock), 0, s, a,
+                     blocks_main, 0, 0, blocks_chunk);
+  RC_LAUNCH_CHECK();
   if (ev_items_done) RC_HIP(hipEventRecord(*ev_items_done, s));
   const uint32_t blocks_rows = cus * 2;
   const uint32_t blocks_long = n_occ > kPlanLongSeg ? 256 : 0;
-  hipLaunchKernelGGL((plan_final_kernel<D, MODE>), dim3(blocks_rows + blocks_long + 1), dim3(kBlock), 0, s, a, blocks_rows,
-                     blocks_long, 1);
+  hipLaunchKernelGGL((plan_final_kernel<D, MODE, true>), dim3(a.blocks_med + blocks_long + blocks_rows + 1), dim3(kBlock), 0, s, a,
+                     blocks_rows, blocks_long, 1);
   RC_LAUNCH_CHECK();
   return RC_OK;
 }
 
-// The three update launches of a BPRMF step (train_step.hip): item rows, chunks of hot rows, user rows + hot rows
+// The two update launches of a BPRMF step (train_step.hip): item rows + chunks of the hot rows, then user rows + hot rows
 // + loss mean.  Item-side gradients read pre-step U rows, so every read of U precedes the last launch.
 int plan_bprmf_step_updates(const BprmfStep& st, const rc_plan_row* rows_i, const uint32_t* n_rows_i, const rc_plan_row* rows_u,
                             const uint32_t* n_rows_u, const uint32_t* occ, uint32_t* counters, const PlanLongWs& lw,
-                            bool long_planned, hipEvent_t* ev_items_done) {
+                            const PlanMedList& med, hipEvent_t* ev_items_done) {
   const int64_t n_i = st.n_i();
   const int d = st.d;
   hipStream_t s = st.s;
   PlanUpdArgs a;
   memset(&a, 0, sizeof(a));
-  a.long_planned = long_planned ? 1 : 0;
+  a.long_planned = 1;
+  a.med = med;
   a.chunk = kPlanChunk;
   a.o = st.o;
   a.side[0].t = PlanTable{st.I, st.mI, st.vI};

@@ -156,6 +156,9 @@ PlanArgs slot_plan_args(const StepWs& w, int k, const int64_t* uid, const int64_
   pa.occ = sl.occ;
   pa.emit_long = 1;
   pa.lw = sl.plan_long;
+  // medium rows (5..32 occurrences of an item, 3..32 of a user), listed from the end of the row-record arrays
+  pa.med.end[0] = sl.rows_i + n_i; pa.med.cap[0] = (uint32_t)n_i; pa.med.over[0] = kPlanIdxOcc;    // items: plan_rows_indexed_body
+  pa.med.end[1] = sl.rows_u + B; pa.med.cap[1] = (uint32_t)B; pa.med.over[1] = kPlanBodyOcc;       // users: plan_rows_body
   return pa;
 }
 }  // namespace
@@ -381,7 +384,7 @@ int step_plan(const BprmfStep& st, const StepWs& w, void* ws, const StepChoice& 
   if (two_streams && !ah.hit) RC_HIP(hipStreamWaitEvent(s, side->join, 0));
   RC_TRY(pm.mark(4));
   RC_TRY(pm.mark(5));  // (the loss mean is one workgroup of the last update launch)
-  RC_TRY(plan_bprmf_step_updates(st, pa.rows_a, pa.n_rows_a, pa.rows_b, pa.n_rows_b, pa.occ, pa.w.counters, pa.lw, true, pm.at(6)));
+  RC_TRY(plan_bprmf_step_updates(st, pa.rows_a, pa.n_rows_a, pa.rows_b, pa.n_rows_b, pa.occ, pa.w.counters, pa.lw, pa.med, pm.at(6)));
   return pm.mark(7);
 }
 
