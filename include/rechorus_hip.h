@@ -1035,6 +1035,40 @@ int rc_directau_fwd(const float* user_tab, const int64_t* uid, const float* item
 int rc_directau_bwd(const float* grad_out, int64_t batch, int d, float coef_align, float coef_unif_user, float coef_unif_item,
                     const void* workspace, size_t ws_bytes, float* grad_user, float* grad_item, rc_stream_t stream);
 
+/* ---- ComiRec multi-interest extraction (models/sequential/ComiRec.py:57-93) --------------------------------------------------------
+ * h_l = item_tab[hist[b, l]], valid_l = hist[b, l] > 0, x_l = h_l + pos_tab[(len_b - l) valid_l] (x = h when pos_tab is NULL, :64-72);
+ * s[l, k] = W2[k] . tanh(W1 x_l + b1) + b2[k], -inf on invalid positions (:75-76); a[k, .] = softmax over l, 0 for a sequence
+ * without a valid position (:78-79; the row maximum is subtracted, not the batch-wide one: softmax is shift invariant per row);
+ * interest[k] = sum_l a[k, l] h_l (:80).  W1 [attn_size, d], b1 [attn_size], W2 [K, attn_size], b2 [K], hist [batch, L] int64,
+ * lengths [batch] int64.  An id outside [1, n_items) counts as padding and reads no memory.  No float atomics: reruns are bitwise
+ * identical.
+ * RC_OK when d % 4 == 0, 4 <= d <= 256, 1 <= attn_size <= 64, 1 <= K <= 16 and 1 <= L <= 256, else RC_ERR_UNSUPPORTED with the reason
+ * in rc_last_error_string() (host logic, no GPU needed; ComiRec.py:39-55, the shapes its parameters take); the entry points below
+ * check the same envelope themselves.                                                                                          */
+int rc_comirec_check_shape(int d, int attn_size, int K, int L);
+/* bytes of rc_comirec_bwd's caller workspace (256-byte aligned): the per-workgroup partials of the weight gradients (the sums
+ * autograd forms behind ComiRec.py:75); 0 outside the envelope */
+size_t rc_comirec_workspace_bytes(int d, int attn_size, int K, int L, int64_t batch);
+/* ComiRec.py:64-80 in one launch, every history row read once: interests [batch, K, d]; attn [batch, K, L] or NULL (the attention
+ * weights, what rc_comirec_bwd reads).  With targets [batch] (item ids; then sel and user are required, :84-87): sel [batch] =
+ * argmax_k <interest[k], item_tab[target]> (the lowest index on an exact tie), user [batch, d] = interest[sel].               */
+int rc_comirec_fwd(const float* item_tab, int64_t n_items, const float* pos_tab, int n_pos, const float* W1, const float* b1,
+                   const float* W2, const float* b2, const int64_t* hist, const int64_t* lengths, const int64_t* targets, int64_t batch,
+                   int L, int d, int attn_size, int K, float* interests, float* attn, int* sel, float* user, rc_stream_t stream);
+/* autograd of ComiRec.py:64-87 from d_user [batch, d] (no gradient flows through the selection): g_hist [batch, L, d] the
+ * per-occurrence item-row gradients (pooling path a[sel, l] d_user plus the W1 path), g_x [batch, L, d] the W1 path alone for the
+ * position table (NULL exactly when pos_tab is NULL); rows at invalid positions are zeros.  dW1, db1, dW2, db2: shaped like the
+ * parameters, only row sel[b] of dW2 / db2 receives anything from sequence b; per-workgroup partials in the workspace, added in
+ * workgroup order by a second launch.  attn, sel, user: what rc_comirec_fwd wrote for the same inputs.                          */
+int rc_comirec_bwd(const float* item_tab, int64_t n_items, const float* pos_tab, int n_pos, const float* W1, const float* b1,
+                   const float* W2, const int64_t* hist, const int64_t* lengths, const float* attn, const int* sel, const float* user,
+                   const float* d_user, int64_t batch, int L, int d, int attn_size, int K, float* g_hist, float* g_x, float* dW1,
+                   float* db1, float* dW2, float* db2, void* workspace, size_t ws_bytes, rc_stream_t stream);
+/* the evaluation head of ComiRec.py:90-91: pred [batch, C] = max_k <interests[b, k], item_tab[iid[b, c]]>, iid [batch, C] int64; the
+ * K interests of a sequence stay in LDS, each candidate row is read once.  An id outside [0, n_items) scores NaN.               */
+int rc_comirec_score_max(const float* interests, const float* item_tab, int64_t n_items, const int64_t* iid, int64_t batch, int64_t C,
+                         int d, int K, float* pred, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,11 @@ SIGNATURES = {
     "rc_directau_workspace_bytes": (_sz, [_i, _i64]),
     "rc_directau_fwd": (_i, [_p, _p, _p, _p, _i64, _i, _f, _i, _p, _sz, _p, _p, _p]),
     "rc_directau_bwd": (_i, [_p, _i64, _i, _f, _f, _f, _p, _sz, _p, _p, _p]),
+    "rc_comirec_check_shape": (_i, [_i, _i, _i, _i]),
+    "rc_comirec_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
+    "rc_comirec_fwd": (_i, [_p, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "rc_comirec_bwd": (_i, [_p, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i] + [_p] * 6 + [_p, _sz, _p]),
+    "rc_comirec_score_max": (_i, [_p, _p, _i64, _p, _i64, _i64, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -40,6 +40,7 @@ SOURCES = [
     "owner_step.hip",
     "lgcn.hip",
     "directau.hip",
+    "comirec.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -2512,3 +2512,101 @@ def directau_bwd(grad_out, batch, d, coef, buf, want_user=True, want_item=True):
               float(coef[2]), C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(gu, torch.float32, "grad_user", allow_none=True),
               _ptr(gi, torch.float32, "grad_item", allow_none=True), _stream())
     return gu, gi
+
+
+# ---- ComiRec multi-interest extraction (models/sequential/ComiRec.py:57-93) --------------------------------------------------------
+
+def comirec_check_shape(d, attn_size, K, L):
+    """rc_comirec_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 1 <= attn_size <= 64, 1 <= K <= 16, 1 <= L <= 256; raises
+    ValueError with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_comirec_check_shape(int(d), int(attn_size), int(K), int(L)) != _lib.RC_OK:
+        raise ValueError("ComiRec on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class ComiRecWorkspace:
+    """the scratch of rc_comirec_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
+    freed or moved while the owner lives"""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, d, attn_size, K, L, batch, device):
+        key = (int(d), int(attn_size), int(K), int(L), int(batch), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_comirec_workspace_bytes(int(d), int(attn_size), int(K), int(L), int(batch))
+            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return buf
+
+
+def _comirec_shapes(item_emb, pos_emb, W1, b1, W2, b2, hist, lengths):
+    d = item_emb.shape[1]
+    A, K = W1.shape[0], W2.shape[0]
+    if hist.dim() != 2 or hist.shape[0] < 1:
+        raise ValueError(f"comirec: history must be [batch >= 1, L], got {tuple(hist.shape)}")
+    B, L = hist.shape
+    comirec_check_shape(d, A, K, L)
+    if W1.shape != (A, d) or b1.shape != (A,) or W2.shape != (K, A) or (b2 is not None and b2.shape != (K,)):
+        raise ValueError("comirec: W1 [attn_size, d], b1 [attn_size], W2 [K, attn_size], b2 [K] expected")
+    if pos_emb is not None and pos_emb.shape[1] != d:
+        raise ValueError("comirec: the position table must have the item table's width")
+    if lengths.shape != (B,):
+        raise ValueError(f"comirec: lengths must be [{B}], got {tuple(lengths.shape)}")
+    return B, L, d, A, K
+
+
+def comirec_fwd(item_emb, pos_emb, W1, b1, W2, b2, hist, lengths, targets=None, want_attn=True):
+    """rc_comirec_fwd: ComiRec.py:64-87 in one launch -> (interests [B, K, d], attn [B, K, L] | None, sel int32 [B] | None,
+    user [B, d] | None); pos_emb None: --add_pos 0; targets [B] item ids: the hard selection of the training path"""
+    B, L, d, A, K = _comirec_shapes(item_emb, pos_emb, W1, b1, W2, b2, hist, lengths)
+    dev, f32 = item_emb.device, torch.float32
+    if targets is not None and targets.shape != (B,):
+        raise ValueError(f"comirec: targets must be [{B}], got {tuple(targets.shape)}")
+    interests = torch.empty((B, K, d), dtype=f32, device=dev)
+    attn = torch.empty((B, K, L), dtype=f32, device=dev) if want_attn else None
+    sel = torch.empty(B, dtype=torch.int32, device=dev) if targets is not None else None
+    user = torch.empty((B, d), dtype=f32, device=dev) if targets is not None else None
+    _lib.call("rc_comirec_fwd", _ptr(item_emb, f32, "item_emb"), item_emb.shape[0], _ptr(pos_emb, f32, "pos_emb", allow_none=True),
+              pos_emb.shape[0] if pos_emb is not None else 0, _ptr(W1, f32, "W1"), _ptr(b1, f32, "b1"), _ptr(W2, f32, "W2"),
+              _ptr(b2, f32, "b2"), _ptr(hist, torch.int64, "history"), _ptr(lengths, torch.int64, "lengths"),
+              _ptr(targets, torch.int64, "targets", allow_none=True), B, L, d, A, K, _ptr(interests, f32, "interests"),
+              _ptr(attn, f32, "attn", allow_none=True), _ptr(sel, torch.int32, "sel", allow_none=True),
+              _ptr(user, f32, "user", allow_none=True), _stream())
+    return interests, attn, sel, user
+
+
+def comirec_bwd(item_emb, pos_emb, W1, b1, W2, hist, lengths, attn, sel, user, d_user, workspace=None):
+    """rc_comirec_bwd -> (g_hist [B, L, d], g_x [B, L, d] | None, dW1, db1, dW2, db2): per-occurrence row gradients (zeros at
+    invalid positions) and the weight gradients, no gradient through the selection"""
+    B, L, d, A, K = _comirec_shapes(item_emb, pos_emb, W1, b1, W2, None, hist, lengths)
+    dev, f32 = item_emb.device, torch.float32
+    if attn.shape != (B, K, L) or sel.shape != (B,) or user.shape != (B, d) or d_user.shape != (B, d):
+        raise ValueError("comirec_bwd: attn [B, K, L], sel [B], user [B, d], d_user [B, d] expected")
+    ws = (workspace if workspace is not None else ComiRecWorkspace()).get(d, A, K, L, B, dev)
+    g_hist = torch.empty((B, L, d), dtype=f32, device=dev)
+    g_x = torch.empty((B, L, d), dtype=f32, device=dev) if pos_emb is not None else None
+    dW1, db1 = torch.empty((A, d), dtype=f32, device=dev), torch.empty(A, dtype=f32, device=dev)
+    dW2, db2 = torch.empty((K, A), dtype=f32, device=dev), torch.empty(K, dtype=f32, device=dev)
+    _lib.call("rc_comirec_bwd", _ptr(item_emb, f32, "item_emb"), item_emb.shape[0], _ptr(pos_emb, f32, "pos_emb", allow_none=True),
+              pos_emb.shape[0] if pos_emb is not None else 0, _ptr(W1, f32, "W1"), _ptr(b1, f32, "b1"), _ptr(W2, f32, "W2"),
+              _ptr(hist, torch.int64, "history"), _ptr(lengths, torch.int64, "lengths"), _ptr(attn, f32, "attn"),
+              _ptr(sel, torch.int32, "sel"), _ptr(user, f32, "user"), _ptr(d_user, f32, "d_user"), B, L, d, A, K,
+              _ptr(g_hist, f32, "g_hist"), _ptr(g_x, f32, "g_x", allow_none=True), _ptr(dW1, f32, "dW1"), _ptr(db1, f32, "db1"),
+              _ptr(dW2, f32, "dW2"), _ptr(db2, f32, "db2"), *_ws_args(ws))
+    return g_hist, g_x, dW1, db1, dW2, db2
+
+
+def comirec_score_max(interests, item_emb, iid):
+    """rc_comirec_score_max: pred [B, C] = max_k <interests[b, k], item_emb[iid[b, c]]> (ComiRec.py:90-91)"""
+    if interests.dim() != 3 or iid.dim() != 2 or iid.shape[0] != interests.shape[0] or iid.shape[1] < 1:
+        raise ValueError(f"comirec_score_max: interests [B, K, d] and candidates [B, C >= 1] expected, got {tuple(interests.shape)} / "
+                         f"{tuple(iid.shape)}")
+    B, K, d = interests.shape
+    comirec_check_shape(d, 1, K, 1)
+    if item_emb.shape[1] != d:
+        raise ValueError("comirec_score_max: interests and item table need the same emb_size")
+    pred = torch.empty(iid.shape, dtype=torch.float32, device=interests.device)
+    _lib.call("rc_comirec_score_max", _ptr(interests, torch.float32, "interests"), _ptr(item_emb, torch.float32, "item_emb"),
+              item_emb.shape[0], _ptr(iid, torch.int64, "candidates"), B, iid.shape[1], d, K, _ptr(pred, torch.float32, "pred"), _stream())
+    return pred

@@ -202,6 +202,60 @@ def uniformity(x, workspace=None):
     return _DirectAUFn.apply(x, x, 0.0, "unif", workspace)
 
 
+class _ComiRecFn(torch.autograd.Function):
+    """ComiRec's multi-interest extraction with the hard selection of training (models/sequential/ComiRec.py:64-87) on
+    rc_comirec_fwd / _bwd -> (user [B, d], interests [B, K, d], sel [B]); only `user` carries gradient, none flows through the
+    selection.  Backward: dense gradients of the item table (engine.embedding_dense_backward over the history occurrences), the
+    position table (the SASRec position rule) and the four weight tensors."""
+
+    @staticmethod
+    def forward(ctx, item_w, pos_w, W1, b1, W2, b2, hist, lengths, targets, workspace):
+        det = [t.detach().contiguous() if t is not None else None for t in (item_w, pos_w, W1, b1, W2, b2)]
+        interests, attn, sel, user = engine.comirec_fwd(*det, hist, lengths, targets=targets)
+        ctx.save_for_backward(*[t for t in det[:5] if t is not None], hist, lengths, attn, sel, user)
+        ctx.has_pos, ctx.workspace = pos_w is not None, workspace
+        ctx.n_items, ctx.n_pos = item_w.shape[0], (pos_w.shape[0] if pos_w is not None else 0)
+        ctx.mark_non_differentiable(interests, sel)
+        return user, interests, sel
+
+    @staticmethod
+    def backward(ctx, d_user, _gi, _gs):
+        saved = list(ctx.saved_tensors)
+        item_w = saved.pop(0)
+        pos_w = saved.pop(0) if ctx.has_pos else None
+        W1, b1, W2, hist, lengths, attn, sel, user = saved
+        g_hist, g_x, dW1, db1, dW2, db2 = engine.comirec_bwd(item_w, pos_w, W1, b1, W2, hist, lengths, attn, sel, user,
+                                                             d_user.contiguous(), workspace=ctx.workspace)
+        G_item = engine.embedding_dense_backward(g_hist, hist, ctx.n_items)
+        G_pos = None
+        if ctx.has_pos:
+            if g_x.shape[2] in (32, 64):
+                G_pos = engine.sasrec_pos_grad(g_x, lengths, ctx.n_pos)
+            else:
+                B, L, d = g_x.shape
+                G_pos = engine.seq_pos_grad(g_x.view(B * L, d), lengths, B, L, ctx.n_pos)
+        return G_item, G_pos, dW1, db1, dW2, db2, None, None, None, None
+
+
+def comirec_user_vector(item_w, pos_w, W1, b1, W2, b2, hist, lengths, targets, workspace=None, details=False):
+    """the training path of ComiRec.py:64-87: user [B, d] = the interest of each sequence that scores its target item highest
+    (pos_w None: --add_pos 0).  Its output goes into bprmf_scores(user, item_w, arange(B), item_id), which adds the candidates'
+    gradient to the item table.  details=True: (user, interests [B, K, d], sel int32 [B]) -- the latter two carry no gradient."""
+    out = _ComiRecFn.apply(item_w, pos_w, W1, b1, W2, b2, hist.contiguous(), lengths.contiguous(), targets.contiguous(), workspace)
+    return out if details else out[0]
+
+
+def comirec_scores(item_w, pos_w, W1, b1, W2, b2, hist, lengths, item_id):
+    """the evaluation path of ComiRec.py:64-80,90-91: prediction [B, C] = max_k <interest[b, k], item_w[item_id[b, c]]>; forward
+    only (rc_comirec_score_max has no backward): raises when autograd is recording"""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (item_w, pos_w, W1, b1, W2, b2)):
+        raise RuntimeError("comirec_scores is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through comirec_user_vector)")
+    det = [t.detach().contiguous() if t is not None else None for t in (item_w, pos_w, W1, b1, W2, b2)]
+    interests, _, _, _ = engine.comirec_fwd(*det, hist.contiguous(), lengths.contiguous(), want_attn=False)
+    return engine.comirec_score_max(interests, det[0], item_id.contiguous())
+
+
 class _BprLossFn(torch.autograd.Function):
     """GeneralModel.loss (models/BaseModel.py:182-185), closed-form backward."""
 
