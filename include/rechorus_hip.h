@@ -1069,6 +1069,45 @@ int rc_comirec_bwd(const float* item_tab, int64_t n_items, const float* pos_tab,
 int rc_comirec_score_max(const float* interests, const float* item_tab, int64_t n_items, const int64_t* iid, int64_t batch, int64_t C,
                          int d, int K, float* pred, rc_stream_t stream);
 
+/* ---- BUIR bootstrap loss, evaluation head and target update (models/general/BUIR.py:66-110, helpers/BUIRRunner.py:35-36) ----------
+ * P = nn.Linear(d, d) with W [d, d] (out x in) and b; uo / io = user_online[uid[b]] / item_online[iid[b]], ut / it the same rows of
+ * the target tables; n(x) = F.normalize(x) = x / max(|x|, 1e-12); pu = W uo + b, pi = W io + b (:83-88);
+ * loss = mean_b [4 - 2 <n(pu), n(it)> - 2 <n(pi), n(ut)>] (:97-110, the target rows carry no gradient).  One workgroup owns 64
+ * batch rows at a time: uo | io rows, W and b in LDS, pu | pi as one product on fp32 MFMA, the target rows read once from HBM.
+ * No float atomics: per-workgroup partials are added in workgroup order by a second launch, reruns are bitwise identical.
+ * RC_OK when d % 16 == 0, 16 <= d <= 128 and 1 <= batch <= 2^20, else RC_ERR_UNSUPPORTED with the reason in
+ * rc_last_error_string() (host logic, no GPU needed); the entry points below check the same envelope themselves.               */
+int rc_buir_check_shape(int d, int64_t batch);
+/* bytes of the caller workspace (256-byte aligned) for this shape: the per-workgroup partials of loss, dW and db; 0 outside the
+ * envelope */
+size_t rc_buir_workspace_bytes(int d, int64_t batch);
+/* forward (BUIR.py:73-110): loss [1] (device); prediction [batch] or NULL: the training prediction <P(io), uo> + <P(uo), io> of
+ * :78-79 for the one positive item of a row.  uid, iid [batch] int64.  Nothing is kept for the backward pass.                   */
+int rc_buir_fwd(const float* user_online, const float* user_target, const float* item_online, const float* item_target,
+                const float* W, const float* b, const int64_t* uid, const int64_t* iid, int64_t batch, int d, void* workspace,
+                size_t ws_bytes, float* prediction, float* loss, rc_stream_t stream);
+/* autograd of BUIR.py:83-110 from grad_out [1] (device), the upstream gradient of the loss: the forward values are recomputed
+ * from the same inputs; g_pu = -2 grad_out / batch times F.normalize's backward of n(it) at pu ((g - x^ (x^ . g)) / |x| past eps,
+ * g / eps below), g_pi its mirror; grad_user = g_pu W and grad_item = g_pi W [batch, d] are per-occurrence row gradients of the
+ * ONLINE tables, dW [d, d] = sum_b (g_pu uo^T + g_pi io^T), db [d] = sum_b (g_pu + g_pi).                                        */
+int rc_buir_bwd(const float* user_online, const float* user_target, const float* item_online, const float* item_target,
+                const float* W, const float* b, const int64_t* uid, const int64_t* iid, const float* grad_out, int64_t batch, int d,
+                void* workspace, size_t ws_bytes, float* grad_user, float* grad_item, float* dW, float* db, rc_stream_t stream);
+/* the evaluation head of BUIR.py:78-79: prediction[b, c] = <P(io_c), uo_b> + <P(uo_b), io_c> = <q_b, io_c> + c_b with
+ * q_b = (W + W^T) uo_b + b and c_b = <b, uo_b>.  rc_buir_query: q [batch, d], c [batch] of one evaluation batch;
+ * rc_buir_scores: scores [batch, n_candidates] = <q_b, item_online[iid[b, c]]> + c_b, iid [batch, n_candidates] int64.
+ * (c_b is constant over a user's candidates: the full-catalogue rank takes q and the item table as they are.)                  */
+int rc_buir_query(const float* user_online, const float* W, const float* b, const int64_t* uid, int64_t batch, int d, float* q,
+                  float* c, rc_stream_t stream);
+int rc_buir_scores(const float* q, const float* c, const float* item_online, const int64_t* iid, int64_t batch, int64_t n_candidates,
+                   int d, float* scores, rc_stream_t stream);
+/* BUIR._update_target (BUIR.py:66-71, called after every optimizer step by BUIRRunner.py:36): target = target * m + online *
+ * (1 - m) on two tables of n_a / n_b floats in ONE launch, in place, each table read once and the target written once.  m and
+ * 1 - m (formed in double) are rounded to fp32 on the host, the two products and the sum are rounded separately as torch rounds
+ * them: the result is bit-equal to the reference's.                                                                           */
+int rc_buir_ema(float* target_a, const float* online_a, int64_t n_a, float* target_b, const float* online_b, int64_t n_b,
+                double momentum, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

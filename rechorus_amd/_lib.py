@@ -79,6 +79,7 @@ _f = C.c_float
 _sz = C.c_size_t
 _hp = C.POINTER(OptHyper)
 _gp = C.POINTER(LgcnGraph)
+_dbl = C.c_double
 
 # name -> (restype, argtypes); must list every symbol include/rechorus_hip.h declares
 SIGNATURES = {
@@ -220,6 +221,13 @@ SIGNATURES = {
     "rc_directau_workspace_bytes": (_sz, [_i, _i64]),
     "rc_directau_fwd": (_i, [_p, _p, _p, _p, _i64, _i, _f, _i, _p, _sz, _p, _p, _p]),
     "rc_directau_bwd": (_i, [_p, _i64, _i, _f, _f, _f, _p, _sz, _p, _p, _p]),
+    "rc_buir_check_shape": (_i, [_i, _i64]),
+    "rc_buir_workspace_bytes": (_sz, [_i, _i64]),
+    "rc_buir_fwd": (_i, [_p] * 8 + [_i64, _i, _p, _sz, _p, _p, _p]),
+    "rc_buir_bwd": (_i, [_p] * 9 + [_i64, _i, _p, _sz, _p, _p, _p, _p, _p]),
+    "rc_buir_query": (_i, [_p, _p, _p, _p, _i64, _i, _p, _p, _p]),
+    "rc_buir_scores": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _p, _p]),
+    "rc_buir_ema": (_i, [_p, _p, _i64, _p, _p, _i64, _dbl, _p]),
     "rc_comirec_check_shape": (_i, [_i, _i, _i, _i]),
     "rc_comirec_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
     "rc_comirec_fwd": (_i, [_p, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

@@ -41,6 +41,7 @@ SOURCES = [
     "lgcn.hip",
     "directau.hip",
     "comirec.hip",
+    "buir.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -2610,3 +2610,124 @@ def comirec_score_max(interests, item_emb, iid):
     _lib.call("rc_comirec_score_max", _ptr(interests, torch.float32, "interests"), _ptr(item_emb, torch.float32, "item_emb"),
               item_emb.shape[0], _ptr(iid, torch.int64, "candidates"), B, iid.shape[1], d, K, _ptr(pred, torch.float32, "pred"), _stream())
     return pred
+
+
+# ---- BUIR bootstrap loss, evaluation head, target update (models/general/BUIR.py:66-110) -----------------------------------------
+
+def buir_check_shape(d, batch=1):
+    """rc_buir_check_shape (host logic): d % 16 == 0, 16 <= d <= 128, 1 <= batch <= 2^20; raises ValueError with the library's
+    reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_buir_check_shape(int(d), int(batch)) != _lib.RC_OK:
+        raise ValueError("BUIR on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class BuirWorkspace:
+    """the scratch of rc_buir_fwd / _bwd (the per-workgroup partials of loss, dW and db), one buffer per (batch, d) that is never
+    freed or moved while the owner lives: a captured training step replays on the same memory.  `generation` counts the launches
+    that wrote it.  Nothing in it outlives the call that wrote it (the backward pass recomputes the forward values from the
+    tables), so two pending losses may share one workspace."""
+
+    def __init__(self):
+        self._bufs = {}
+        self.generation = 0
+
+    def get(self, batch, d, device):
+        key = (int(batch), int(d), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_buir_workspace_bytes(int(d), int(batch))
+            buf = self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.generation += 1
+        return buf
+
+
+def _buir_shapes(user_online, user_target, item_online, item_target, W, b, uid, iid):
+    d = W.shape[-1]
+    B = uid.numel()
+    buir_check_shape(d, B)
+    if W.shape != (d, d) or b.shape != (d,):
+        raise ValueError(f"buir: predictor weight [d, d] and bias [d] expected, got {tuple(W.shape)} / {tuple(b.shape)}")
+    for name, t in (("user_online", user_online), ("user_target", user_target), ("item_online", item_online),
+                    ("item_target", item_target)):
+        if t is not None and (t.dim() != 2 or t.shape[1] != d):
+            raise ValueError(f"buir: {name} must be [rows, {d}], got {tuple(t.shape)}")
+    if user_target is not None and (user_target.shape != user_online.shape or item_target.shape != item_online.shape):
+        raise ValueError("buir: a target table has its online table's shape")
+    if iid is not None and iid.numel() != B:
+        raise ValueError(f"buir: one positive item per row expected, got {tuple(iid.shape)} for {B} users")
+    return B, d
+
+
+def _buir_common(tables, W, b, uid, iid):
+    f32, i64 = torch.float32, torch.int64
+    names = ("user_online", "user_target", "item_online", "item_target")
+    return ([_ptr(t, f32, n) for t, n in zip(tables, names)] + [_ptr(W, f32, "W"), _ptr(b, f32, "b"), _ptr(uid, i64, "user ids"),
+                                                                 _ptr(iid, i64, "item ids")])
+
+
+def buir_fwd(user_online, user_target, item_online, item_target, W, b, uid, iid, workspace=None, prediction=True):
+    """rc_buir_fwd -> (loss [], prediction [B, 1] | None): BUIR.py:73-110 for B (user, positive item) rows"""
+    B, d = _buir_shapes(user_online, user_target, item_online, item_target, W, b, uid, iid)
+    uid, iid = uid.reshape(-1).contiguous(), iid.reshape(-1).contiguous()
+    dev = W.device
+    buf = (workspace if workspace is not None else BuirWorkspace()).get(B, d, dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    pred = torch.empty((B, 1), dtype=torch.float32, device=dev) if prediction else None
+    _lib.call("rc_buir_fwd", *_buir_common((user_online, user_target, item_online, item_target), W, b, uid, iid), B, d,
+              C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(pred, torch.float32, "prediction", allow_none=True),
+              _ptr(loss, torch.float32, "loss"), _stream())
+    return loss[0], pred
+
+
+def buir_bwd(grad_out, user_online, user_target, item_online, item_target, W, b, uid, iid, workspace=None):
+    """rc_buir_bwd: grad_out [] / [1] on the device -> (grad_user [B, d], grad_item [B, d], dW [d, d], db [d]); the first two are
+    per-occurrence row gradients of the online tables"""
+    B, d = _buir_shapes(user_online, user_target, item_online, item_target, W, b, uid, iid)
+    uid, iid = uid.reshape(-1).contiguous(), iid.reshape(-1).contiguous()
+    dev, f32 = W.device, torch.float32
+    buf = (workspace if workspace is not None else BuirWorkspace()).get(B, d, dev)
+    g = grad_out.reshape(1).to(f32).contiguous()
+    gu, gi = torch.empty((B, d), dtype=f32, device=dev), torch.empty((B, d), dtype=f32, device=dev)
+    dW, db = torch.empty((d, d), dtype=f32, device=dev), torch.empty(d, dtype=f32, device=dev)
+    _lib.call("rc_buir_bwd", *_buir_common((user_online, user_target, item_online, item_target), W, b, uid, iid),
+              _ptr(g, f32, "grad_out"), B, d, C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(gu, f32, "grad_user"),
+              _ptr(gi, f32, "grad_item"), _ptr(dW, f32, "dW"), _ptr(db, f32, "db"), _stream())
+    return gu, gi, dW, db
+
+
+def buir_query(user_online, W, b, uid):
+    """rc_buir_query -> (q [B, d], c [B]): q_b = (W + W^T) u_b + b, c_b = <b, u_b> for u_b = user_online[uid[b]]"""
+    B, d = _buir_shapes(user_online, None, None, None, W, b, uid, None)
+    uid = uid.reshape(-1).contiguous()
+    f32 = torch.float32
+    q, c = torch.empty((B, d), dtype=f32, device=W.device), torch.empty(B, dtype=f32, device=W.device)
+    _lib.call("rc_buir_query", _ptr(user_online, f32, "user_online"), _ptr(W, f32, "W"), _ptr(b, f32, "b"),
+              _ptr(uid, torch.int64, "user ids"), B, d, _ptr(q, f32, "q"), _ptr(c, f32, "c"), _stream())
+    return q, c
+
+
+def buir_scores(q, c, item_online, iid):
+    """rc_buir_scores -> [B, C]: <q_b, item_online[iid[b, c]]> + c_b"""
+    if q.dim() != 2 or iid.dim() != 2 or iid.shape[0] != q.shape[0] or iid.shape[1] < 1 or c.shape != (q.shape[0],):
+        raise ValueError(f"buir_scores: q [B, d], c [B] and candidates [B, C >= 1] expected, got {tuple(q.shape)} / {tuple(c.shape)} / "
+                         f"{tuple(iid.shape)}")
+    B, d = q.shape
+    buir_check_shape(d, B)
+    if item_online.dim() != 2 or item_online.shape[1] != d:
+        raise ValueError("buir_scores: q and the item table need the same emb_size")
+    out = torch.empty(iid.shape, dtype=torch.float32, device=q.device)
+    _lib.call("rc_buir_scores", _ptr(q, torch.float32, "q"), _ptr(c, torch.float32, "c"), _ptr(item_online, torch.float32, "item_online"),
+              _ptr(iid.contiguous(), torch.int64, "candidates"), B, iid.shape[1], d, _ptr(out, torch.float32, "scores"), _stream())
+    return out
+
+
+def ema_update(target_a, online_a, target_b, online_b, momentum):
+    """rc_buir_ema: target = target * m + online * (1 - m) on both pairs in place, one launch, rounded as torch rounds the
+    expression (BUIR.py:66-71)"""
+    for t, o in ((target_a, online_a), (target_b, online_b)):
+        if t.shape != o.shape:
+            raise ValueError(f"ema_update: target {tuple(t.shape)} and online {tuple(o.shape)} differ in shape")
+    f32 = torch.float32
+    _lib.call("rc_buir_ema", _ptr(target_a, f32, "target_a"), _ptr(online_a, f32, "online_a"), target_a.numel(),
+              _ptr(target_b, f32, "target_b"), _ptr(online_b, f32, "online_b"), target_b.numel(), float(momentum), _stream())

@@ -256,6 +256,50 @@ def comirec_scores(item_w, pos_w, W1, b1, W2, b2, hist, lengths, item_id):
     return engine.comirec_score_max(interests, det[0], item_id.contiguous())
 
 
+class _BuirLossFn(torch.autograd.Function):
+    """BUIR's training step up to the loss (models/general/BUIR.py:73-110) on rc_buir_fwd / _bwd -> (loss, prediction [B, 1]).
+    The prediction is marked non-differentiable: a loss built on it raises instead of training on nothing.  Backward: the forward
+    values are recomputed from the saved inputs (autograd's version check refuses tables modified in between); the per-occurrence
+    row gradients become dense gradients of the two online tables, the target tables get none."""
+
+    @staticmethod
+    def forward(ctx, user_online, user_target, item_online, item_target, W, b, uid, iid, workspace):
+        det = [t.detach() for t in (user_online, user_target, item_online, item_target, W, b)]
+        loss, pred = engine.buir_fwd(*det, uid, iid, workspace=workspace)
+        ctx.save_for_backward(*det, uid, iid)
+        ctx.workspace = workspace
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _g_pred):
+        *tables, uid, iid = ctx.saved_tensors
+        gu, gi, dW, db = engine.buir_bwd(g, *tables, uid, iid, workspace=ctx.workspace)
+        G_user = engine.embedding_dense_backward(gu, uid, tables[0].shape[0], route="small", small_tag="buir_user")
+        G_item = engine.embedding_dense_backward(gi, iid, tables[2].shape[0], route="small", small_tag="buir_item")
+        return G_user, None, G_item, None, dW, db, None, None, None
+
+
+def buir_loss(user_online, user_target, item_online, item_target, W, b, uid, iid, workspace=None):
+    """BUIR.forward's training branch and BUIR.loss (models/general/BUIR.py:73-110) for B (user, positive item) rows as ONE
+    autograd node -> (loss, prediction [B, 1]); workspace: the model's engine.BuirWorkspace, reused step after step"""
+    for t in (user_online, user_target, item_online, item_target, W, b):
+        if not t.is_contiguous():
+            raise ValueError("buir_loss: tables, weight and bias must be contiguous")
+    return _BuirLossFn.apply(user_online, user_target, item_online, item_target, W, b, uid.reshape(-1).contiguous(),
+                             iid.reshape(-1).contiguous(), workspace)
+
+
+def buir_scores(user_online, item_online, W, b, uid, iid):
+    """the evaluation path of BUIR.py:78-79: prediction [B, C] = <P(i_c), u> + <P(u), i_c>, as <q, i_c> + c with q = (W + W^T) u +
+    b and c = <b, u> (rc_buir_query, rc_buir_scores); forward only: raises when autograd is recording"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (user_online, item_online, W, b)):
+        raise RuntimeError("buir_scores is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through buir_loss)")
+    q, c = engine.buir_query(user_online.detach(), W.detach(), b.detach(), uid)
+    return engine.buir_scores(q, c, item_online.detach(), iid)
+
+
 class _BprLossFn(torch.autograd.Function):
     """GeneralModel.loss (models/BaseModel.py:182-185), closed-form backward."""
 

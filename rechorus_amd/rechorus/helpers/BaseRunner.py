@@ -271,6 +271,7 @@ class BaseRunner(object):
                 if step is None:
                     step = self._graphed[key] = hgraph.GraphedStep(model)
                 losses.append(step.run(batch))
+                self._after_step(model)
                 continue
             item_ids = batch['item_id']
             indices = None
@@ -288,9 +289,14 @@ class BaseRunner(object):
             loss = model.loss(out_dict)
             loss.backward()
             model.optimizer.step()
+            self._after_step(model)
             losses.append(loss.detach().reshape(1))
         # epoch loss = mean of per-batch means (reference :207-208); one D2H copy per epoch
         return float(torch.cat([l.reshape(1) for l in losses]).mean().item()) if losses else float('nan')
+
+    def _after_step(self, model):
+        """called after every dense optimizer step of fit(), replayed or eager; nothing to do here (BUIRRunner moves the target
+        tables)"""
 
     def eval_termination(self, criterion: List[float]) -> bool:
         if len(criterion) > self.early_stop and utils.non_increasing(criterion[-self.early_stop:]):

@@ -1,8 +1,9 @@
-"""Train BPRMF / NeuMF / SASRec / LightGCN / DirectAU / ComiRec with the reference's demo flags (docs/demo_scripts_results/Topk_Amazon.sh:6,8,26,12,16,35) on the
+"""Train BPRMF / NeuMF / SASRec / LightGCN / DirectAU / ComiRec / BUIR with the reference's demo flags (docs/demo_scripts_results/Topk_Amazon.sh:6,8,26,12,16,35,14) on the
 Grocery split of tools/make_grocery_split.py through the plugin's main.py, in dense (torch.optim semantics) and
-row-wise mode, and report test HR@5 / NDCG@5 next to the published numbers (docs/demo_scripts_results/README.md:47,48,56,49,51,57).
-LightGCN, DirectAU and ComiRec have no row-wise step (LightGCN's gradient is dense over L-hop neighbourhoods, DirectAU's uniformity
-term couples every pair of the batch, ComiRec's model file has none yet): they run in dense mode only.
+row-wise mode, and report test HR@5 / NDCG@5 next to the published numbers (docs/demo_scripts_results/README.md:47,48,56,49,51,57,50).
+LightGCN, DirectAU, ComiRec and BUIR have no row-wise step (LightGCN's gradient is dense over L-hop neighbourhoods, DirectAU's
+uniformity term couples every pair of the batch, ComiRec's model file has none yet, BUIR's target tables follow dense updates):
+they run in dense mode only.
 GPU box: python tools/run_grocery.py --out gpurun_out/<tag>/grocery_metrics.json"""
 import argparse
 import json
@@ -16,7 +17,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "rechorus_amd", "rechorus"))
 
 PUBLISHED = {"BPRMF": (0.3549, 0.2486, 2.5), "NeuMF": (0.3237, 0.2221, 3.4), "SASRec": (0.3917, 0.2942, 5.5),
-             "LightGCN": (0.3705, 0.2564, 6.1), "DirectAU": (0.3911, 0.2779, 3.3), "ComiRec": (0.3753, 0.2675, 4.5)}
+             "LightGCN": (0.3705, 0.2564, 6.1), "DirectAU": (0.3911, 0.2779, 3.3), "ComiRec": (0.3753, 0.2675, 4.5), "BUIR": (0.3701, 0.2567, 3.3)}
 FLAGS = {
     "BPRMF": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-6"],
     "NeuMF": ["--emb_size", "64", "--layers", "[64]", "--lr", "5e-4", "--l2", "1e-7", "--dropout", "0.2"],
@@ -24,6 +25,7 @@ FLAGS = {
     "LightGCN": ["--emb_size", "64", "--n_layers", "3", "--lr", "1e-3", "--l2", "1e-8"],
     "DirectAU": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-5", "--gamma", "0.3"],
     "ComiRec": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-6", "--attn_size", "8", "--K", "4", "--add_pos", "1", "--history_max", "20"],
+    "BUIR": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-6"],
 }
 
 
@@ -31,7 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--epoch", type=int, default=200)
-    ap.add_argument("--models", default="BPRMF,NeuMF,SASRec,LightGCN,DirectAU,ComiRec")
+    ap.add_argument("--models", default="BPRMF,NeuMF,SASRec,LightGCN,DirectAU,ComiRec,BUIR")
     ap.add_argument("--engines", default="dense,rowwise")
     a = ap.parse_args()
     import main as plugin_main
@@ -41,7 +43,7 @@ def main():
     res = {}
     for model in a.models.split(","):
         for engine in a.engines.split(","):
-            if engine == "rowwise" and model in ("LightGCN", "DirectAU", "ComiRec"):
+            if engine == "rowwise" and model in ("LightGCN", "DirectAU", "ComiRec", "BUIR"):
                 continue
             if engine == "rowwise" and model == "NeuMF":
                 extra = ["--dropout", "0.2"]
