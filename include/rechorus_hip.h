@@ -1108,6 +1108,35 @@ int rc_buir_scores(const float* q, const float* c, const float* item_online, con
 int rc_buir_ema(float* target_a, const float* online_a, int64_t n_a, float* target_b, const float* online_b, int64_t n_b,
                 double momentum, rc_stream_t stream);
 
+/* ---- AutoInt: field self-attention layer (models/context/AutoInt.py:49-80, utils/layers.py:9-63) ----------------------------------
+ * One interacting layer over X [n_instances, n_fields, d_in] (n_instances = batch * candidates): Q | K | V = X W^T with
+ * Wq, Wk, Wv [attention_size, d_in] (no bias), R = X Wr^T + br, per instance and head S = Q_h K_h^T / sqrt(dk), P = softmax over the
+ * key axis, O_h = P V_h (no output projection), Y = relu(O + R) [n_instances, n_fields, attention_size].  The reference shifts the
+ * scores by their GLOBAL maximum before the softmax and replaces NaN by 0 (layers.py:60-61); for finite inputs and no mask that is
+ * a mathematical no-op and the kernels use the row maximum: finite inputs are part of the envelope.
+ * No float atomics: per-workgroup partials are added in workgroup order by a second launch, reruns are bitwise identical.
+ * RC_OK when 2 <= n_fields <= 32, d_in % 4 == 0, 4 <= d_in <= 128, 4 <= attention_size <= 64 and num_heads divides attention_size,
+ * else RC_ERR_UNSUPPORTED with the reason in rc_last_error_string() (host logic, no GPU needed); the entry points below check the
+ * same envelope themselves, and 1 <= n_instances <= 2^24.                                                                        */
+int rc_autoint_check_shape(int n_fields, int d_in, int attention_size, int num_heads);
+/* bytes of the caller workspace (256-byte aligned) of rc_autoint_layer_bwd for this shape: the per-workgroup partials of the
+ * weight gradients; 0 outside the envelope */
+size_t rc_autoint_workspace_bytes(int64_t n_instances, int n_fields, int d_in, int attention_size, int num_heads);
+/* forward of one layer (AutoInt.py:72-75 = layers.py:34-63 + the residual Linear + relu) in ONE launch: X is read once, Y written
+ * once, nothing is kept for the backward pass.                                                                                   */
+int rc_autoint_layer_fwd(const float* X, const float* Wq, const float* Wk, const float* Wv, const float* Wr, const float* br,
+                         int64_t n_instances, int n_fields, int d_in, int attention_size, int num_heads, float* Y,
+                         rc_stream_t stream);
+/* autograd of AutoInt.py:72-75 from dY (the gradient of Y) and the forward's X and Y: Q, K, V and P are recomputed;
+ * dZ = dY * (Y > 0) = dR = dO, dP = dO_h V_h^T, dV_h = P^T dO_h, dS = P * (dP - rowsum(dP * P)), dQ_h = dS K_h / sqrt(dk),
+ * dK_h = dS^T Q_h / sqrt(dk); dX [n_instances, n_fields, d_in] = dQ Wq + dK Wk + dV Wv + dR Wr is written once;
+ * dWq, dWk, dWv, dWr [attention_size, d_in] = G^T X over all rows, dbr [attention_size] = column sum of dR (two launches: the tile
+ * kernel and the fixed-order reduce of its partials).                                                                            */
+int rc_autoint_layer_bwd(const float* X, const float* Wq, const float* Wk, const float* Wv, const float* Wr, const float* Y,
+                         const float* dY, int64_t n_instances, int n_fields, int d_in, int attention_size, int num_heads,
+                         void* workspace, size_t ws_bytes, float* dX, float* dWq, float* dWk, float* dWv, float* dWr, float* dbr,
+                         rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ SOURCES = [
     "directau.hip",
     "comirec.hip",
     "buir.hip",
+    "autoint.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

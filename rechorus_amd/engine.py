@@ -2731,3 +2731,72 @@ def ema_update(target_a, online_a, target_b, online_b, momentum):
     f32 = torch.float32
     _lib.call("rc_buir_ema", _ptr(target_a, f32, "target_a"), _ptr(online_a, f32, "online_a"), target_a.numel(),
               _ptr(target_b, f32, "target_b"), _ptr(online_b, f32, "online_b"), target_b.numel(), float(momentum), _stream())
+
+
+# ---- AutoInt field self-attention layer (models/context/AutoInt.py:49-80, utils/layers.py:9-63) ----------------------------------
+
+def autoint_check_shape(n_fields, d_in, attention_size, num_heads):
+    """rc_autoint_check_shape (host logic): 2 <= fields <= 32, d_in % 4 == 0, 4 <= d_in <= 128, 4 <= attention_size <= 64, num_heads a
+    divisor of attention_size; raises ValueError with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_autoint_check_shape(int(n_fields), int(d_in), int(attention_size), int(num_heads)) != _lib.RC_OK:
+        raise ValueError("AutoInt on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class AutoIntWorkspace:
+    """the scratch of rc_autoint_layer_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
+    freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
+    that wrote it, so the layers of a stack share one workspace."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, n, n_fields, d_in, attention_size, num_heads, device):
+        key = (int(n), int(n_fields), int(d_in), int(attention_size), int(num_heads), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_autoint_workspace_bytes(*key[:5])
+            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return buf
+
+
+def _autoint_shapes(X, Wq, Wk, Wv, Wr, br, heads):
+    if X.dim() < 3 or X.numel() == 0:
+        raise ValueError(f"autoint_layer: X must be [..., fields, width] with at least one instance, got {tuple(X.shape)}")
+    F, d = X.shape[-2:]
+    N = X.numel() // (F * d)
+    A = Wq.shape[0]
+    autoint_check_shape(F, d, A, heads)
+    for name, W in (("Wq", Wq), ("Wk", Wk), ("Wv", Wv), ("Wr", Wr)):
+        if W.shape != (A, d):
+            raise ValueError(f"autoint_layer: {name} must be [{A}, {d}], got {tuple(W.shape)}")
+    if br is not None and br.shape != (A,):
+        raise ValueError(f"autoint_layer: the residual bias must be [{A}], got {tuple(br.shape)}")
+    return N, F, d, A
+
+
+def autoint_layer_fwd(X, Wq, Wk, Wv, Wr, br, heads):
+    """rc_autoint_layer_fwd: Y [..., F, A] = relu(attention over the fields of one instance + X Wr^T + br), one launch"""
+    N, F, d, A = _autoint_shapes(X, Wq, Wk, Wv, Wr, br, heads)
+    f32 = torch.float32
+    Y = torch.empty(X.shape[:-1] + (A,), dtype=f32, device=X.device)
+    _lib.call("rc_autoint_layer_fwd", _ptr(X, f32, "X"), _ptr(Wq, f32, "Wq"), _ptr(Wk, f32, "Wk"), _ptr(Wv, f32, "Wv"),
+              _ptr(Wr, f32, "Wr"), _ptr(br, f32, "br"), N, F, d, A, int(heads), _ptr(Y, f32, "Y"), _stream())
+    return Y
+
+
+def autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, dY, heads, workspace=None):
+    """rc_autoint_layer_bwd -> (dX, dWq, dWk, dWv, dWr, dbr): Q, K, V and the softmax are recomputed from X; two launches"""
+    N, F, d, A = _autoint_shapes(X, Wq, Wk, Wv, Wr, None, heads)
+    if Y.shape != X.shape[:-1] + (A,) or dY.shape != Y.shape:
+        raise ValueError(f"autoint_layer_bwd: Y and dY must be {tuple(X.shape[:-1]) + (A,)}, got {tuple(Y.shape)} / {tuple(dY.shape)}")
+    dev, f32 = X.device, torch.float32
+    ws = (workspace if workspace is not None else AutoIntWorkspace()).get(N, F, d, A, heads, dev)
+    dX = torch.empty_like(X)
+    dWq, dWk, dWv, dWr = (torch.empty((A, d), dtype=f32, device=dev) for _ in range(4))
+    dbr = torch.empty(A, dtype=f32, device=dev)
+    _lib.call("rc_autoint_layer_bwd", _ptr(X, f32, "X"), _ptr(Wq, f32, "Wq"), _ptr(Wk, f32, "Wk"), _ptr(Wv, f32, "Wv"),
+              _ptr(Wr, f32, "Wr"), _ptr(Y, f32, "Y"), _ptr(dY, f32, "dY"), N, F, d, A, int(heads), C.c_void_p(ws.data_ptr()), ws.numel(),
+              _ptr(dX, f32, "dX"), _ptr(dWq, f32, "dWq"), _ptr(dWk, f32, "dWk"), _ptr(dWv, f32, "dWv"), _ptr(dWr, f32, "dWr"),
+              _ptr(dbr, f32, "dbr"), _stream())
+    return dX, dWq, dWk, dWv, dWr, dbr

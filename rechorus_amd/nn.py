@@ -256,6 +256,41 @@ def comirec_scores(item_w, pos_w, W1, b1, W2, b2, hist, lengths, item_id):
     return engine.comirec_score_max(interests, det[0], item_id.contiguous())
 
 
+class _AutoIntLayerFn(torch.autograd.Function):
+    """One AutoInt interacting layer (models/context/AutoInt.py:72-75) on rc_autoint_layer_fwd / _bwd.  Saves X and Y only: the
+    backward recomputes Q, K, V and the softmax.  No host synchronisation and no data-dependent allocation: capture-safe."""
+
+    @staticmethod
+    def forward(ctx, X, Wq, Wk, Wv, Wr, br, heads, workspace):
+        det = [t.detach().contiguous() for t in (X, Wq, Wk, Wv, Wr, br)]
+        Y = engine.autoint_layer_fwd(*det, heads)
+        ctx.save_for_backward(*det[:5], Y)
+        ctx.heads, ctx.workspace = heads, workspace
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, Wq, Wk, Wv, Wr, Y = ctx.saved_tensors
+        dX, dWq, dWk, dWv, dWr, dbr = engine.autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, dY.contiguous(), ctx.heads,
+                                                               workspace=ctx.workspace)
+        return dX, dWq, dWk, dWv, dWr, dbr, None, None
+
+
+def autoint_layer(X, Wq, Wk, Wv, Wr, br, heads, workspace=None):
+    """relu(MultiHeadAttention(X, X, X) + Linear(X)) over the fields of each instance (models/context/AutoInt.py:72-75): X [..., F,
+    Din], Wq / Wk / Wv / Wr [A, Din], br [A] -> [..., F, A], as ONE autograd node (one forward launch, one backward launch plus the
+    fixed-order reduce); workspace: the model's engine.AutoIntWorkspace, reused step after step"""
+    return _AutoIntLayerFn.apply(X, Wq, Wk, Wv, Wr, br, int(heads), workspace)
+
+
+def autoint_layer_eval(X, Wq, Wk, Wv, Wr, br, heads):
+    """the same layer on the evaluation path: forward only, raises when autograd is recording"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (X, Wq, Wk, Wv, Wr, br)):
+        raise RuntimeError("autoint_layer_eval is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through autoint_layer)")
+    return engine.autoint_layer_fwd(*[t.detach().contiguous() for t in (X, Wq, Wk, Wv, Wr, br)], int(heads))
+
+
 class _BuirLossFn(torch.autograd.Function):
     """BUIR's training step up to the loss (models/general/BUIR.py:73-110) on rc_buir_fwd / _bwd -> (loss, prediction [B, 1]).
     The prediction is marked non-differentiable: a loss built on it raises instead of training on nothing.  Backward: the forward
