@@ -1137,6 +1137,55 @@ int rc_autoint_layer_bwd(const float* X, const float* Wq, const float* Wk, const
                          void* workspace, size_t ws_bytes, float* dX, float* dWq, float* dWk, float* dWv, float* dWr, float* dbr,
                          rc_stream_t stream);
 
+/* ---- FinalMLP: feature gates + first stream layers, bilinear fusion (models/context/FinalMLP.py:141-249) --------------------------
+ * X [n_instances, D] are the flattened field vectors (D = fields * emb_size, n_instances = batch * candidates).  One stream:     */
+typedef struct rc_finalmlp_stream {
+  const float* Zin;      /* [n_gate_rows, G]: the input of the gate MLP's last Linear (FinalMLP.py:203,219)                      */
+  const float* Wg;       /* [D, G], bg [D]: that Linear; the gate is 2 sigmoid(Zin Wg^T + bg)                                     */
+  const float* bg;
+  const float* W;        /* [H, D], b [H]: the first Linear of the stream's MLP_Block (FinalMLP.py:100-101)                       */
+  const float* b;
+  const uint64_t* seed;  /* device seed of the dropout mask stream (as rc_linear_fwd); NULL with drop_p == 0                     */
+  int64_t n_gate_rows;   /* 1: every instance uses row 0; n_instances / n_cand: instance n uses row n / n_cand; n_instances       */
+  int G, H;
+  float drop_p;          /* dropout behind the first layer's ReLU, [0, 1)                                                         */
+  uint32_t site;         /* dropout site (rc_linear_fwd's convention), < 65536                                                    */
+} rc_finalmlp_stream;
+typedef struct rc_finalmlp_grads {
+  float *dZin, *dWg, *dbg, *dW, *db; /* shapes of Zin, Wg, bg, W, b */
+} rc_finalmlp_grads;
+/* RC_OK when 3 <= n_fields <= 32, emb_size % 4 == 0 in [4, 128], the gate inputs G, the first-layer widths H and the fusion's x_dim,
+ * y_dim are multiples of 4 in [4, 256], num_heads divides x_dim and y_dim, 0 <= dropout < 1, and a tile of 32 rows fits the 160 KiB
+ * of LDS (backward: G and H of ONE stream, each rounded up to 32, with 256 G + 272 H <= 122,880 -- e.g. not both 256); else
+ * RC_ERR_UNSUPPORTED with the reason in rc_last_error_string() (host logic, no GPU needed).                                        */
+int rc_finalmlp_check_shape(int n_fields, int emb_size, int gate_in_1, int first_1, int gate_in_2, int first_2, int x_dim, int y_dim,
+                            int num_heads, float drop_p_1, float drop_p_2);
+/* bytes of the caller workspace (256-byte aligned) of rc_finalmlp_gate_bwd: per-row-block partials of the weight gradients and, for
+ * a gate with more than one row, the per-slab shares of dZin [ceil(D / 32)][n_instances][G]; 0 outside the envelope               */
+size_t rc_finalmlp_gate_workspace_bytes(int64_t n_instances, int n_cand, int D, int gate_in_1, int first_1, int64_t gate_rows_1,
+                                        int gate_in_2, int first_2, int64_t gate_rows_2);
+/* FeatureSelection.forward (:188-221) from the gate's last Linear on, and the first Linear + ReLU + Dropout of mlp1 / mlp2 (:100-101),
+ * both streams in ONE launch: A_s [n_instances, H_s] = drop(relu((X * 2 sigmoid(Zin_s Wg_s^T + bg_s)) W_s^T + b_s)).  X is read once;
+ * neither the gate nor the gated features are written.  drop_p == 0 (evaluation): nothing is drawn.                               */
+int rc_finalmlp_gate_fwd(const float* X, int64_t n_instances, int n_cand, int D, const rc_finalmlp_stream* s1,
+                         const rc_finalmlp_stream* s2, float* A1, float* A2, rc_stream_t stream);
+/* its autograd from X, the forward's A_s (their own ReLU / dropout masks) and dA_s; the gates are recomputed.  dX is written once;
+ * three launches: the tile kernel, the fixed-order reduce of its partials, and the sums that finish dZin.                          */
+int rc_finalmlp_gate_bwd(const float* X, int64_t n_instances, int n_cand, int D, const rc_finalmlp_stream* s1,
+                         const rc_finalmlp_stream* s2, const float* A1, const float* dA1, const float* A2, const float* dA2,
+                         void* workspace, size_t ws_bytes, float* dX, const rc_finalmlp_grads* g1, const rc_finalmlp_grads* g2,
+                         rc_stream_t stream);
+/* InteractionAggregation.forward (:238-249) in ONE launch: out [n] = w_x x + b_x + w_y y + b_y + sum_h x_h^T W_h y_h with
+ * x [n, x_dim], y [n, y_dim], w_xy [num_heads * (x_dim / num_heads) * (y_dim / num_heads)] (the reference's [., 1] parameter), w_x
+ * [x_dim], w_y [y_dim], b_x, b_y [1] on the device.  Nothing is saved: the same call serves evaluation.                           */
+int rc_finalmlp_fusion_fwd(const float* x, const float* y, const float* w_xy, const float* w_x, const float* b_x, const float* w_y,
+                           const float* b_y, int64_t n_instances, int x_dim, int y_dim, int num_heads, float* out, rc_stream_t stream);
+size_t rc_finalmlp_fusion_workspace_bytes(int64_t n_instances, int x_dim, int y_dim, int num_heads);
+/* its autograd from dout [n]: one launch (x and y read once) + the fixed-order reduce of the per-workgroup partials */
+int rc_finalmlp_fusion_bwd(const float* x, const float* y, const float* w_xy, const float* w_x, const float* w_y, const float* dout,
+                           int64_t n_instances, int x_dim, int y_dim, int num_heads, void* workspace, size_t ws_bytes, float* dx,
+                           float* dy, float* dw_xy, float* dw_x, float* db_x, float* dw_y, float* db_y, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,21 @@ class LgcnGraph(C.Structure):
     ]
 
 
+class FinalMlpStream(C.Structure):
+    """struct rc_finalmlp_stream: one stream of the gated first layers; device pointers"""
+    _fields_ = [
+        ("Zin", C.c_void_p), ("Wg", C.c_void_p), ("bg", C.c_void_p), ("W", C.c_void_p), ("b", C.c_void_p), ("seed", C.c_void_p),
+        ("n_gate_rows", C.c_int64), ("G", C.c_int), ("H", C.c_int), ("drop_p", C.c_float), ("site", C.c_uint32),
+    ]
+
+
+class FinalMlpGrads(C.Structure):
+    """struct rc_finalmlp_grads"""
+    _fields_ = [("dZin", C.c_void_p), ("dWg", C.c_void_p), ("dbg", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p)]
+
+
+_fsp = C.POINTER(FinalMlpStream)
+_fgp = C.POINTER(FinalMlpGrads)
 _p = C.c_void_p
 _i = C.c_int
 _u64 = C.c_uint64
@@ -237,6 +252,13 @@ SIGNATURES = {
     "rc_autoint_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "rc_autoint_layer_fwd": (_i, [_p] * 6 + [_i64, _i, _i, _i, _i, _p, _p]),
     "rc_autoint_layer_bwd": (_i, [_p] * 7 + [_i64, _i, _i, _i, _i, _p, _sz] + [_p] * 6 + [_p]),
+    "rc_finalmlp_check_shape": (_i, [_i] * 9 + [_f, _f]),
+    "rc_finalmlp_gate_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i64, _i, _i, _i64]),
+    "rc_finalmlp_gate_fwd": (_i, [_p, _i64, _i, _i, _fsp, _fsp, _p, _p, _p]),
+    "rc_finalmlp_gate_bwd": (_i, [_p, _i64, _i, _i, _fsp, _fsp, _p, _p, _p, _p, _p, _sz, _p, _fgp, _fgp, _p]),
+    "rc_finalmlp_fusion_fwd": (_i, [_p] * 7 + [_i64, _i, _i, _i, _p, _p]),
+    "rc_finalmlp_fusion_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_finalmlp_fusion_bwd": (_i, [_p] * 6 + [_i64, _i, _i, _i, _p, _sz] + [_p] * 7 + [_p]),
 }
 
 _lib = None

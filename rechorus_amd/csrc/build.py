@@ -43,6 +43,7 @@ SOURCES = [
     "comirec.hip",
     "buir.hip",
     "autoint.hip",
+    "finalmlp.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -2800,3 +2800,147 @@ def autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, dY, heads, workspace=None):
               _ptr(dX, f32, "dX"), _ptr(dWq, f32, "dWq"), _ptr(dWk, f32, "dWk"), _ptr(dWv, f32, "dWv"), _ptr(dWr, f32, "dWr"),
               _ptr(dbr, f32, "dbr"), _stream())
     return dX, dWq, dWk, dWv, dWr, dbr
+
+
+# ---- FinalMLP: feature gates + first stream layers, bilinear fusion (models/context/FinalMLP.py:141-249) -------------------------------
+
+def finalmlp_check_shape(n_fields, emb_size, gate_in_1, first_1, gate_in_2, first_2, x_dim, y_dim, num_heads, drop_p_1=0.0, drop_p_2=0.0):
+    """rc_finalmlp_check_shape (host logic): 3 <= fields <= 32, emb_size % 4 == 0 in [4, 128], gate inputs / first-layer widths / stream
+    outputs multiples of 4 in [4, 256], num_heads a divisor of both stream outputs, dropout in [0, 1), a 32-row tile within the LDS;
+    raises ValueError with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_finalmlp_check_shape(int(n_fields), int(emb_size), int(gate_in_1), int(first_1), int(gate_in_2), int(first_2), int(x_dim),
+                                   int(y_dim), int(num_heads), float(drop_p_1), float(drop_p_2)) != _lib.RC_OK:
+        raise ValueError("FinalMLP on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def finalmlp_fusion_check_shape(x_dim, y_dim, num_heads):
+    """the fusion kernels' own envelope (what a model without the feature gates needs): stream outputs multiples of 4 in [4, 256],
+    num_heads a divisor of both; raises ValueError with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_finalmlp_fusion_workspace_bytes(1, int(x_dim), int(y_dim), int(num_heads)) == 0:
+        raise ValueError("FinalMLP on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class FinalMLPWorkspace:
+    """the scratch of rc_finalmlp_gate_bwd and rc_finalmlp_fusion_bwd (per-workgroup partials, the per-slab shares of dZin), one buffer
+    per call kind and shape that is never freed or moved while the owner lives: a captured training step replays on the same memory"""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, kind, key, device):
+        key = (kind,) + tuple(int(k) for k in key) + (torch.device(device),)
+        buf = self._bufs.get(key)
+        if buf is None:
+            fn = {"gate": "rc_finalmlp_gate_workspace_bytes", "fusion": "rc_finalmlp_fusion_workspace_bytes"}[kind]
+            nbytes = getattr(_lib.load(), fn)(*key[1:-1])
+            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return buf
+
+
+def _finalmlp_stream(X, n_cand, stream, which, need_seed=True):
+    """(struct rc_finalmlp_stream, shapes) of stream = (Zin, Wg, bg, W, b, drop_p, seed, site); every shape and dtype checked here"""
+    Zin, Wg, bg, W, b, drop_p, seed, site = stream
+    N, D = X.shape
+    f32 = torch.float32
+    if Zin.dim() != 2 or Zin.shape[0] not in (1, N // n_cand, N):
+        raise ValueError(f"finalmlp_gate: the gate input of stream {which} must be [1 | {N // n_cand} | {N}, G], got {tuple(Zin.shape)}")
+    G, H = Zin.shape[1], W.shape[0]
+    if Wg.shape != (D, G) or bg.shape != (D,):
+        raise ValueError(f"finalmlp_gate: the gate's last Linear of stream {which} must be [{D}, {G}] + [{D}], got {tuple(Wg.shape)} + {tuple(bg.shape)}")
+    if W.shape != (H, D) or b.shape != (H,):
+        raise ValueError(f"finalmlp_gate: the first layer of stream {which} must be [H, {D}] + [H], got {tuple(W.shape)} + {tuple(b.shape)}")
+    drop_p = float(drop_p)
+    if not 0.0 <= drop_p < 1.0 or (need_seed and drop_p > 0.0 and seed is None):
+        raise ValueError(f"finalmlp_gate: dropout p={drop_p} of stream {which} needs p in [0, 1) and a device seed")
+    st = _lib.FinalMlpStream(_ptr(Zin, f32, "Zin").value, _ptr(Wg, f32, "Wg").value, _ptr(bg, f32, "bg").value, _ptr(W, f32, "W").value,
+                             _ptr(b, f32, "b").value, _ptr(seed, torch.int64, "seed").value if (drop_p > 0.0 and need_seed) else None,
+                             Zin.shape[0], G, H, drop_p, int(site))
+    return st, G, H
+
+
+def _finalmlp_x(X, n_cand):
+    if X.dim() != 2 or X.shape[0] < 1 or n_cand < 1 or X.shape[0] % n_cand != 0:
+        raise ValueError(f"finalmlp_gate: X must be [instances, fields * emb_size] with whole candidate lists of {n_cand}, got {tuple(X.shape)}")
+    return X.shape
+
+
+def finalmlp_gate_fwd(X, n_cand, stream1, stream2):
+    """rc_finalmlp_gate_fwd -> (A1 [N, H1], A2 [N, H2]): A_s = drop(relu((X * 2 sigmoid(Zin_s Wg_s^T + bg_s)) W_s^T + b_s)), one launch.
+    stream = (Zin [1 | N / n_cand | N, G], Wg [D, G], bg [D], W [H, D], b [H], drop_p, seed | None, site)"""
+    N, D = _finalmlp_x(X, n_cand)
+    s1, _, H1 = _finalmlp_stream(X, n_cand, stream1, 1)
+    s2, _, H2 = _finalmlp_stream(X, n_cand, stream2, 2)
+    f32 = torch.float32
+    A1 = torch.empty((N, H1), dtype=f32, device=X.device)
+    A2 = torch.empty((N, H2), dtype=f32, device=X.device)
+    _lib.call("rc_finalmlp_gate_fwd", _ptr(X, f32, "X"), N, int(n_cand), D, C.byref(s1), C.byref(s2), _ptr(A1, f32, "A1"),
+              _ptr(A2, f32, "A2"), _stream())
+    return A1, A2
+
+
+def finalmlp_gate_bwd(X, n_cand, stream1, stream2, A1, dA1, A2, dA2, workspace=None):
+    """rc_finalmlp_gate_bwd -> (dX, (dZin, dWg, dbg, dW, db) of stream 1, the same of stream 2); the gates are recomputed"""
+    N, D = _finalmlp_x(X, n_cand)
+    s1, G1, H1 = _finalmlp_stream(X, n_cand, stream1, 1, need_seed=False)      # (the saved A is the mask: nothing is drawn)
+    s2, G2, H2 = _finalmlp_stream(X, n_cand, stream2, 2, need_seed=False)
+    for name, t, H in (("A1", A1, H1), ("dA1", dA1, H1), ("A2", A2, H2), ("dA2", dA2, H2)):
+        if t.shape != (N, H):
+            raise ValueError(f"finalmlp_gate_bwd: {name} must be [{N}, {H}], got {tuple(t.shape)}")
+    dev, f32 = X.device, torch.float32
+    ws = (workspace if workspace is not None else FinalMLPWorkspace()).get(
+        "gate", (N, n_cand, D, G1, H1, stream1[0].shape[0], G2, H2, stream2[0].shape[0]), dev)
+    dX = torch.empty_like(X)
+    grads, structs = [], []
+    for stream in (stream1, stream2):
+        g = tuple(torch.empty_like(t) for t in stream[:5])
+        grads.append(g)
+        structs.append(_lib.FinalMlpGrads(*[_ptr(t, f32, "grad").value for t in g]))
+    _lib.call("rc_finalmlp_gate_bwd", _ptr(X, f32, "X"), N, int(n_cand), D, C.byref(s1), C.byref(s2), _ptr(A1, f32, "A1"),
+              _ptr(dA1, f32, "dA1"), _ptr(A2, f32, "A2"), _ptr(dA2, f32, "dA2"), C.c_void_p(ws.data_ptr()), ws.numel(),
+              _ptr(dX, f32, "dX"), C.byref(structs[0]), C.byref(structs[1]), _stream())
+    return dX, grads[0], grads[1]
+
+
+def _finalmlp_fusion_shapes(x, y, w_xy, w_x, w_y, heads):
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0] or x.shape[0] < 1:
+        raise ValueError(f"finalmlp_fusion: x and y must be [instances, width] with the same instances, got {tuple(x.shape)} / {tuple(y.shape)}")
+    N, H1 = x.shape
+    H2 = y.shape[1]
+    lib = _lib.load()
+    if lib.rc_finalmlp_fusion_workspace_bytes(N, H1, H2, int(heads)) == 0:
+        raise ValueError("FinalMLP on the HIP engine: " + lib.rc_last_error_string().decode())
+    if w_xy.numel() != H1 * H2 // heads or w_x.numel() != H1 or w_y.numel() != H2:
+        raise ValueError(f"finalmlp_fusion: w_xy / w_x / w_y must hold {H1 * H2 // heads} / {H1} / {H2} elements, got {w_xy.numel()} / "
+                         f"{w_x.numel()} / {w_y.numel()}")
+    return N, H1, H2
+
+
+def finalmlp_fusion_fwd(x, y, w_xy, w_x, b_x, w_y, b_y, heads):
+    """rc_finalmlp_fusion_fwd -> out [N] = w_x x + b_x + w_y y + b_y + sum_h x_h^T W_h y_h, one launch, nothing saved"""
+    N, H1, H2 = _finalmlp_fusion_shapes(x, y, w_xy, w_x, w_y, heads)
+    if b_x.numel() != 1 or b_y.numel() != 1:
+        raise ValueError("finalmlp_fusion: b_x and b_y hold one element each")
+    f32 = torch.float32
+    out = torch.empty(N, dtype=f32, device=x.device)
+    _lib.call("rc_finalmlp_fusion_fwd", _ptr(x, f32, "x"), _ptr(y, f32, "y"), _ptr(w_xy, f32, "w_xy"), _ptr(w_x, f32, "w_x"),
+              _ptr(b_x, f32, "b_x"), _ptr(w_y, f32, "w_y"), _ptr(b_y, f32, "b_y"), N, H1, H2, int(heads), _ptr(out, f32, "out"), _stream())
+    return out
+
+
+def finalmlp_fusion_bwd(x, y, w_xy, w_x, w_y, dout, heads, workspace=None):
+    """rc_finalmlp_fusion_bwd -> (dx, dy, dw_xy, dw_x, db_x, dw_y, db_y), shaped like their parameters (biases [1])"""
+    N, H1, H2 = _finalmlp_fusion_shapes(x, y, w_xy, w_x, w_y, heads)
+    if dout.shape != (N,):
+        raise ValueError(f"finalmlp_fusion_bwd: dout must be [{N}], got {tuple(dout.shape)}")
+    dev, f32 = x.device, torch.float32
+    ws = (workspace if workspace is not None else FinalMLPWorkspace()).get("fusion", (N, H1, H2, heads), dev)
+    dx, dy = torch.empty_like(x), torch.empty_like(y)
+    dw_xy, dw_x, dw_y = torch.empty_like(w_xy), torch.empty_like(w_x), torch.empty_like(w_y)
+    db_x, db_y = torch.empty(1, dtype=f32, device=dev), torch.empty(1, dtype=f32, device=dev)
+    _lib.call("rc_finalmlp_fusion_bwd", _ptr(x, f32, "x"), _ptr(y, f32, "y"), _ptr(w_xy, f32, "w_xy"), _ptr(w_x, f32, "w_x"),
+              _ptr(w_y, f32, "w_y"), _ptr(dout, f32, "dout"), N, H1, H2, int(heads), C.c_void_p(ws.data_ptr()), ws.numel(),
+              _ptr(dx, f32, "dx"), _ptr(dy, f32, "dy"), _ptr(dw_xy, f32, "dw_xy"), _ptr(dw_x, f32, "dw_x"), _ptr(db_x, f32, "db_x"),
+              _ptr(dw_y, f32, "dw_y"), _ptr(db_y, f32, "db_y"), _stream())
+    return dx, dy, dw_xy, dw_x, db_x, dw_y, db_y

@@ -291,6 +291,100 @@ def autoint_layer_eval(X, Wq, Wk, Wv, Wr, br, heads):
     return engine.autoint_layer_fwd(*[t.detach().contiguous() for t in (X, Wq, Wk, Wv, Wr, br)], int(heads))
 
 
+class _FinalMlpGateFn(torch.autograd.Function):
+    """FinalMLP's feature gates and the first layer of both streams (models/context/FinalMLP.py:188-221, :100-101) on
+    rc_finalmlp_gate_fwd / _bwd.  Saves X, the gate inputs, the weights and A_1, A_2 (their own ReLU / dropout masks): the gates are
+    recomputed, nothing of size N D is kept.  No host synchronisation and no data-dependent allocation: capture-safe."""
+
+    @staticmethod
+    def forward(ctx, X, n_cand, opts, workspace, Zin1, Wg1, bg1, W1, b1, Zin2, Wg2, bg2, W2, b2):
+        det = [t.detach().contiguous() for t in (X, Zin1, Wg1, bg1, W1, b1, Zin2, Wg2, bg2, W2, b2)]
+        Xf = det[0].reshape(-1, det[0].shape[-1])
+        (p1, seed1, site1), (p2, seed2, site2) = opts
+        A1, A2 = engine.finalmlp_gate_fwd(Xf, n_cand, (*det[1:6], p1, seed1, site1), (*det[6:11], p2, seed2, site2))
+        ctx.save_for_backward(Xf, *det[1:], A1, A2)
+        ctx.n_cand, ctx.opts, ctx.workspace, ctx.xshape = n_cand, opts, workspace, X.shape
+        return A1, A2
+
+    @staticmethod
+    def backward(ctx, dA1, dA2):
+        Xf, *par, A1, A2 = ctx.saved_tensors
+        (p1, _, site1), (p2, _, site2) = ctx.opts
+        # (the mask is the saved output: the backward draws nothing, so it takes no seed)
+        dA1 = torch.zeros_like(A1) if dA1 is None else dA1.contiguous()
+        dA2 = torch.zeros_like(A2) if dA2 is None else dA2.contiguous()
+        dX, g1, g2 = engine.finalmlp_gate_bwd(Xf, ctx.n_cand, (*par[0:5], p1, None, site1), (*par[5:10], p2, None, site2), A1, dA1, A2, dA2,
+                                              workspace=ctx.workspace)
+        return (dX.view(ctx.xshape), None, None, None) + tuple(g1) + tuple(g2)
+
+
+def _finalmlp_opts(stream):
+    p, seed, site = (tuple(stream[5:]) + (0.0, None, 0)[len(stream) - 5:])
+    return (float(p), seed if float(p) > 0.0 else None, int(site))
+
+
+def finalmlp_gate(X, n_cand, stream1, stream2, workspace=None):
+    """(A_1 [N, H_1], A_2 [N, H_2]) with A_s = drop(relu((X * 2 sigmoid(Zin_s Wg_s^T + bg_s)) W_s^T + b_s)): the last Linear + Sigmoid of
+    both gate MLPs, the products with the flattened field vectors X [..., D] and the first Linear + ReLU + Dropout of mlp1 / mlp2
+    (models/context/FinalMLP.py:203-220, :100-101) as ONE autograd node (one forward launch; backward: tile kernel, reduce, dZin).
+    stream = (Zin [1 | B | N, G], Wg [D, G], bg [D], W [H, D], b [H][, drop_p, seed, site]); workspace: the model's
+    engine.FinalMLPWorkspace, reused step after step"""
+    if not X.is_cuda:
+        raise RuntimeError("finalmlp_gate runs on the GPU only (no CPU path)")
+    return _FinalMlpGateFn.apply(X, int(n_cand), (_finalmlp_opts(stream1), _finalmlp_opts(stream2)), workspace, *stream1[:5], *stream2[:5])
+
+
+def finalmlp_gate_eval(X, n_cand, stream1, stream2):
+    """the same on the evaluation path: forward only, no dropout, raises when autograd is recording"""
+    ts = (X,) + tuple(stream1[:5]) + tuple(stream2[:5])
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise RuntimeError("finalmlp_gate_eval is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through finalmlp_gate)")
+    det = [t.detach().contiguous() for t in ts]
+    return engine.finalmlp_gate_fwd(det[0].reshape(-1, det[0].shape[-1]), int(n_cand), (*det[1:6], 0.0, None, 0), (*det[6:11], 0.0, None, 0))
+
+
+class _FinalMlpFusionFn(torch.autograd.Function):
+    """FinalMLP's bilinear fusion (models/context/FinalMLP.py:238-249) on rc_finalmlp_fusion_fwd / _bwd; saves its inputs only.
+    Capture-safe."""
+
+    @staticmethod
+    def forward(ctx, x, y, w_xy, w_x, b_x, w_y, b_y, heads, workspace):
+        det = [t.detach().contiguous() for t in (x, y, w_xy, w_x, b_x, w_y, b_y)]
+        xf, yf = det[0].reshape(-1, det[0].shape[-1]), det[1].reshape(-1, det[1].shape[-1])
+        out = engine.finalmlp_fusion_fwd(xf, yf, *det[2:], heads)
+        ctx.save_for_backward(xf, yf, det[2], det[3], det[5])
+        ctx.heads, ctx.workspace, ctx.shapes = heads, workspace, (x.shape, y.shape)
+        return out.view(x.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        xf, yf, w_xy, w_x, w_y = ctx.saved_tensors
+        dx, dy, dw_xy, dw_x, db_x, dw_y, db_y = engine.finalmlp_fusion_bwd(xf, yf, w_xy, w_x, w_y, dout.contiguous().view(-1), ctx.heads,
+                                                                          workspace=ctx.workspace)
+        return dx.view(ctx.shapes[0]), dy.view(ctx.shapes[1]), dw_xy, dw_x, db_x, dw_y, db_y, None, None
+
+
+def finalmlp_fusion(x, y, w_xy, w_x, b_x, w_y, b_y, heads, workspace=None):
+    """w_x x + b_x + w_y y + b_y + sum_h x_h^T W_h y_h (models/context/FinalMLP.py:238-249): x [..., H1], y [..., H2], w_xy the
+    reference's [heads * (H1 / heads) * (H2 / heads), 1] parameter, w_x [1, H1], w_y [1, H2], b_x, b_y [1] -> [...], ONE autograd node
+    (one forward launch, one backward launch plus the fixed-order reduce)"""
+    if not x.is_cuda:
+        raise RuntimeError("finalmlp_fusion runs on the GPU only (no CPU path)")
+    return _FinalMlpFusionFn.apply(x, y, w_xy, w_x, b_x, w_y, b_y, int(heads), workspace)
+
+
+def finalmlp_fusion_eval(x, y, w_xy, w_x, b_x, w_y, b_y, heads):
+    """the same on the evaluation path: forward only, raises when autograd is recording"""
+    ts = (x, y, w_xy, w_x, b_x, w_y, b_y)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise RuntimeError("finalmlp_fusion_eval is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through finalmlp_fusion)")
+    det = [t.detach().contiguous() for t in ts]
+    out = engine.finalmlp_fusion_fwd(det[0].reshape(-1, x.shape[-1]), det[1].reshape(-1, y.shape[-1]), *det[2:], int(heads))
+    return out.view(x.shape[:-1])
+
+
 class _BuirLossFn(torch.autograd.Function):
     """BUIR's training step up to the loss (models/general/BUIR.py:73-110) on rc_buir_fwd / _bwd -> (loss, prediction [B, 1]).
     The prediction is marked non-differentiable: a loss built on it raises instead of training on nothing.  Backward: the forward
@@ -496,6 +590,51 @@ class _FieldGatherFn(torch.autograd.Function):
 def gather_fields(tables, ids, n_cand):
     """tables: F HipEmbedding weights of equal width; ids: F int64 tensors ([B] or [B, C])"""
     return _FieldGatherFn.apply(n_cand, len(tables), *ids, *tables)
+
+
+class _FieldGatherKindsFn(torch.autograd.Function):
+    """ONE table family with numeric fields among the categorical ones (models/context/FinalMLP.py:57-60,79-92: `embedding_dict`
+    holds nn.Embedding and Linear(1, d, bias=False) side by side): the same gather launch as the pair's (rc_gather_fields' kinds,
+    no second family); backward, one sort of the composite keys with the numeric occurrences behind every row + one segmented sum,
+    and rc_numeric_field_grads on gV alone for the Linear weights."""
+
+    @staticmethod
+    def forward(ctx, n_cand, n_fields, kinds, *args):
+        ids = [x.contiguous() for x in args[:n_fields]]
+        tables = args[n_fields:]
+        cat = [f for f in range(n_fields) if kinds[f] == engine.FIELD_IDS]
+        num = [f for f in range(n_fields) if kinds[f] != engine.FIELD_IDS]
+        n_rows = sum(tables[f].shape[0] for f in cat)
+        res = engine.gather_fields([t.detach() for t in tables], ids, n_cand, want_cid=True, kinds=kinds, numeric_key=n_rows)
+        ctx.cid, ctx.offs, ctx.kinds, ctx.num, ctx.n_cand = res.cid, res.offsets, kinds, num, n_cand
+        ctx.values = [ids[f] for f in num]
+        return res.out
+
+    @staticmethod
+    def backward(ctx, gV):
+        offs, num, F = ctx.offs, ctx.num, len(ctx.kinds)
+        n_rows, n = offs[-1], ctx.cid.numel()
+        gV = gV.contiguous()
+        d = gV.shape[-1]
+        gw, _ = engine.numeric_field_grads(gV.view(n // F, F, d), None, ctx.values, num, F, ctx.n_cand, d)
+        G = None
+        if n_rows > 0:
+            keys, perm = engine.sort_ids(ctx.cid.reshape(-1), n_rows + 1)
+            n_cat = (n // F) * (F - len(num))
+            G = engine.embedding_dense_backward(gV, ctx.cid, n_rows, route="sort", presorted=(keys[:n_cat], perm[:n_cat]))
+        grads = [None if ctx.kinds[f] != engine.FIELD_IDS else G[offs[f]:offs[f + 1]] for f in range(F)]
+        for j, f in enumerate(num):
+            grads[f] = gw[j]
+        return (None, None, None) + (None,) * F + tuple(grads)
+
+
+def gather_fields_kinds(tables, ids, n_cand, kinds=None):
+    """gather_fields for ONE table family that may hold numeric fields: kinds[f] is engine.FIELD_IDS (tables[f] a [vocab, d] table
+    looked up by ids[f]) or the value type of a numeric field (engine.field_kind; tables[f] the Linear(1, d, bias=False) weight
+    [d, 1], ids[f] the feature's values).  kinds None / all ids: exactly gather_fields"""
+    if kinds is None or all(k == engine.FIELD_IDS for k in kinds):
+        return gather_fields(tables, ids, n_cand)
+    return _FieldGatherKindsFn.apply(n_cand, len(tables), tuple(int(k) for k in kinds), *ids, *tables)
 
 
 class _FieldGatherPairFn(torch.autograd.Function):
