@@ -1069,6 +1069,42 @@ int rc_comirec_bwd(const float* item_tab, int64_t n_items, const float* pos_tab,
 int rc_comirec_score_max(const float* interests, const float* item_tab, int64_t n_items, const int64_t* iid, int64_t batch, int64_t C,
                          int d, int K, float* pred, rc_stream_t stream);
 
+/* ---- ContraRec: context-context contrastive loss (models/sequential/ContraRec.py:142-193) and the forward-indexed position
+ * embedding of its BERT4Rec encoder (:259-267) -----------------------------------------------------------------------------------
+ * va, vb [batch, d]: the two augmented views' encoder outputs, un-normalised (the F.normalize of :92 is part of the kernels).  They
+ * are stacked view-major as :167 does: rows 0..batch-1 view a, batch..2 batch-1 view b, N = 2 batch.  z_r = x_r / max(|x_r|,
+ * 1e-12), l_rc = z_r . z_c / temperature (:170), pos_rc = [labels[r mod batch] == labels[c mod batch]] and c != r (:164,176-182;
+ * labels NULL: only the other view of the same sample, :159), m_r = max_c l_rc with the diagonal (:172),
+ * D_r = sum_{c != r} exp(l_rc - m_r) + 1e-10 (:185-186), P_r = sum_c pos_rc, A_r = sum_c pos_rc l_rc,
+ * loss = -(temperature / N) sum_r (A_r - P_r (m_r + log D_r)) / (P_r + 1e-10) (:189-193).
+ * Two owner-computes sweeps on fp32 MFMA, the N x N matrix is never stored; large N is split into column chunks combined in
+ * chunk order.  No float atomics: every sum has a fixed order, reruns are bitwise identical.
+ * RC_OK when d % 4 == 0, 4 <= d <= 256 and 1 <= batch <= 2^19, else RC_ERR_UNSUPPORTED with the reason in rc_last_error_string()
+ * (host logic, no GPU needed); the entry points below check the same envelope themselves.                                      */
+int rc_contra_check_shape(int d, int64_t batch);
+/* bytes of the caller workspace (256-byte aligned) for this shape; 0 outside the envelope */
+size_t rc_contra_workspace_bytes(int d, int64_t batch);
+/* forward (:148-193 behind the F.normalize of :92): loss [1] (device).  labels [batch] int64 or NULL.  The workspace keeps what the
+ * backward pass reads (z, the row norms, m + log D, 1 / (P + 1e-10), P / (P + 1e-10)): do not reuse it for another forward before
+ * that.                                                                                                                          */
+int rc_contra_loss_fwd(const float* va, const float* vb, const int64_t* labels, int64_t batch, int d, float temperature,
+                       void* workspace, size_t ws_bytes, float* loss, rc_stream_t stream);
+/* autograd of :92,148-193 from grad_out [1] (device), the upstream gradient of the loss (the maximum is detached, :173):
+ * dz_r = -(grad_out / N) sum_{c != r} [pos_rc (a_r + a_c) - b_r p_rc - b_c p_cr] z_c with a = 1 / (P + 1e-10), b = P a,
+ * p_rc = exp(l_rc - m_r) / D_r, mapped back through F.normalize -> grad_va, grad_vb [batch, d].  Same labels, temperature and
+ * workspace as the forward call.                                                                                                 */
+int rc_contra_loss_bwd(const float* grad_out, const int64_t* labels, int64_t batch, int d, float temperature, void* workspace,
+                       size_t ws_bytes, float* grad_va, float* grad_vb, rc_stream_t stream);
+/* BERT4RecEncoder's embedding (:259-267): X [B * L, d], X[b, i] = item_emb[hist[b, i]] + pos_emb[i] on valid rows (i < len_b), 0 on
+ * the padding (the reference adds pos_emb[0] there, hides those rows as keys and zeroes them at :273: every valid row agrees).
+ * rc_seq_embed_fwd is the same with position id len_b - i.                                                                       */
+int rc_seq_embed_fwdpos_fwd(const float* item_emb, const float* pos_emb, const int64_t* hist, const int64_t* lengths, int64_t B,
+                            int L, int d, float* X, rc_stream_t stream);
+/* its position-table gradient (autograd's embedding backward behind :266): grad_pos [n_pos, d], grad_pos[p] = sum_b dX[b, p] over
+ * the sequences with len_b > p in ascending b, zeros for p >= L.  rc_seq_pos_grad is the same for position id len_b - i.         */
+int rc_seq_pos_grad_fwdpos(const float* dX, const int64_t* lengths, int64_t B, int L, int d, int n_pos, float* grad_pos,
+                           rc_stream_t stream);
+
 /* ---- BUIR bootstrap loss, evaluation head and target update (models/general/BUIR.py:66-110, helpers/BUIRRunner.py:35-36) ----------
  * P = nn.Linear(d, d) with W [d, d] (out x in) and b; uo / io = user_online[uid[b]] / item_online[iid[b]], ut / it the same rows of
  * the target tables; n(x) = F.normalize(x) = x / max(|x|, 1e-12); pu = W uo + b, pi = W io + b (:83-88);

@@ -248,6 +248,12 @@ SIGNATURES = {
     "rc_comirec_fwd": (_i, [_p, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "rc_comirec_bwd": (_i, [_p, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i] + [_p] * 6 + [_p, _sz, _p]),
     "rc_comirec_score_max": (_i, [_p, _p, _i64, _p, _i64, _i64, _i, _i, _p, _p]),
+    "rc_contra_check_shape": (_i, [_i, _i64]),
+    "rc_contra_workspace_bytes": (_sz, [_i, _i64]),
+    "rc_contra_loss_fwd": (_i, [_p, _p, _p, _i64, _i, _f, _p, _sz, _p, _p]),
+    "rc_contra_loss_bwd": (_i, [_p, _p, _i64, _i, _f, _p, _sz, _p, _p, _p]),
+    "rc_seq_embed_fwdpos_fwd": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p]),
+    "rc_seq_pos_grad_fwdpos": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p]),
     "rc_autoint_check_shape": (_i, [_i, _i, _i, _i]),
     "rc_autoint_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "rc_autoint_layer_fwd": (_i, [_p] * 6 + [_i64, _i, _i, _i, _i, _p, _p]),

@@ -41,6 +41,7 @@ SOURCES = [
     "lgcn.hip",
     "directau.hip",
     "comirec.hip",
+    "contrarec.hip",
     "buir.hip",
     "autoint.hip",
     "finalmlp.hip",

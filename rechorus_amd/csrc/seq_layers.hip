@@ -60,7 +60,8 @@ __global__ __launch_bounds__(1024) void seq_offsets_kernel(const int64_t* __rest
 }
 
 // ---- X[b, i, :] = item_emb[hist[b, i]] + pos_emb[len_b - i] on valid rows, 0 elsewhere (SASRec.py:58-66) ---------------------
-template <int VEC>
+// FWDPOS: position id i instead of len_b - i (ContraRec.py:259-267, BERT4RecEncoder)
+template <int VEC, bool FWDPOS>
 __global__ __launch_bounds__(kBlock) void seq_embed_kernel(const float* __restrict__ item_emb, const float* __restrict__ pos_emb,
                                                            const int64_t* __restrict__ hist, const int64_t* __restrict__ lengths,
                                                            int64_t B, int L, int d, float* __restrict__ X) {
@@ -73,16 +74,17 @@ __global__ __launch_bounds__(kBlock) void seq_embed_kernel(const float* __restri
     const int i = (int)(row - b * L);
     const int64_t len = lengths[b];
     const bool valid = i < len;
+    const int64_t pid = FWDPOS ? (int64_t)i : len - i;
     if (VEC == 4) {
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (valid) {
         const float4 a = reinterpret_cast<const float4*>(item_emb)[hist[row] * dq + q];
-        const float4 p = reinterpret_cast<const float4*>(pos_emb)[(len - i) * dq + q];
+        const float4 p = reinterpret_cast<const float4*>(pos_emb)[pid * dq + q];
         v = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
       }
       reinterpret_cast<float4*>(X)[e] = v;
     } else {
-      X[e] = valid ? item_emb[hist[row] * dq + q] + pos_emb[(len - i) * dq + q] : 0.f;
+      X[e] = valid ? item_emb[hist[row] * dq + q] + pos_emb[pid * dq + q] : 0.f;
     }
   }
 }
@@ -115,7 +117,8 @@ __global__ __launch_bounds__(kBlock) void seq_pick_last_bwd_kernel(const float* 
 // ---- gradient of the position table: grad_pos[p] = sum_b dX[b, len_b - p] over the sequences with min(len_b, L) >= p ----------
 // (SASRec.py:64: position id = length - index on valid rows; autograd's embedding backward behind it.)  One workgroup per
 // position, lane-groups stride over the sequences in ascending order and are combined in a fixed order: any row width.
-template <int VEC>
+// FWDPOS (position id = index, ContraRec.py:265-266): grad_pos[p] = sum_b dX[b, p] over the sequences with len_b > p, p < L.
+template <int VEC, bool FWDPOS>
 __global__ __launch_bounds__(kBlock) void seq_pos_grad_kernel(const float* __restrict__ dX, const int64_t* __restrict__ lengths, int64_t B,
                                                               int L, int d, int n_pos, float* __restrict__ grad_pos) {
   __shared__ float red[kBlock * VEC];
@@ -129,12 +132,12 @@ __global__ __launch_bounds__(kBlock) void seq_pos_grad_kernel(const float* __res
     float acc[VEC];
 #pragma unroll
     for (int c = 0; c < VEC; ++c) acc[c] = 0.f;
-    if (rs < slots && p >= 1 && p <= L) {
+    if (rs < slots && (FWDPOS ? p < L : (p >= 1 && p <= L))) {
       for (int64_t b = rs; b < B; b += slots) {
         int64_t len = lengths[b];
         len = len > L ? L : len;
-        if (len >= p) {
-          const float* src = dX + ((size_t)b * L + (size_t)(len - p)) * d + (size_t)cq * VEC;
+        if (FWDPOS ? len > p : len >= p) {
+          const float* src = dX + ((size_t)b * L + (size_t)(FWDPOS ? p : len - p)) * d + (size_t)cq * VEC;
           if (VEC == 4) {
             const float4 t = *reinterpret_cast<const float4*>(src);
             acc[0] += t.x; acc[1 % VEC] += t.y; acc[2 % VEC] += t.z; acc[3 % VEC] += t.w;
@@ -619,22 +622,33 @@ extern "C" int rc_seq_offsets(const int64_t* lengths, int64_t B, int L, int32_t*
   return RC_OK;
 }
 
-extern "C" int rc_seq_embed_fwd(const float* item_emb, const float* pos_emb, const int64_t* hist, const int64_t* lengths, int64_t B,
-                                int L, int d, float* X, rc_stream_t stream) {
+template <bool FWDPOS>
+static int seq_embed_launch(const char* fn, const float* item_emb, const float* pos_emb, const int64_t* hist, const int64_t* lengths,
+                            int64_t B, int L, int d, float* X, rc_stream_t stream) {
   if (B == 0) return RC_OK;
-  RC_REQUIRE(item_emb && pos_emb && hist && lengths && X, "rc_seq_embed_fwd: null pointer");
-  RC_REQUIRE(B > 0 && L >= 1 && d >= 1, "rc_seq_embed_fwd: bad shape B=%lld L=%d d=%d", (long long)B, L, d);
+  RC_REQUIRE(item_emb && pos_emb && hist && lengths && X, "%s: null pointer", fn);
+  RC_REQUIRE(B > 0 && L >= 1 && d >= 1, "%s: bad shape B=%lld L=%d d=%d", fn, (long long)B, L, d);
   const bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(item_emb) % 16 == 0 && reinterpret_cast<uintptr_t>(pos_emb) % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(X) % 16 == 0;
   const int64_t total = B * L * (vec ? d / 4 : d);
   int64_t blocks = (total + kBlock - 1) / kBlock;
   if (blocks > 256 * 32) blocks = 256 * 32;
   if (vec)
-    hipLaunchKernelGGL((seq_embed_kernel<4>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), item_emb, pos_emb, hist, lengths, B, L, d, X);
+    hipLaunchKernelGGL((seq_embed_kernel<4, FWDPOS>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), item_emb, pos_emb, hist, lengths, B, L, d, X);
   else
-    hipLaunchKernelGGL((seq_embed_kernel<1>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), item_emb, pos_emb, hist, lengths, B, L, d, X);
+    hipLaunchKernelGGL((seq_embed_kernel<1, FWDPOS>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), item_emb, pos_emb, hist, lengths, B, L, d, X);
   RC_LAUNCH_CHECK();
   return RC_OK;
+}
+
+extern "C" int rc_seq_embed_fwd(const float* item_emb, const float* pos_emb, const int64_t* hist, const int64_t* lengths, int64_t B,
+                                int L, int d, float* X, rc_stream_t stream) {
+  return seq_embed_launch<false>("rc_seq_embed_fwd", item_emb, pos_emb, hist, lengths, B, L, d, X, stream);
+}
+
+extern "C" int rc_seq_embed_fwdpos_fwd(const float* item_emb, const float* pos_emb, const int64_t* hist, const int64_t* lengths,
+                                       int64_t B, int L, int d, float* X, rc_stream_t stream) {
+  return seq_embed_launch<true>("rc_seq_embed_fwdpos_fwd", item_emb, pos_emb, hist, lengths, B, L, d, X, stream);
 }
 
 extern "C" int rc_seq_pick_last_fwd(const float* X, const int64_t* lengths, int64_t B, int L, int d, float* hv, rc_stream_t stream) {
@@ -659,16 +673,27 @@ extern "C" int rc_seq_pick_last_bwd(const float* dhv, const int64_t* lengths, in
   return RC_OK;
 }
 
-extern "C" int rc_seq_pos_grad(const float* dX, const int64_t* lengths, int64_t B, int L, int d, int n_pos, float* grad_pos, rc_stream_t stream) {
-  RC_REQUIRE(grad_pos && n_pos >= 1 && L >= 1 && d >= 1 && B >= 0, "rc_seq_pos_grad: bad arguments (n_pos=%d, L=%d, d=%d)", n_pos, L, d);
-  RC_REQUIRE(B == 0 || (dX && lengths), "rc_seq_pos_grad: null pointer");
+template <bool FWDPOS>
+static int seq_pos_grad_launch(const char* fn, const float* dX, const int64_t* lengths, int64_t B, int L, int d, int n_pos,
+                               float* grad_pos, rc_stream_t stream) {
+  RC_REQUIRE(grad_pos && n_pos >= 1 && L >= 1 && d >= 1 && B >= 0, "%s: bad arguments (n_pos=%d, L=%d, d=%d)", fn, n_pos, L, d);
+  RC_REQUIRE(B == 0 || (dX && lengths), "%s: null pointer", fn);
   const bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(dX) % 16 == 0;
   if (vec)
-    hipLaunchKernelGGL((seq_pos_grad_kernel<4>), dim3((unsigned)n_pos), dim3(kBlock), 0, as_stream(stream), dX, lengths, B, L, d, n_pos, grad_pos);
+    hipLaunchKernelGGL((seq_pos_grad_kernel<4, FWDPOS>), dim3((unsigned)n_pos), dim3(kBlock), 0, as_stream(stream), dX, lengths, B, L, d, n_pos, grad_pos);
   else
-    hipLaunchKernelGGL((seq_pos_grad_kernel<1>), dim3((unsigned)n_pos), dim3(kBlock), 0, as_stream(stream), dX, lengths, B, L, d, n_pos, grad_pos);
+    hipLaunchKernelGGL((seq_pos_grad_kernel<1, FWDPOS>), dim3((unsigned)n_pos), dim3(kBlock), 0, as_stream(stream), dX, lengths, B, L, d, n_pos, grad_pos);
   RC_LAUNCH_CHECK();
   return RC_OK;
+}
+
+extern "C" int rc_seq_pos_grad(const float* dX, const int64_t* lengths, int64_t B, int L, int d, int n_pos, float* grad_pos, rc_stream_t stream) {
+  return seq_pos_grad_launch<false>("rc_seq_pos_grad", dX, lengths, B, L, d, n_pos, grad_pos, stream);
+}
+
+extern "C" int rc_seq_pos_grad_fwdpos(const float* dX, const int64_t* lengths, int64_t B, int L, int d, int n_pos, float* grad_pos,
+                                      rc_stream_t stream) {
+  return seq_pos_grad_launch<true>("rc_seq_pos_grad_fwdpos", dX, lengths, B, L, d, n_pos, grad_pos, stream);
 }
 
 extern "C" int rc_seq_attention_supported(int L, int dk) { return (L >= 1 && L <= kSeqMaxL && dk >= 1 && dk <= kSeqMaxDk) ? 1 : 0; }

@@ -2612,6 +2612,116 @@ def comirec_score_max(interests, item_emb, iid):
     return pred
 
 
+# ---- ContraRec: contrastive loss, forward-indexed position embedding (models/sequential/ContraRec.py:142-193, :259-267) -----------
+
+def contra_check_shape(d, batch=1):
+    """rc_contra_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 1 <= batch <= 2^19; raises ValueError with the library's
+    reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_contra_check_shape(int(d), int(batch)) != _lib.RC_OK:
+        raise ValueError("ContraRec on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def contra_layout(d, batch):
+    """(column chunks, 32-row column blocks per chunk, workspace bytes) of the two sweeps at this shape: the host-side statement of
+    con_layout in csrc/contrarec.hip (tests pin the byte count to rc_contra_workspace_bytes).  The sweep over the N = 2 batch stacked
+    rows is split so that about 512 workgroups run: at most 16 chunks, at most one per column block."""
+    N = 2 * int(batch)
+    ncb = (N + 31) // 32
+    nwg = (N + 127) // 128
+    want = max(1, min((512 + nwg - 1) // nwg, 16, ncb))
+    per = (ncb + want - 1) // want
+    chunks = (ncb + per - 1) // per
+    up = lambda n: (4 * n + 255) // 256 * 256
+    nbytes = up(N * d) + up(N) + 4 * up(chunks * N) + 4 * up(N) + up(chunks * N * d)
+    return chunks, per, nbytes
+
+
+def contra_first_split_batch():
+    """the smallest batch at which the layout splits the sweep into more than one column chunk"""
+    B = 1
+    while contra_layout(4, B)[0] < 2:
+        B += 1
+    return B
+
+
+class ContraWorkspace:
+    """the scratch of rc_contra_loss_fwd / _bwd, one buffer per (batch, d) that is never freed or moved while the owner lives.
+    `generation` counts forwards, so that a backward can tell whether another forward has overwritten what it reads."""
+
+    def __init__(self):
+        self._bufs = {}
+        self.generation = 0
+
+    def get(self, batch, d, device):
+        key = (int(batch), int(d), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_contra_workspace_bytes(int(d), int(batch))
+            buf = self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return buf
+
+
+def _contra_args(va, vb, labels):
+    if va.dim() != 2 or va.shape != vb.shape:
+        raise ValueError(f"contra_loss: the two views must be [batch, d] alike, got {tuple(va.shape)} / {tuple(vb.shape)}")
+    B, d = va.shape
+    contra_check_shape(d, B)
+    if labels is not None and labels.shape != (B,):
+        raise ValueError(f"contra_loss: labels must be [{B}], got {tuple(labels.shape)}")
+    return B, d
+
+
+def contra_loss_fwd(va, vb, labels, temperature, workspace=None):
+    """rc_contra_loss_fwd on the two views' un-normalised rows [B, d] -> (loss [1], the workspace buffer, its generation);
+    labels int64 [B] or None (InfoNCE)"""
+    B, d = _contra_args(va, vb, labels)
+    ws = workspace if workspace is not None else ContraWorkspace()
+    buf = ws.get(B, d, va.device)
+    ws.generation += 1
+    loss = torch.empty(1, dtype=torch.float32, device=va.device)
+    _lib.call("rc_contra_loss_fwd", _ptr(va, torch.float32, "va"), _ptr(vb, torch.float32, "vb"),
+              _ptr(labels, torch.int64, "labels", allow_none=True), B, d, float(temperature), C.c_void_p(buf.data_ptr()), buf.numel(),
+              _ptr(loss, torch.float32, "loss"), _stream())
+    return loss, buf, ws.generation
+
+
+def contra_loss_bwd(grad_out, labels, batch, d, temperature, buf):
+    """rc_contra_loss_bwd: grad_out [] / [1] on the device -> (grad_va, grad_vb) [B, d], from what the forward left in buf"""
+    contra_check_shape(d, batch)
+    g = grad_out.reshape(1).to(torch.float32).contiguous()
+    ga = torch.empty((batch, d), dtype=torch.float32, device=buf.device)
+    gb = torch.empty((batch, d), dtype=torch.float32, device=buf.device)
+    _lib.call("rc_contra_loss_bwd", _ptr(g, torch.float32, "grad_out"), _ptr(labels, torch.int64, "labels", allow_none=True),
+              int(batch), int(d), float(temperature), C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(ga, torch.float32, "grad_va"),
+              _ptr(gb, torch.float32, "grad_vb"), _stream())
+    return ga, gb
+
+
+def seq_embed_fwdpos(item_emb, pos_emb, hist, lengths):
+    """X [B * L, d] = item rows + position rows (position id = index) on valid rows, 0 on the padding (ContraRec.py:259-267)"""
+    B, L = hist.shape
+    d = item_emb.shape[1]
+    if pos_emb.shape[0] < L or pos_emb.shape[1] != d:
+        raise ValueError(f"seq_embed_fwdpos: the position table must be [>= {L}, {d}], got {tuple(pos_emb.shape)}")
+    f32, i64 = torch.float32, torch.int64
+    X = torch.empty((B * L, d), dtype=f32, device=hist.device)
+    _lib.call("rc_seq_embed_fwdpos_fwd", _ptr(item_emb, f32, "item_emb"), _ptr(pos_emb, f32, "pos_emb"), _ptr(hist, i64, "hist"),
+              _ptr(lengths, i64, "lengths"), B, L, d, _ptr(X, f32, "X"), _stream())
+    return X
+
+
+def seq_pos_grad_fwdpos(dX, lengths, B, L, n_pos):
+    """dense gradient [n_pos, d] of the position table from the rows' gradients dX [B * L, d] (position id = index)"""
+    d = dX.shape[1]
+    if n_pos < L:
+        raise ValueError(f"seq_pos_grad_fwdpos: the position table needs at least {L} rows, got {n_pos}")
+    out = torch.empty((n_pos, d), dtype=torch.float32, device=dX.device)
+    _lib.call("rc_seq_pos_grad_fwdpos", _ptr(dX, torch.float32, "dX"), _ptr(lengths, torch.int64, "lengths"), B, int(L), d, int(n_pos),
+              _ptr(out, torch.float32, "grad_pos"), _stream())
+    return out
+
+
 # ---- BUIR bootstrap loss, evaluation head, target update (models/general/BUIR.py:66-110) -----------------------------------------
 
 def buir_check_shape(d, batch=1):

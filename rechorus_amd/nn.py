@@ -987,22 +987,25 @@ def sasrec_encode(item_emb, pos_emb, blocks, n_heads, hist, lengths, drop_p=0.0,
 # ---- the encoder layer by layer, any shape (csrc/seq_layers.hip + the GEMMs of csrc/mlp.hip) ---------------------------------
 
 class _SeqEmbedFn(torch.autograd.Function):
-    """item rows + position rows of a right-padded history (SASRec.py:58-66) as B * L rows; the backward is the two dense
-    embedding gradients (the rows' gradients are zero on the padding)"""
+    """item rows + position rows of a right-padded history as B * L rows, position id = length - index (SASRec.py:58-66) or, with
+    fwdpos, the index itself (ContraRec.py:259-267); the backward is the two dense embedding gradients (the rows' gradients are
+    zero on the padding)"""
 
     @staticmethod
-    def forward(ctx, item_emb, pos_emb, hist, lengths):
-        ctx.hist, ctx.lengths = hist, lengths
+    def forward(ctx, item_emb, pos_emb, hist, lengths, fwdpos):
+        ctx.hist, ctx.lengths, ctx.fwdpos = hist, lengths, fwdpos
         ctx.n_items, ctx.n_pos = item_emb.shape[0], pos_emb.shape[0]
-        return engine.seq_embed(item_emb.detach(), pos_emb.detach(), hist, lengths)
+        embed = engine.seq_embed_fwdpos if fwdpos else engine.seq_embed
+        return embed(item_emb.detach(), pos_emb.detach(), hist, lengths)
 
     @staticmethod
     def backward(ctx, gX):
         B, L = ctx.hist.shape
         g = gX.contiguous()
         GI = engine.embedding_dense_backward(g.view(B, L, -1), ctx.hist, ctx.n_items)
-        GP = engine.seq_pos_grad(g, ctx.lengths, B, L, ctx.n_pos)
-        return GI, GP, None, None
+        pos_grad = engine.seq_pos_grad_fwdpos if ctx.fwdpos else engine.seq_pos_grad
+        GP = pos_grad(g, ctx.lengths, B, L, ctx.n_pos)
+        return GI, GP, None, None, None
 
 
 class _SeqAttentionFn(torch.autograd.Function):
@@ -1060,26 +1063,68 @@ class _SeqPickLastFn(torch.autograd.Function):
         return engine.seq_pick_last_bwd(dhv.contiguous(), lengths, B, L), None, None, None
 
 
-def sasrec_encode_layers(item_emb, pos_emb, blocks, n_heads, hist, lengths, drop_p=0.0, seed=None):
-    """The SASRec encoder (SASRec.py:58-76) block by block for the shapes outside the register-resident kernels' envelope
-    (engine.sasrec_supported): embeddings, every Linear (fp32 MFMA GEMMs, bias / ReLU in the epilogue), the attention of every
-    head, LayerNorm(dropout(.) + residual) -- all HIP kernels, autograd only strings them together.  -> hv [B, d], the output
-    row at position length - 1 of every sequence"""
+def _encode_layers(fwdpos, causal, item_emb, pos_emb, blocks, n_heads, hist, lengths, drop_p, seed):
+    """the layer loop both encoders share: the embedding with either position rule, the TransformerLayers with the causal mask or
+    with the key-padding mask alone, the row at position length - 1"""
     hist, lengths = hist.contiguous(), lengths.contiguous()
     B, L = hist.shape
     off = engine.seq_offsets(lengths, L)
-    x = _SeqEmbedFn.apply(item_emb, pos_emb, hist, lengths)
+    x = _SeqEmbedFn.apply(item_emb, pos_emb, hist, lengths, fwdpos)
     for l, blk in enumerate(blocks):
         a = blk.masked_attn_head
         q = linear(x, a.q_linear.weight, a.q_linear.bias)
         k = linear(x, a.k_linear.weight, a.k_linear.bias)
         v = linear(x, a.v_linear.weight, a.v_linear.bias)
-        c = _SeqAttentionFn.apply(q, k, v, off, B, L, n_heads, None, True)        # causal mask only (SASRec.py:69-70)
+        c = _SeqAttentionFn.apply(q, k, v, off, B, L, n_heads, None, causal)
         y1 = _AddLayerNormFn.apply(c, x, blk.layer_norm1.weight, blk.layer_norm1.bias, off, L, float(drop_p), seed, 2 * l)
         h = linear(y1, blk.linear1.weight, blk.linear1.bias, relu=True)
         f = linear(h, blk.linear2.weight, blk.linear2.bias)
         x = _AddLayerNormFn.apply(f, y1, blk.layer_norm2.weight, blk.layer_norm2.bias, off, L, float(drop_p), seed, 2 * l + 1)
     return _SeqPickLastFn.apply(x, lengths, B, L)
+
+
+def sasrec_encode_layers(item_emb, pos_emb, blocks, n_heads, hist, lengths, drop_p=0.0, seed=None):
+    """The SASRec encoder (SASRec.py:58-76) block by block for the shapes outside the register-resident kernels' envelope
+    (engine.sasrec_supported): embeddings, every Linear (fp32 MFMA GEMMs, bias / ReLU in the epilogue), the attention of every
+    head, LayerNorm(dropout(.) + residual) -- all HIP kernels, autograd only strings them together.  -> hv [B, d], the output
+    row at position length - 1 of every sequence"""
+    return _encode_layers(False, True, item_emb, pos_emb, blocks, n_heads, hist, lengths, drop_p, seed)   # causal mask only (SASRec.py:69-70)
+
+
+def bert4rec_encode_layers(item_emb, pos_emb, blocks, n_heads, hist, lengths):
+    """ContraRec's BERT4RecEncoder (ContraRec.py:259-276) on the same kernels: position id = index, no causal mask (a valid row
+    attends to every valid row of its sequence: `off` restricts queries and keys alike), no dropout.  -> hv [B, d]"""
+    return _encode_layers(True, False, item_emb, pos_emb, blocks, n_heads, hist, lengths, 0.0, None)
+
+
+class _ContraLossFn(torch.autograd.Function):
+    """ContraLoss behind F.normalize (ContraRec.py:92,142-193) on rc_contra_loss_fwd / _bwd: va, vb [B, d] un-normalised, labels
+    int64 [B] or None.  Backward: the two [B, d] gradients of the views."""
+
+    @staticmethod
+    def forward(ctx, va, vb, labels, temperature, workspace):
+        ws = workspace if workspace is not None else engine.ContraWorkspace()
+        loss, buf, gen = engine.contra_loss_fwd(va.detach(), vb.detach(), labels, temperature, workspace=ws)
+        ctx.buf, ctx.gen, ctx.workspace, ctx.labels = buf, gen, ws, labels
+        ctx.batch, ctx.d, ctx.temperature = va.shape[0], va.shape[1], temperature
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.workspace.generation != ctx.gen:
+            raise RuntimeError("contra_loss: another contra_loss forward ran on this workspace before this backward; give each "
+                               "pending loss a workspace of its own (rechorus_amd.engine.ContraWorkspace)")
+        ga, gb = engine.contra_loss_bwd(g, ctx.labels, ctx.batch, ctx.d, ctx.temperature, ctx.buf)
+        return ga, gb, None, None, None
+
+
+def contra_loss(va, vb, labels, temperature, workspace=None):
+    """ContraRec's context-context loss (ContraRec.py:92,102,142-193) of the two views' encoder outputs [B, d] as ONE autograd
+    node; labels None: InfoNCE; workspace: the model's engine.ContraWorkspace, reused step after step (None: a fresh one)"""
+    if not va.is_cuda:
+        raise RuntimeError("contra_loss runs on the GPU only (no CPU path)")
+    labels = None if labels is None else labels.contiguous()
+    return _ContraLossFn.apply(va.contiguous(), vb.contiguous(), labels, float(temperature), workspace)
 
 
 def sasrec_layers_supported(d, n_heads, L):
