@@ -1222,6 +1222,40 @@ int rc_finalmlp_fusion_bwd(const float* x, const float* y, const float* w_xy, co
                            int64_t n_instances, int x_dim, int y_dim, int num_heads, void* workspace, size_t ws_bytes, float* dx,
                            float* dy, float* dw_xy, float* dw_x, float* db_x, float* dw_y, float* db_y, rc_stream_t stream);
 
+/* ---- FPMC (csrc/fpmc.hip; reference models/sequential/FPMC.py:44-56) ----------------------------------------------------------
+ * Four fp32 tables, row-major, 16-byte aligned: UI [n_users, d], LI / IU / IL [n_items, d]; d in {16, 32, 64, 128}; ids int64.
+ *   pred[b, c] = <UI[uid[b]], IU[iid[b, c]]> + <LI[lid[b]], IL[iid[b, c]]>,   lid[b] = the last item of the history before the target.
+ * A candidate's two rows are read once as one "pair row" by d / 2 lanes; no floating-point atomics, every sum in a fixed order.
+ * These entry points return the same statuses as the rest of the library, spelled as the enum.                                   */
+
+/* RC_OK, or RC_ERR_INVALID_ARG with the reason in rc_last_error_string: d outside {16, 32, 64, 128}, C < 1 */
+enum rc_status rc_fpmc_check_shape(int d, int C);
+/* the path rc_fpmc_fwd_bwd takes for (d, C): 256 * GS + CPL for the register path (GS lane-groups of d / 2 lanes per tuple, each
+ * holding CPL candidate pair rows in registers; C <= 264 / 200 / 100 / 50 at d = 16 / 32 / 64 / 128), 0 for the streaming path.  Host logic, nothing is launched.    */
+size_t rc_fpmc_fwd_bwd_layout(int d, int C);
+/* the two-term score for any C >= 1 (evaluation: C = 100, or C = n_items with --test_all): pred [B, C] */
+enum rc_status rc_fpmc_scores(const float* UI, const float* LI, const float* IU, const float* IL, const int64_t* uid,
+                              const int64_t* lid, const int64_t* iid, int B, int C, int d, float* pred, rc_stream_t stream);
+/* scores, GeneralModel.loss (models/BaseModel.py:182-185; the arithmetic of rc_bpr_loss_fwd_bwd) and the backward to the query
+ * side in one launch: pred [B, C] (optional, may be NULL), loss_vec [B], gpred [B, C] = d(inv_b * sum loss_vec) / d pred,
+ *   ugrad[b, :] = sum_c gpred[b, c] * IU[iid[b, c]],   lgrad[b, :] = sum_c gpred[b, c] * IL[iid[b, c]]      (two [B, d] arrays).
+ * Any C >= 2, any B >= 1.                                                                                                          */
+enum rc_status rc_fpmc_fwd_bwd(const float* UI, const float* LI, const float* IU, const float* IL, const int64_t* uid,
+                               const int64_t* lid, const int64_t* iid, int B, int C, int d, float inv_b, float* pred,
+                               float* loss_vec, float* gpred, float* ugrad, float* lgrad, rc_stream_t stream);
+/* The item-side update of IU and IL in one pass over the sorted candidate ids (keys / perm of rc_sort_ids over iid [B * C], heads /
+ * n_heads of rc_segment_heads with only_multi = 0; both required).  For every distinct row r, over its occurrences o = perm[j] in
+ * ascending sorted position:  g_iu = sum_o gpred[o] * UI[uid[o / C]],  g_il = sum_o gpred[o] * LI[lid[o / C]];  then either
+ * dense_grad_iu[r] = g_iu and dense_grad_il[r] = g_il (both pointers given; caller zero-fills), or the optimizer `h` on row r of IU
+ * (mIU, vIU) and IL (mIL, vIL) in place, with the arithmetic of rc_segmented_update.  One dense pointer without the other is
+ * RC_ERR_INVALID_ARG.  UI and LI are read as they are before the step and must not alias IU / IL.  ws: 256-byte aligned.           */
+size_t rc_fpmc_item_update_workspace_bytes(int64_t n_occ, int d);
+enum rc_status rc_fpmc_item_update(float* IU, float* mIU, float* vIU, float* IL, float* mIL, float* vIL, int d, const uint32_t* keys,
+                                   const uint32_t* perm, int64_t n_occ, const float* gpred, const float* UI, const float* LI,
+                                   const int64_t* uid, const int64_t* lid, int C, const rc_opt_hyper* h, float* dense_grad_iu,
+                                   float* dense_grad_il, const uint32_t* heads, const uint32_t* n_heads, void* ws, size_t ws_bytes,
+                                   rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,12 @@ SIGNATURES = {
     "rc_finalmlp_fusion_fwd": (_i, [_p] * 7 + [_i64, _i, _i, _i, _p, _p]),
     "rc_finalmlp_fusion_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "rc_finalmlp_fusion_bwd": (_i, [_p] * 6 + [_i64, _i, _i, _i, _p, _sz] + [_p] * 7 + [_p]),
+    "rc_fpmc_check_shape": (_i, [_i, _i]),
+    "rc_fpmc_fwd_bwd_layout": (_sz, [_i, _i]),
+    "rc_fpmc_scores": (_i, [_p] * 7 + [_i, _i, _i, _p, _p]),
+    "rc_fpmc_fwd_bwd": (_i, [_p] * 7 + [_i, _i, _i, _f] + [_p] * 5 + [_p]),
+    "rc_fpmc_item_update_workspace_bytes": (_sz, [_i64, _i]),
+    "rc_fpmc_item_update": (_i, [_p] * 6 + [_i, _p, _p, _i64] + [_p] * 5 + [_i, _hp, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

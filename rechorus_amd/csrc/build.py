@@ -45,6 +45,7 @@ SOURCES = [
     "buir.hip",
     "autoint.hip",
     "finalmlp.hip",
+    "fpmc.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

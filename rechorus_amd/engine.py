@@ -3054,3 +3054,139 @@ def finalmlp_fusion_bwd(x, y, w_xy, w_x, w_y, dout, heads, workspace=None):
               _ptr(dx, f32, "dx"), _ptr(dy, f32, "dy"), _ptr(dw_xy, f32, "dw_xy"), _ptr(dw_x, f32, "dw_x"), _ptr(db_x, f32, "db_x"),
               _ptr(dw_y, f32, "dw_y"), _ptr(db_y, f32, "db_y"), _stream())
     return dx, dy, dw_xy, dw_x, db_x, dw_y, db_y
+
+
+# ---- FPMC: pair-table scores, fused BPR step, item-side pair update (models/sequential/FPMC.py:44-56) -----------------------------
+
+def fpmc_check_shape(d, n_cand=1):
+    """rc_fpmc_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate; raises ValueError with the library's
+    reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_fpmc_check_shape(int(d), int(n_cand)) != _lib.RC_OK:
+        raise ValueError("FPMC on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def fpmc_fwd_bwd_layout(d, n_cand):
+    """the path rc_fpmc_fwd_bwd takes for (d, C): (lane-groups per tuple, candidate pair rows per lane-group) on the register path,
+    None on the streaming path (rc_fpmc_fwd_bwd_layout, host logic)"""
+    code = int(_lib.load().rc_fpmc_fwd_bwd_layout(int(d), int(n_cand)))
+    return (code // 256, code % 256) if code else None
+
+
+def _fpmc_shapes(UI, LI, IU, IL, uid, lid, iid):
+    d = UI.shape[1]
+    if not (LI.shape[1] == IU.shape[1] == IL.shape[1] == d):
+        raise ValueError("FPMC: the four tables need the same emb_size")
+    if not (LI.shape[0] == IU.shape[0] == IL.shape[0]):
+        raise ValueError("FPMC: li, iu and il embeddings are indexed by item ids and need the same number of rows")
+    if iid.dim() != 2 or uid.shape != (iid.shape[0],) or lid.shape != (iid.shape[0],):
+        raise ValueError(f"FPMC: ids must be uid [B], lid [B], iid [B, C]; got {tuple(uid.shape)}, {tuple(lid.shape)}, {tuple(iid.shape)}")
+    return iid.shape[0], iid.shape[1], d
+
+
+def _fpmc_front_args(UI, LI, IU, IL, uid, lid, iid):
+    f32, i64 = torch.float32, torch.int64
+    return (_ptr(UI, f32, "UI"), _ptr(LI, f32, "LI"), _ptr(IU, f32, "IU"), _ptr(IL, f32, "IL"), _ptr(uid, i64, "uid"),
+            _ptr(lid, i64, "lid"), _ptr(iid, i64, "iid"))
+
+
+def fpmc_scores(UI, LI, IU, IL, uid, lid, iid):
+    """pred[b, c] = <UI[uid[b]], IU[iid[b, c]]> + <LI[lid[b]], IL[iid[b, c]]>, any C >= 1 (rc_fpmc_scores)"""
+    B, Cn, d = _fpmc_shapes(UI, LI, IU, IL, uid, lid, iid)
+    pred = torch.empty((B, Cn), dtype=torch.float32, device=UI.device)
+    _lib.call("rc_fpmc_scores", *_fpmc_front_args(UI, LI, IU, IL, uid, lid, iid), B, Cn, d, _ptr(pred, torch.float32, "pred"), _stream())
+    return pred
+
+
+def fpmc_fwd_bwd(UI, LI, IU, IL, uid, lid, iid, inv_b=None, want_pred=True):
+    """rc_fpmc_fwd_bwd: scores + GeneralModel.loss + backward to the query rows in one launch.
+    Returns (pred|None, loss_vec [B], gpred [B, C], ugrad [B, d], lgrad [B, d])."""
+    B, Cn, d = _fpmc_shapes(UI, LI, IU, IL, uid, lid, iid)
+    if inv_b is None:
+        inv_b = 1.0 / B
+    dev, f32 = UI.device, torch.float32
+    pred = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
+    loss_vec = torch.empty(B, dtype=f32, device=dev)
+    gpred = torch.empty((B, Cn), dtype=f32, device=dev)
+    ugrad = torch.empty((B, d), dtype=f32, device=dev)
+    lgrad = torch.empty((B, d), dtype=f32, device=dev)
+    _lib.call("rc_fpmc_fwd_bwd", *_fpmc_front_args(UI, LI, IU, IL, uid, lid, iid), B, Cn, d, float(inv_b),
+              _ptr(pred, f32, "pred", True), _ptr(loss_vec, f32, "loss_vec"), _ptr(gpred, f32, "gpred"), _ptr(ugrad, f32, "ugrad"),
+              _ptr(lgrad, f32, "lgrad"), _stream())
+    return pred, loss_vec, gpred, ugrad, lgrad
+
+
+def fpmc_item_update(keys, perm, heads, n_heads, gpred, UI, LI, uid, lid, hyper=None, IU=None, IL=None, m=(None, None), v=(None, None),
+                     dense_grad=(None, None)):
+    """rc_fpmc_item_update: one pass over the sorted candidate ids (keys / perm of sort_ids(iid), heads / n_heads of segment_heads)
+    that sums gpred[o] * UI[uid[o / C]] and gpred[o] * LI[lid[o / C]] per distinct candidate row and either applies `hyper` to rows
+    of IU / IL (m, v: (state of IU, state of IL)) in place or writes dense_grad = (dense .grad of IU, of IL); gpred [B, C]"""
+    n_occ = keys.numel()
+    d = UI.shape[1]
+    Cn = gpred.shape[-1]
+    f32, i32 = torch.float32, torch.int32
+    ws = workspace(_lib.load().rc_fpmc_item_update_workspace_bytes(n_occ, d), keys.device, "fpmc_item")
+    _lib.call("rc_fpmc_item_update", _ptr(IU, f32, "IU", True), _ptr(m[0], f32, "mIU", True), _ptr(v[0], f32, "vIU", True),
+              _ptr(IL, f32, "IL", True), _ptr(m[1], f32, "mIL", True), _ptr(v[1], f32, "vIL", True), d, _ptr(keys, i32, "keys"),
+              _ptr(perm, i32, "perm"), n_occ, _ptr(gpred, f32, "gpred"), _ptr(UI, f32, "UI"), _ptr(LI, f32, "LI"),
+              _ptr(uid, torch.int64, "uid"), _ptr(lid, torch.int64, "lid"), Cn, _hyper_ref(hyper),
+              _ptr(dense_grad[0], f32, "dense_grad_iu", True), _ptr(dense_grad[1], f32, "dense_grad_il", True),
+              _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
+
+
+class FpmcTrainer:
+    """Row-wise-optimizer FPMC training on the device tables UI [n_users, d], LI / IU / IL [n_items, d] (ui_embeddings, li_embeddings,
+    iu_embeddings, il_embeddings of models/sequential/FPMC.py:36-39).
+
+    One `step(uid, lid, iid)` = one iteration of BaseRunner.fit's batch loop (helpers/BaseRunner.py:193-206): two sorts + the head
+    list -> rc_fpmc_fwd_bwd -> rc_fpmc_item_update (reads the pre-step UI / LI) -> the two query-side rc_segmented_update.  Only rows
+    of the batch move (and only their optimizer state): the row-wise semantics of BprmfTrainer."""
+
+    def __init__(self, UI, LI, IU, IL, opt="SGD", lr=1e-3, l2=0.0, beta1=0.9, beta2=0.999, eps=None):
+        if opt not in ("SGD", "Adam", "Adagrad"):
+            raise ValueError(f"FpmcTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        self.UI, self.LI, self.IU, self.IL = UI, LI, IU, IL
+        self.d = UI.shape[1]
+        fpmc_check_shape(self.d)
+        self.opt = opt
+        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
+        self.state = {name: new_opt_state(t, opt) for name, t in (("UI", UI), ("LI", LI), ("IU", IU), ("IL", IL))}
+
+    def _mv(self, name):
+        return self.state[name].get("m"), self.state[name].get("v")
+
+    def _query_update(self, W, name, keys, perm, grad, key_base, occ_base):
+        n_occ = keys.numel()
+        m, v = self._mv(name)
+        ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, self.d), keys.device, "seg")
+        # plain gradient rows, one per occurrence; keys / perm are a slice of the joint sort of users and last items
+        _lib.call("rc_segmented_update", *_table_args(W, m, v, need_W=True), self.d, _ptr(keys, torch.int32, "keys"),
+                  _ptr(perm, torch.int32, "perm"), n_occ, *_source_args(None, grad, None, 1, None, None, default=n_occ),
+                  int(key_base), int(occ_base), _hyper_ref(self.hyper), None, None, None, 0, *_ws_args(ws))
+
+    def step(self, uid, lid, iid, inv_b=None):
+        """one training step; returns the device loss tensor (shape [1], no sync)"""
+        B, Cn, d = _fpmc_shapes(self.UI, self.LI, self.IU, self.IL, uid, lid, iid)
+        if inv_b is None:
+            inv_b = 1.0 / B
+        dev = self.UI.device
+        n_users, n_items = self.UI.shape[0], self.IU.shape[0]
+        self.hyper.step += 1
+        # candidates on their own; users + last items jointly (last items keyed behind the users)
+        ikeys, iperm = sort_ids(iid, n_items)
+        _, heads, n_heads = segment_heads(ikeys, iperm, want_single=False)
+        qkeys = torch.empty(2 * B, dtype=torch.int32, device=dev)
+        qperm = torch.empty(2 * B, dtype=torch.int32, device=dev)
+        ws = workspace(_lib.load().rc_sort_workspace_bytes(2 * B), dev, "sort")
+        _lib.call("rc_sort_ids", _ptr(uid, torch.int64, "uid"), B, _ptr(lid, torch.int64, "lid"), B, n_users, n_users + n_items,
+                  _ptr(qkeys, torch.int32, "keys"), _ptr(qperm, torch.int32, "perm"), *_ws_args(ws))
+        _, loss_vec, gpred, ugrad, lgrad = fpmc_fwd_bwd(self.UI, self.LI, self.IU, self.IL, uid, lid, iid, inv_b, want_pred=False)
+        loss = reduce_sum(loss_vec, inv_b)
+        mIU, vIU = self._mv("IU")
+        mIL, vIL = self._mv("IL")
+        fpmc_item_update(ikeys, iperm, heads, n_heads, gpred, self.UI, self.LI, uid, lid, hyper=self.hyper, IU=self.IU, IL=self.IL,
+                         m=(mIU, mIL), v=(vIU, vIL))
+        # the query side last: the item-side update above read the pre-step UI and LI
+        self._query_update(self.UI, "UI", qkeys[:B], qperm[:B], ugrad, 0, 0)
+        self._query_update(self.LI, "LI", qkeys[B:], qperm[B:], lgrad, n_users, B)
+        return loss

@@ -121,6 +121,37 @@ def bprmf_scores(U, I, uid, iid):
     return _BprmfScoreFn.apply(U, I, uid.contiguous(), iid.contiguous())
 
 
+class _FpmcScoreFn(torch.autograd.Function):
+    """prediction[b,c] = <UI[uid[b]], IU[iid[b,c]]> + <LI[lid[b]], IL[iid[b,c]]>  (models/sequential/FPMC.py:44-56)."""
+
+    @staticmethod
+    def forward(ctx, UI, LI, IU, IL, uid, lid, iid):
+        ctx.save_for_backward(UI, LI, IU, IL, uid, lid, iid)
+        return engine.fpmc_scores(UI.detach(), LI.detach(), IU.detach(), IL.detach(), uid, lid, iid)
+
+    @staticmethod
+    def backward(ctx, gpred):
+        UI, LI, IU, IL, uid, lid, iid = (t.detach() for t in ctx.saved_tensors)
+        gpred = gpred.contiguous()
+        # item side: dL/dIU[r] = sum_{(b,c): iid[b,c]=r} g[b,c] * UI[uid[b]], dL/dIL[r] likewise from LI[lid[b]] -- one pass
+        keys, perm = engine.sort_ids(iid, IU.shape[0])
+        _, heads, n_heads = engine.segment_heads(keys, perm, want_single=False)
+        GIU, GIL = torch.zeros_like(IU), torch.zeros_like(IL)
+        engine.fpmc_item_update(keys, perm, heads, n_heads, gpred, UI, LI, uid, lid, dense_grad=(GIU, GIL))
+        # query side: per-tuple rows sum_c g[b,c] * IU / IL[iid[b,c]], summed per user / per last item
+        GUI, GLI = torch.zeros_like(UI), torch.zeros_like(LI)
+        for G, table, ids in ((GUI, IU, uid), (GLI, IL, lid)):
+            rows = engine.weighted_row_sum(table, iid, gpred)
+            k, p = engine.sort_ids(ids, G.shape[0])
+            engine.segmented_update(k, p, rows, dense_grad=G)
+        return GUI, GLI, GIU, GIL, None, None, None
+
+
+def fpmc_scores(UI, LI, IU, IL, uid, lid, iid):
+    """FPMC's two-term head as one autograd node: dense gradients for the four tables from an arbitrary loss on the scores"""
+    return _FpmcScoreFn.apply(UI, LI, IU, IL, uid.contiguous(), lid.contiguous(), iid.contiguous())
+
+
 def table_rows(W, ids):
     """W[ids] with an autograd that sums the rows' gradients into a dense [n_rows, d] tensor (HipEmbedding's lookup on a table
     that is not a module's Parameter, e.g. LightGCN's propagated tables)"""

@@ -11,7 +11,7 @@ time-ordered histories (CSR) are uploaded once; per epoch one kernel samples all
 (rc_assemble_candidates, rc_gather_history).
 
 Only datasets whose feed dict is exactly one of the reference's standard ones are eligible (`dataset_kind()`:
-General (with sampled or, DirectAU's, empty training negatives), Sequential, Context top-k, Context CTR -- the latter two add the user / item / situation feature
+General (with sampled or, DirectAU's, empty training negatives), Sequential, FPMC's last-item feed, Context top-k, Context CTR -- the latter two add the user / item / situation feature
 columns, gathered on the device from dense per-id tables); a model file that overrides `_get_feed_dict` /
 `collate_batch` keeps the DataLoader path.
 """
@@ -101,9 +101,11 @@ def history_csr(corpus, device, which=None):
 
 
 def dataset_kind(dataset):
-    """'general' | 'general_unsampled' | 'sequential' | 'context' | 'ctr' when the dataset produces exactly one of the
-    reference's standard feed dicts (so it can be assembled on the device), else None (DataLoader path).  'general_unsampled':
-    the general feed dict whose training negatives are empty lists (DirectAU); dev / test keep the reader's negatives."""
+    """'general' | 'general_unsampled' | 'sequential' | 'last_item' | 'context' | 'ctr' when the dataset produces exactly one of
+    the reference's standard feed dicts (so it can be assembled on the device), else None (DataLoader path).  'general_unsampled':
+    the general feed dict whose training negatives are empty lists (DirectAU); dev / test keep the reader's negatives.  'last_item':
+    user, candidates and the last history item before the target (models/sequential/FPMC.py:58-73), declared by the Dataset class
+    that defines _get_feed_dict."""
     from models.BaseModel import BaseModel, GeneralModel, SequentialModel  # plugin surface (on sys.path)
     from models.BaseModel import CTRModel
     from models.BaseContextModel import ContextCTRModel, ContextModel
@@ -120,6 +122,8 @@ def dataset_kind(dataset):
         return 'general_unsampled'
     if feed is SequentialModel.Dataset._get_feed_dict and sampled:
         return 'sequential'
+    if _last_item_feed(cls) and sampled and issubclass(cls, SequentialModel.Dataset):
+        return 'last_item'
     if feed is ContextModel.Dataset._get_feed_dict and sampled:
         return 'context'
     unsampled = cls.actions_before_epoch in (BaseModel.Dataset.actions_before_epoch, CTRModel.Dataset.actions_before_epoch)
@@ -133,6 +137,13 @@ def _empty_train_negatives(cls):
     batches are (user, positive) only.  A subclass that overrides actions_before_epoch again does not inherit the declaration."""
     owner = next(k for k in cls.__mro__ if 'actions_before_epoch' in k.__dict__)
     return bool(owner.__dict__.get('empty_train_negatives', False))
+
+
+def _last_item_feed(cls):
+    """the class that defines _get_feed_dict declares that its feed dict is {user_id, item_id, last_item_id} (FPMC.Dataset).  A
+    subclass that overrides _get_feed_dict again does not inherit the declaration."""
+    owner = next(k for k in cls.__mro__ if '_get_feed_dict' in k.__dict__)
+    return bool(owner.__dict__.get('last_item_feed', False))
 
 
 def _impression_kind(cls, feed):
@@ -205,6 +216,10 @@ class DeviceDataset:
             self.position = col('position')
             self.his_ptr, self.his_items, self.his_times = history_csr(corpus, device)
             self.max_his = model.history_max if model.history_max > 0 else max(1, int(self.position.max()))
+        self.last_item = self.kind == 'last_item'
+        if self.last_item:  # the history columns only: the feed dict carries no history window
+            self.position = col('position')
+            self.his_ptr, self.his_items, _ = history_csr(corpus, device)
         self.impression = self.kind in ('impression', 'impression_seq')
         if self.impression:  # fixed-width positive / negative lists, right-padded with item 0 (collate_batch :190-201)
             self.lists = torch.from_numpy(np.concatenate(
@@ -259,6 +274,8 @@ class DeviceDataset:
             hist, times, lengths = engine.gather_history(idx, self.users, self.position, self.his_ptr, self.his_items,
                                                          self.max_his, his_times=self.his_times)
             feed.update(history_items=hist, history_times=times, lengths=lengths)
+        if self.last_item:  # user_his[u][position - 1][0] (models/sequential/FPMC.py:66-67)
+            feed['last_item_id'] = self._last_item_id(idx, user_id)
         if self.labels is not None:
             feed['label'] = self.labels[idx, None]
         if self.user_feat is not None:
@@ -271,6 +288,9 @@ class DeviceDataset:
         feed['batch_size'] = B
         feed['phase'] = self.phase
         return feed
+
+    def _last_item_id(self, idx, user_id):
+        return self.his_items[self.his_ptr[user_id] + self.position[idx] - 1]
 
     def _impression_feed(self, idx):
         """models/BaseImpressionModel.py Dataset._get_feed_dict + collate_batch: positives then negatives"""
@@ -292,6 +312,8 @@ class DeviceDataset:
             hist, times, lengths = engine.gather_history(idx, self.users, self.position, self.his_ptr, self.his_items,
                                                          self.max_his, his_times=self.his_times)
             feed.update(history_items=hist, history_times=times, lengths=lengths)
+        if self.last_item:
+            feed['last_item_id'] = self._last_item_id(idx, feed['user_id'])
         feed['batch_size'] = idx.numel()
         feed['phase'] = self.phase
         return feed
