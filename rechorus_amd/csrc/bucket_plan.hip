@@ -147,13 +147,19 @@ PlanLongWs carve_plan_long_ws(void* base, int64_t n, int d) {
 }
 
 // ---- device helpers -----------------------------------------------------------------------------------
-// the 32-bit key of position p.  Direct geometry: list a = the id, list b = base_b + id (one joint range, bucket = key >>
-// shift).  Hashed geometry: the id itself; the list follows from p.
+// The 32-bit key of position p, in two steps.  First the id as stored (past the end of the batch: "no key") ...
+__device__ __forceinline__ int64_t plan_raw_id(const PlanArgs& a, uint32_t p) {
+  return p < a.n ? (p < a.n_a ? a.ids_a[p] : a.ids_b[p - a.n_a]) : (int64_t)-1;
+}
+// ... then its key.  Direct geometry: list a = the id, list b = base_b + id (one joint range, bucket = key >> shift).  Hashed
+// geometry: the id itself; the list follows from p.
 // A NEGATIVE id marks a position that takes no part (padding slots of a history window): it yields the "no key" value
 // and is neither counted nor placed.
+// Two steps because a thread of the count / scatter kernels takes 16 positions: it requests all 16 raw ids and only then looks
+// at them, so its loads are in flight TOGETHER.  (With load and key in one function under the `p < n` guard, the compiler put
+// a wait for the load into every guarded block: 16 dependent memory round trips per thread.)
 template <bool HASHED>
-__device__ __forceinline__ uint32_t plan_key(const PlanArgs& a, uint32_t p) {
-  const int64_t id = p < a.n_a ? a.ids_a[p] : a.ids_b[p - a.n_a];
+__device__ __forceinline__ uint32_t plan_key_of(const PlanArgs& a, uint32_t p, int64_t id) {
   if (id < 0) return 0xFFFFFFFFu;
   if (HASHED) return (uint32_t)id;
   return p < a.n_a ? (uint32_t)id : a.g.base_b + (uint32_t)id;
@@ -234,12 +240,12 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(PlanArgs a) {
   for (uint32_t i = threadIdx.x; i < nb; i += kPlanThreads) s_hist[i] = 0;
   __syncthreads();
   const uint32_t tile0 = tile * (uint32_t)kPlanTile;
+  int64_t raw[kPlanRounds];
+#pragma unroll
+  for (int r = 0; r < kPlanRounds; ++r) raw[r] = plan_raw_id(a, tile0 + r * kPlanThreads + threadIdx.x);
   uint32_t key[kPlanRounds];
 #pragma unroll
-  for (int r = 0; r < kPlanRounds; ++r) {
-    const uint32_t p = tile0 + r * kPlanThreads + threadIdx.x;
-    key[r] = p < a.n ? plan_key<HASHED>(a, p) : 0xFFFFFFFFu;
-  }
+  for (int r = 0; r < kPlanRounds; ++r) key[r] = plan_key_of<HASHED>(a, tile0 + r * kPlanThreads + threadIdx.x, raw[r]);
   if (a.single_a && tile0 < a.n_a)  // flags of this tile's list-a positions start at 0 (padded buffer: whole uint4s)
     reinterpret_cast<uint4*>(a.single_a + tile0)[threadIdx.x] = make_uint4(0, 0, 0, 0);
 #pragma unroll
@@ -305,23 +311,27 @@ __global__ __launch_bounds__(kPlanThreads) void plan_scatter_kernel(PlanArgs a) 
   // issue this wave's id loads (1,024 consecutive positions) before anything else
   const uint32_t tile0 = tile * (uint32_t)kPlanTile;
   const uint32_t pos0 = tile0 + wave * (kPlanTile / kPlanWaves);
-  uint32_t key[kPlanRounds];
+  int64_t raw[kPlanRounds];
 #pragma unroll
-  for (int r = 0; r < kPlanRounds; ++r) {
-    const uint32_t p = pos0 + r * 64 + lane;
-    key[r] = p < a.n ? plan_key<HASHED>(a, p) : 0xFFFFFFFFu;
-  }
+  for (int r = 0; r < kPlanRounds; ++r) raw[r] = plan_raw_id(a, pos0 + r * 64 + lane);
 
-  // bucket bases: exclusive scan of the bucket totals (nb <= 4096 = 8 consecutive buckets per thread)
+  // bucket bases: exclusive scan of the bucket totals (nb <= 4096 = 8 consecutive buckets per thread).  The tile's histogram
+  // column (this tile's offset inside every bucket) is requested here too, in the same memory round trip as the ids and the
+  // totals: asked for after the barrier below, where it is used, it cost every workgroup a second dependent trip.
   constexpr int kPer = kPlanMaxBuckets / kPlanThreads;
-  uint32_t tv[kPer];
-  uint32_t tsum = 0;
+  uint32_t tv[kPer], hv[kPer];
 #pragma unroll
   for (int q = 0; q < kPer; ++q) {
     const uint32_t b = threadIdx.x * kPer + q;
     tv[q] = b < nb ? a.w.totals[b] : 0u;
-    tsum += tv[q];
+    hv[q] = b < nb ? a.w.hist[(size_t)b * a.g.tiles + tile] : 0u;
   }
+  uint32_t key[kPlanRounds];
+#pragma unroll
+  for (int r = 0; r < kPlanRounds; ++r) key[r] = plan_key_of<HASHED>(a, pos0 + r * 64 + lane, raw[r]);
+  uint32_t tsum = 0;
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) tsum += tv[q];
   uint32_t incl = wave_inclusive_scan(tsum, lane);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();  // also: cnt[] zeroed
@@ -331,7 +341,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_scatter_kernel(PlanArgs a) 
   for (int q = 0; q < kPer; ++q) {
     const uint32_t b = threadIdx.x * kPer + q;
     if (b < nb) {
-      gdelta[b] = run + a.w.hist[(size_t)b * a.g.tiles + tile];  // bucket base + this bucket's keys in earlier tiles
+      gdelta[b] = run + hv[q];  // bucket base + this bucket's keys in earlier tiles
       if (tile == 0) a.w.bucket_base[b] = run;
     }
     run += tv[q];
