@@ -1256,6 +1256,66 @@ enum rc_status rc_fpmc_item_update(float* IU, float* mIU, float* vIU, float* IL,
                                    float* dense_grad_il, const uint32_t* heads, const uint32_t* n_heads, void* ws, size_t ws_bytes,
                                    rc_stream_t stream);
 
+/* ---- SLRC+ (csrc/slrc.hip; reference models/sequential/SLRCPlus.py:62-89) ------------------------------------------------------
+ * Ten fp32 parameter arrays in the reference's layout: U [n_users, d] and I [n_items, d] (row-major, 16-byte aligned, d in
+ * {16, 32, 64, 128}), user_bias [n_users], item_bias [n_items], global_alpha [1], and the five Hawkes tables alphas, pis, betas,
+ * sigmas, mus [n_items, R] each (1 <= R <= 8 = item relations + 1; read as scalars, no alignment asked).  ids int64; intervals
+ * [B, C, R] fp32, -1 where the relation has no history event.  With t_r = intervals[b, c, r], on = (t_r >= 0), dt = on ? t_r : 0:
+ *   pred[b, c] = <U[u], I[i]> + user_bias[u] + item_bias[i] + sum_r [on] (global_alpha + alphas[i, r]) (pi e + (1 - pi) n),
+ *   pi = pis[i, r] + 0.5, beta = clamp(betas[i, r] + 1, 1e-10, 10), sigma likewise, mu = mus[i, r] + 1,
+ *   e = exp(log beta - beta dt), n = exp(-(dt - mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi)).
+ * No floating-point atomics, every sum in a fixed order.                                                                          */
+
+/* RC_OK, or RC_ERR_INVALID_ARG with the reason in rc_last_error_string: d outside {16, 32, 64, 128}, C < 1, R outside 1..8 */
+enum rc_status rc_slrc_check_shape(int d, int C, int R);
+/* the path rc_slrc_fwd_bwd takes for (d, C, R): the candidate rows each lane-group of d / 4 lanes holds in registers (one of 1, 2,
+ * 4, 8, 13, 25; 256 / d lane-groups per tuple, so C <= 400 / 200 / 100 / 50 at d = 16 / 32 / 64 / 128), 0 for the streaming path or
+ * a shape outside the envelope.  Host logic, nothing is launched.                                                                */
+size_t rc_slrc_fwd_bwd_layout(int d, int C, int R);
+/* the score for any C >= 1 (evaluation: C = 100, or C = n_items - 1 + 1 with --test_all): pred [B, C] */
+enum rc_status rc_slrc_scores(const float* U, const float* I, const float* user_bias, const float* item_bias,
+                              const float* global_alpha, const float* alphas, const float* pis, const float* betas,
+                              const float* sigmas, const float* mus, const int64_t* uid, const int64_t* iid, const float* intervals,
+                              int B, int C, int d, int R, float* pred, rc_stream_t stream);
+/* scores, GeneralModel.loss (models/BaseModel.py:182-185; the arithmetic of rc_bpr_loss_fwd_bwd) and the backward in one launch:
+ * pred [B, C] (optional, may be NULL), loss_vec [B], gpred [B, C] = d(inv_b * sum loss_vec) / d pred,
+ *   ugrad[b, :] = sum_c gpred[b, c] * I[iid[b, c]]  [B, d],   ubgrad[b] = sum_c gpred[b, c]  [B],
+ *   hgrad [B * C, 5 R]: row o = b C + c holds gpred[o] * d pred[o] / d (alphas | pis | betas | sigmas | mus)[iid[o], 0..R), clamp
+ *     (gradient passes on [1e-10, 10], ends included) and mask applied,
+ *   gagrad [B]: per-tuple partials of d loss / d global_alpha (their rc_reduce_sum is the gradient).
+ * Any C >= 2, any B >= 1.                                                                                                          */
+enum rc_status rc_slrc_fwd_bwd(const float* U, const float* I, const float* user_bias, const float* item_bias,
+                               const float* global_alpha, const float* alphas, const float* pis, const float* betas,
+                               const float* sigmas, const float* mus, const int64_t* uid, const int64_t* iid, const float* intervals,
+                               int B, int C, int d, int R, float inv_b, float* pred, float* loss_vec, float* gpred, float* ugrad,
+                               float* ubgrad, float* hgrad, float* gagrad, rc_stream_t stream);
+/* The backward of the biases and the excitation for a GIVEN gpred [B, C] (the autograd node of the dense engine, whose loss is not
+ * this file's): hgrad, ubgrad and gagrad as rc_slrc_fwd_bwd leaves them.  Any C >= 1.                                              */
+enum rc_status rc_slrc_excitation_bwd(const float* global_alpha, const float* alphas, const float* pis, const float* betas,
+                                      const float* sigmas, const float* mus, const int64_t* iid, const float* intervals,
+                                      const float* gpred, int B, int C, int R, float* hgrad, float* ubgrad, float* gagrad,
+                                      rc_stream_t stream);
+/* The item-side update of the seven item tables in one pass over the sorted candidate ids (keys / perm of rc_sort_ids over iid
+ * [B * C], heads / n_heads of rc_segment_heads with only_multi = 0; both required).  W, M, V and dense_grad are HOST arrays of seven
+ * device pointers in the order I, item_bias, alphas, pis, betas, sigmas, mus.  For every distinct row r, over its occurrences
+ * o = perm[j] in ascending sorted position:  g_I = sum_o gpred[o] * U[uid[o / C]],  g_ib = sum_o gpred[o],  g_H = sum_o hgrad[o];
+ * then either the seven dense gradients' row r is written (dense_grad given: all seven pointers, or RC_ERR_INVALID_ARG; the caller
+ * zero-fills), or the optimizer `h` is applied to row r of each table (and of M / V) in place with the arithmetic of
+ * rc_segmented_update: I and the five Hawkes tables with h's l2, item_bias with l2 = 0.  U is read as it is before the step and must
+ * not alias an item table.  Rows with more than 32 occurrences are summed by one workgroup each (fixed LDS tree).
+ * ws: 256-byte aligned.                                                                                                            */
+size_t rc_slrc_item_update_workspace_bytes(int64_t n_occ, int d);
+enum rc_status rc_slrc_item_update(float* const* W, float* const* M, float* const* V, int d, int R, const uint32_t* keys,
+                                   const uint32_t* perm, int64_t n_occ, const float* gpred, const float* hgrad, const float* U,
+                                   const int64_t* uid, int C, const rc_opt_hyper* h, float* const* dense_grad, const uint32_t* heads,
+                                   const uint32_t* n_heads, void* ws, size_t ws_bytes, rc_stream_t stream);
+/* user_bias [n_users] (one float per row, narrower than rc_segmented_update's d = 16): per distinct user r of the sorted uid list
+ * (keys / perm of rc_sort_ids over uid [B]), g = sum of ubgrad[perm[j]] in ascending sorted position; then dense_grad[r] = g, or the
+ * optimizer `h` on user_bias[r] (m, v) with l2 = 0 whatever h says ('bias' parameters take no weight decay).                     */
+enum rc_status rc_slrc_user_bias_update(float* user_bias, float* m, float* v, const uint32_t* keys, const uint32_t* perm,
+                                        int64_t n_occ, const float* ubgrad, const rc_opt_hyper* h, float* dense_grad,
+                                        rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

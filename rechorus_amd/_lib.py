@@ -271,6 +271,14 @@ SIGNATURES = {
     "rc_fpmc_fwd_bwd": (_i, [_p] * 7 + [_i, _i, _i, _f] + [_p] * 5 + [_p]),
     "rc_fpmc_item_update_workspace_bytes": (_sz, [_i64, _i]),
     "rc_fpmc_item_update": (_i, [_p] * 6 + [_i, _p, _p, _i64] + [_p] * 5 + [_i, _hp, _p, _p, _p, _p, _p, _sz, _p]),
+    "rc_slrc_check_shape": (_i, [_i, _i, _i]),
+    "rc_slrc_fwd_bwd_layout": (_sz, [_i, _i, _i]),
+    "rc_slrc_scores": (_i, [_p] * 13 + [_i, _i, _i, _i, _p, _p]),
+    "rc_slrc_fwd_bwd": (_i, [_p] * 13 + [_i, _i, _i, _i, _f] + [_p] * 7 + [_p]),
+    "rc_slrc_excitation_bwd": (_i, [_p] * 9 + [_i, _i, _i, _p, _p, _p, _p]),
+    "rc_slrc_item_update_workspace_bytes": (_sz, [_i64, _i]),
+    "rc_slrc_item_update": (_i, [_p] * 3 + [_i, _i, _p, _p, _i64] + [_p] * 4 + [_i, _hp, _p, _p, _p, _p, _sz, _p]),
+    "rc_slrc_user_bias_update": (_i, [_p] * 5 + [_i64, _p, _hp, _p, _p]),
 }
 
 _lib = None

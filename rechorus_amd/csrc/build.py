@@ -46,6 +46,7 @@ SOURCES = [
     "autoint.hip",
     "finalmlp.hip",
     "fpmc.hip",
+    "slrc.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

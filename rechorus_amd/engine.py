@@ -3190,3 +3190,174 @@ class FpmcTrainer:
         self._query_update(self.UI, "UI", qkeys[:B], qperm[:B], ugrad, 0, 0)
         self._query_update(self.LI, "LI", qkeys[B:], qperm[B:], lgrad, n_users, B)
         return loss
+
+
+# ---- SLRC+: biased MF + Hawkes excitation, fused BPR step, seven-table item update (models/sequential/SLRCPlus.py:62-89) ----------
+
+SLRC_PARAMS = ("U", "I", "user_bias", "item_bias", "global_alpha", "alphas", "pis", "betas", "sigmas", "mus")   # the argument order
+SLRC_ITEM_TABLES = ("I", "item_bias", "alphas", "pis", "betas", "sigmas", "mus")   # the [7] arrays of rc_slrc_item_update
+
+
+def slrc_check_shape(d, n_cand=1, n_rel=1):
+    """rc_slrc_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate, 1..8 relations; raises ValueError
+    with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_slrc_check_shape(int(d), int(n_cand), int(n_rel)) != _lib.RC_OK:
+        raise ValueError("SLRCPlus on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def slrc_fwd_bwd_layout(d, n_cand, n_rel=1):
+    """the path rc_slrc_fwd_bwd takes for (d, C, R): the candidate rows per lane-group on the register path, None on the
+    streaming path (rc_slrc_fwd_bwd_layout, host logic)"""
+    return int(_lib.load().rc_slrc_fwd_bwd_layout(int(d), int(n_cand), int(n_rel))) or None
+
+
+def _slrc_shapes(P, uid, iid, intervals):
+    U, I, ub, ib, ga, *H = P
+    d, n_users, n_items = U.shape[1], U.shape[0], I.shape[0]
+    R = H[0].shape[1]
+    if I.shape[1] != d:
+        raise ValueError("SLRCPlus: u_embeddings and i_embeddings need the same emb_size")
+    if ub.numel() != n_users or ib.numel() != n_items or ga.numel() != 1:
+        raise ValueError("SLRCPlus: user_bias [n_users, 1], item_bias [n_items, 1] and a scalar global_alpha are needed")
+    if any(tuple(h.shape) != (n_items, R) for h in H):
+        raise ValueError("SLRCPlus: alphas, pis, betas, sigmas and mus must all be [n_items, relation_num]")
+    if iid.dim() != 2 or uid.shape != (iid.shape[0],) or tuple(intervals.shape) != (iid.shape[0], iid.shape[1], R):
+        raise ValueError(f"SLRCPlus: need uid [B], iid [B, C], relational_interval [B, C, {R}]; got {tuple(uid.shape)}, "
+                         f"{tuple(iid.shape)}, {tuple(intervals.shape)}")
+    return iid.shape[0], iid.shape[1], d, R
+
+
+def _slrc_front_args(P, uid, iid, intervals):
+    f32, i64 = torch.float32, torch.int64
+    return tuple(_ptr(t, f32, name) for t, name in zip(P, SLRC_PARAMS)) + (
+        _ptr(uid, i64, "uid"), _ptr(iid, i64, "iid"), _ptr(intervals, f32, "relational_interval"))
+
+
+def slrc_scores(P, uid, iid, intervals):
+    """SLRC+'s prediction [B, C] for any C >= 1 (rc_slrc_scores); P: the ten parameter tensors in SLRC_PARAMS order"""
+    B, Cn, d, R = _slrc_shapes(P, uid, iid, intervals)
+    pred = torch.empty((B, Cn), dtype=torch.float32, device=iid.device)
+    _lib.call("rc_slrc_scores", *_slrc_front_args(P, uid, iid, intervals), B, Cn, d, R, _ptr(pred, torch.float32, "pred"), _stream())
+    return pred
+
+
+def slrc_fwd_bwd(P, uid, iid, intervals, inv_b=None, want_pred=True):
+    """rc_slrc_fwd_bwd: scores + GeneralModel.loss + backward in one launch.
+    Returns (pred|None, loss_vec [B], gpred [B, C], ugrad [B, d], ubgrad [B], hgrad [B * C, 5 R], gagrad [B])."""
+    B, Cn, d, R = _slrc_shapes(P, uid, iid, intervals)
+    if inv_b is None:
+        inv_b = 1.0 / B
+    dev, f32 = iid.device, torch.float32
+    pred = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
+    loss_vec = torch.empty(B, dtype=f32, device=dev)
+    gpred = torch.empty((B, Cn), dtype=f32, device=dev)
+    ugrad = torch.empty((B, d), dtype=f32, device=dev)
+    ubgrad = torch.empty(B, dtype=f32, device=dev)
+    hgrad = torch.empty((B * Cn, 5 * R), dtype=f32, device=dev)
+    gagrad = torch.empty(B, dtype=f32, device=dev)
+    _lib.call("rc_slrc_fwd_bwd", *_slrc_front_args(P, uid, iid, intervals), B, Cn, d, R, float(inv_b), _ptr(pred, f32, "pred", True),
+              _ptr(loss_vec, f32, "loss_vec"), _ptr(gpred, f32, "gpred"), _ptr(ugrad, f32, "ugrad"), _ptr(ubgrad, f32, "ubgrad"),
+              _ptr(hgrad, f32, "hgrad"), _ptr(gagrad, f32, "gagrad"), _stream())
+    return pred, loss_vec, gpred, ugrad, ubgrad, hgrad, gagrad
+
+
+def slrc_excitation_grads(P, uid, iid, intervals, gpred):
+    """rc_slrc_excitation_bwd: for a given gpred [B, C] -> (hgrad [B * C, 5 R], ubgrad [B], gagrad [B]) as slrc_fwd_bwd returns them"""
+    B, Cn, d, R = _slrc_shapes(P, uid, iid, intervals)
+    dev, f32 = iid.device, torch.float32
+    hgrad = torch.empty((B * Cn, 5 * R), dtype=f32, device=dev)
+    ubgrad = torch.empty(B, dtype=f32, device=dev)
+    gagrad = torch.empty(B, dtype=f32, device=dev)
+    _lib.call("rc_slrc_excitation_bwd", *(_ptr(t, f32, name) for t, name in zip(P[4:], SLRC_PARAMS[4:])), _ptr(iid, torch.int64, "iid"),
+              _ptr(intervals, f32, "relational_interval"), _ptr(gpred, f32, "gpred"), B, Cn, R, _ptr(hgrad, f32, "hgrad"),
+              _ptr(ubgrad, f32, "ubgrad"), _ptr(gagrad, f32, "gagrad"), _stream())
+    return hgrad, ubgrad, gagrad
+
+
+def _ptr_array7(tensors, name, allow_none=False):
+    """a host array of seven device pointers (SLRC_ITEM_TABLES order), or NULL when `tensors` is None"""
+    if tensors is None:
+        return None
+    if len(tensors) != 7:
+        raise ValueError(f"{name}: seven tensors are needed ({', '.join(SLRC_ITEM_TABLES)})")
+    return (C.c_void_p * 7)(*(_ptr(t, torch.float32, f"{name}[{k}]", allow_none) for t, k in zip(tensors, SLRC_ITEM_TABLES)))
+
+
+def slrc_item_update(keys, perm, heads, n_heads, gpred, hgrad, U, uid, hyper=None, W=None, m=None, v=None, dense_grad=None):
+    """rc_slrc_item_update: one pass over the sorted candidate ids (keys / perm of sort_ids(iid), heads / n_heads of segment_heads)
+    that sums gpred[o] * U[uid[o / C]], gpred[o] and hgrad[o] per distinct candidate row and either applies `hyper` to that row of
+    the seven item tables W (m, v: their states; SLRC_ITEM_TABLES order; item_bias with l2 = 0) in place or writes the seven
+    dense gradients; gpred [B, C], hgrad [B * C, 5 R]"""
+    n_occ = keys.numel()
+    d = U.shape[1]
+    Cn = gpred.shape[-1]
+    R = hgrad.shape[-1] // 5
+    f32, i32 = torch.float32, torch.int32
+    ws = workspace(_lib.load().rc_slrc_item_update_workspace_bytes(n_occ, d), keys.device, "slrc_item")
+    _lib.call("rc_slrc_item_update", _ptr_array7(W, "W"), _ptr_array7(m, "m", True), _ptr_array7(v, "v", True), d, R,
+              _ptr(keys, i32, "keys"), _ptr(perm, i32, "perm"), n_occ, _ptr(gpred, f32, "gpred"), _ptr(hgrad, f32, "hgrad"),
+              _ptr(U, f32, "U"), _ptr(uid, torch.int64, "uid"), Cn, _hyper_ref(hyper), _ptr_array7(dense_grad, "dense_grad"),
+              _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
+
+
+def slrc_user_bias_update(keys, perm, ubgrad, hyper=None, user_bias=None, m=None, v=None, dense_grad=None):
+    """rc_slrc_user_bias_update: per distinct user of the sorted uid list the sum of ubgrad over its tuples, then `hyper` on
+    user_bias (one float per row, l2 forced to 0) in place, or the dense gradient"""
+    f32, i32 = torch.float32, torch.int32
+    _lib.call("rc_slrc_user_bias_update", _ptr(user_bias, f32, "user_bias", True), _ptr(m, f32, "m", True), _ptr(v, f32, "v", True),
+              _ptr(keys, i32, "keys"), _ptr(perm, i32, "perm"), keys.numel(), _ptr(ubgrad, f32, "ubgrad"), _hyper_ref(hyper),
+              _ptr(dense_grad, f32, "dense_grad", True), _stream())
+
+
+class SlrcTrainer:
+    """Row-wise-optimizer SLRC+ training on the ten device parameters (SLRC_PARAMS order; models/sequential/SLRCPlus.py:49-60).
+
+    One `step(uid, iid, intervals)` = one iteration of BaseRunner.fit's batch loop (helpers/BaseRunner.py:193-206): two sorts + the
+    head list -> rc_slrc_fwd_bwd -> rc_slrc_item_update (reads the pre-step U) -> rc_segmented_update on U, rc_slrc_user_bias_update,
+    rc_dense_update on global_alpha.  Only rows of the batch move (and only their optimizer state): the row-wise semantics of
+    BprmfTrainer; the two bias tables take no weight decay, global_alpha (dense, one float) does."""
+
+    def __init__(self, *params, opt="SGD", lr=1e-3, l2=0.0, beta1=0.9, beta2=0.999, eps=None):
+        if opt not in ("SGD", "Adam", "Adagrad"):
+            raise ValueError(f"SlrcTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        if len(params) != len(SLRC_PARAMS):
+            raise ValueError("SlrcTrainer: ten parameter tensors are needed: " + ", ".join(SLRC_PARAMS))
+        self.P = dict(zip(SLRC_PARAMS, params))
+        self.d, self.R = self.P["U"].shape[1], self.P["alphas"].shape[1]
+        slrc_check_shape(self.d, 1, self.R)
+        self.opt = opt
+        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
+        self.state = {name: new_opt_state(t, opt) for name, t in self.P.items()}
+
+    def _mv(self, name):
+        return self.state[name].get("m"), self.state[name].get("v")
+
+    def step(self, uid, iid, intervals, inv_b=None):
+        """one training step; returns the device loss tensor (shape [1], no sync)"""
+        P = [self.P[k] for k in SLRC_PARAMS]
+        B, Cn, d, R = _slrc_shapes(P, uid, iid, intervals)
+        if inv_b is None:
+            inv_b = 1.0 / B
+        U = self.P["U"]
+        self.hyper.step += 1
+        ikeys, iperm = sort_ids(iid, self.P["I"].shape[0])
+        _, heads, n_heads = segment_heads(ikeys, iperm, want_single=False)
+        ukeys, uperm = sort_ids(uid, U.shape[0])
+        _, loss_vec, gpred, ugrad, ubgrad, hgrad, gagrad = slrc_fwd_bwd(P, uid, iid, intervals, inv_b, want_pred=False)
+        loss = reduce_sum(loss_vec, inv_b)
+        items = [self.P[k] for k in SLRC_ITEM_TABLES]
+        mv = [self._mv(k) for k in SLRC_ITEM_TABLES]
+        slrc_item_update(ikeys, iperm, heads, n_heads, gpred, hgrad, U, uid, hyper=self.hyper, W=items,
+                         m=[x[0] for x in mv] if mv[0][0] is not None else None, v=[x[1] for x in mv] if mv[0][1] is not None else None)
+        # the user side last: the item-side update above read the pre-step U
+        m, v = self._mv("U")
+        ws = workspace(_lib.load().rc_segmented_workspace_bytes(B, d), U.device, "seg")
+        _lib.call("rc_segmented_update", *_table_args(U, m, v, need_W=True), d, _ptr(ukeys, torch.int32, "keys"),
+                  _ptr(uperm, torch.int32, "perm"), B, *_source_args(None, ugrad, None, 1, None, None, default=B), 0, 0,
+                  _hyper_ref(self.hyper), None, None, None, 0, *_ws_args(ws))
+        m, v = self._mv("user_bias")
+        slrc_user_bias_update(ukeys, uperm, ubgrad, hyper=self.hyper, user_bias=self.P["user_bias"], m=m, v=v)
+        m, v = self._mv("global_alpha")
+        dense_update(self.P["global_alpha"], reduce_sum(gagrad), self.hyper, m=m, v=v)
+        return loss

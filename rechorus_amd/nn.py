@@ -152,6 +152,43 @@ def fpmc_scores(UI, LI, IU, IL, uid, lid, iid):
     return _FpmcScoreFn.apply(UI, LI, IU, IL, uid.contiguous(), lid.contiguous(), iid.contiguous())
 
 
+class _SlrcScoreFn(torch.autograd.Function):
+    """SLRC+'s prediction (models/sequential/SLRCPlus.py:62-89) with dense gradients for its ten parameters; none for the ids or the
+    intervals.  The backward runs on the saved inputs: per-candidate excitation derivatives are recomputed by rc_slrc_fwd_bwd's
+    arithmetic through engine.slrc_excitation_grads."""
+
+    @staticmethod
+    def forward(ctx, uid, iid, intervals, *params):
+        ctx.save_for_backward(uid, iid, intervals, *params)
+        return engine.slrc_scores([p.detach() for p in params], uid, iid, intervals)
+
+    @staticmethod
+    def backward(ctx, gpred):
+        uid, iid, intervals, *params = (t.detach() for t in ctx.saved_tensors)
+        U, I, ub, ib, ga = params[:5]
+        gpred = gpred.contiguous()
+        # the per-occurrence Hawkes rows and the per-tuple partials, scaled by the incoming gradient
+        hgrad, ubgrad, gagrad = engine.slrc_excitation_grads(params, uid, iid, intervals, gpred)
+        keys, perm = engine.sort_ids(iid, I.shape[0])
+        _, heads, n_heads = engine.segment_heads(keys, perm, want_single=False)
+        dense = [torch.zeros_like(params[k]) for k in (1, 3, 5, 6, 7, 8, 9)]
+        engine.slrc_item_update(keys, perm, heads, n_heads, gpred, hgrad, U, uid, dense_grad=dense)
+        GI, Gib, *GH = dense
+        # user side: per-tuple rows sum_c g[b,c] * I[iid[b,c]] and sum_c g[b,c], summed per user
+        GU, Gub = torch.zeros_like(U), torch.zeros_like(ub)
+        k, p = engine.sort_ids(uid, U.shape[0])
+        engine.segmented_update(k, p, engine.weighted_row_sum(I, iid, gpred), dense_grad=GU)
+        engine.slrc_user_bias_update(k, p, ubgrad, dense_grad=Gub)
+        Gga = engine.reduce_sum(gagrad).reshape(ga.shape)
+        return (None, None, None, GU, GI, Gub, Gib, Gga, *GH)
+
+
+def slrc_scores(params, uid, iid, intervals):
+    """SLRC+'s head as one autograd node: dense gradients for the ten parameters (engine.SLRC_PARAMS order) from an arbitrary loss
+    on the scores; the intervals take no gradient"""
+    return _SlrcScoreFn.apply(uid.contiguous(), iid.contiguous(), intervals.contiguous(), *params)
+
+
 def table_rows(W, ids):
     """W[ids] with an autograd that sums the rows' gradients into a dense [n_rows, d] tensor (HipEmbedding's lookup on a table
     that is not a module's Parameter, e.g. LightGCN's propagated tables)"""
