@@ -1316,6 +1316,44 @@ enum rc_status rc_slrc_user_bias_update(float* user_bias, float* m, float* v, co
                                         int64_t n_occ, const float* ubgrad, const rc_opt_hyper* h, float* dense_grad,
                                         rc_stream_t stream);
 
+/* ---- CFKG (csrc/cfkg.hip; reference models/general/CFKG.py:57-76) ---------------------------------------------------------------
+ * Two fp32 tables, row-major, 16-byte aligned: E [n_rows, d] (e_embeddings: the users first, entity e in row n_users + e; heads and
+ * tails alike index it) and R [n_rel, d] (r_embeddings; relation 0 is "buy"); d in {16, 32, 64, 128}, 1 <= n_rel <= 8; ids int64,
+ * already row indices of E (< n_rows) and of R (< n_rel).
+ *   pred[b, c] = -sum_k (E[head[b, c]] + R[rel[b, c]] - E[tail[b, c]])_k^2                                          (CFKG.py:63-67)
+ * One lane-group of d / 4 lanes per translation; ids first, then every row load in flight.  No floating-point atomics, every sum in
+ * a fixed order: results are bit-identical from run to run.                                                                       */
+
+/* RC_OK, or RC_ERR_INVALID_ARG with the reason in rc_last_error_string: d outside {16, 32, 64, 128}, C < 1, n_rel outside 1..8
+ * (the envelope CFKG.__init__, CFKG.py:41-48, is held to at construction) */
+enum rc_status rc_cfkg_check_shape(int d, int C, int n_rel);
+/* the quadruple rows (CFKG.py:91-99) one workgroup of rc_cfkg_fwd_bwd takes at width d (the launch geometry changes at its multiples; the workspace holds
+ * one [n_rel, d] partial per workgroup); 0 for a width without a kernel.  Host logic, nothing is launched.                        */
+size_t rc_cfkg_fwd_bwd_rows_per_block(int d);
+/* CFKG.forward (CFKG.py:57-68) for any [B, C] id triple, C >= 1 (evaluation: C = 100, or C = n_items with --test_all): pred [B, C].
+ * A wave whose candidates share one head and one relation (the evaluation feed, CFKG.py:106-108) reads those two rows once.       */
+enum rc_status rc_cfkg_scores(const float* E, const float* R, const int64_t* head, const int64_t* tail, const int64_t* rel, int B,
+                              int C, int d, int64_t n_rows, int n_rel, float* pred, rc_stream_t stream);
+/* the backward of CFKG.py:63-67 for a GIVEN gpred [B, C] (the autograd node of the dense engine):
+ *   G[b * C + c, :] = -2 gpred[b, c] (E[head] + R[rel] - E[tail])      [B * C, d]
+ * -- the head row's gradient; the tail row's is its negative, the relation row's equals it.                                       */
+enum rc_status rc_cfkg_scores_bwd(const float* E, const float* R, const int64_t* head, const int64_t* tail, const int64_t* rel,
+                                  const float* gpred, int B, int C, int d, int64_t n_rows, int n_rel, float* G, rc_stream_t stream);
+/* CFKG.forward on the training feed (CFKG.py:91-99: head = (h, h, h, h'), tail = (t, t, t', t), one relation r per row), CFKG.loss
+ * (CFKG.py:70-76: MarginRankingLoss(margin) over the 2 B pairs) and its backward, in one launch plus the relation reduce.  With
+ * a = h + r - t, b = h + r - t', c = h' + r - t, x1 = margin + |a|^2 - |b|^2, x2 = margin + |a|^2 - |c|^2, s = [x >= 0] (at a tie the
+ * gradient passes, as clamp_min(0)'s backward does) and w = inv_b:
+ *   loss_vec[b] = (s1 x1 + s2 x2) / 2           (rc_reduce_sum(loss_vec, B, inv_b) is the reference's mean over 2 B pairs)
+ *   pred [B, 4] (optional, may be NULL; 16-byte aligned) = (-|a|^2, -|a|^2, -|b|^2, -|c|^2)
+ *   grows [B, 4, d]: the gradient rows of (h, t, h', t') in that order: w ((s1 + s2) a - s1 b), w (-(s1 + s2) a + s2 c), -w s2 c, w s1 b
+ *   GR [n_rel, d] (dense, every row written): sum over the rows b with r[b] = k of w ((s1 + s2) a - s1 b - s2 c)
+ * ws: 16-byte aligned, rc_cfkg_fwd_bwd_workspace_bytes(B, d, n_rel) bytes (one [n_rel, d] partial per workgroup, summed in
+ * workgroup order).  Any B >= 1.                                                                                                  */
+size_t rc_cfkg_fwd_bwd_workspace_bytes(int64_t B, int d, int n_rel);
+enum rc_status rc_cfkg_fwd_bwd(const float* E, const float* R, const int64_t* h, const int64_t* t, const int64_t* hn,
+                               const int64_t* tn, const int64_t* r, int B, int d, int64_t n_rows, int n_rel, float margin, float inv_b,
+                               float* loss_vec, float* pred, float* grows, float* GR, void* ws, size_t ws_bytes, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

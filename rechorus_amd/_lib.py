@@ -279,6 +279,12 @@ SIGNATURES = {
     "rc_slrc_item_update_workspace_bytes": (_sz, [_i64, _i]),
     "rc_slrc_item_update": (_i, [_p] * 3 + [_i, _i, _p, _p, _i64] + [_p] * 4 + [_i, _hp, _p, _p, _p, _p, _sz, _p]),
     "rc_slrc_user_bias_update": (_i, [_p] * 5 + [_i64, _p, _hp, _p, _p]),
+    "rc_cfkg_check_shape": (_i, [_i, _i, _i]),
+    "rc_cfkg_fwd_bwd_rows_per_block": (_sz, [_i]),
+    "rc_cfkg_scores": (_i, [_p] * 5 + [_i, _i, _i, _i64, _i, _p, _p]),
+    "rc_cfkg_scores_bwd": (_i, [_p] * 6 + [_i, _i, _i, _i64, _i, _p, _p]),
+    "rc_cfkg_fwd_bwd_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "rc_cfkg_fwd_bwd": (_i, [_p] * 7 + [_i, _i, _i64, _i, _f, _f] + [_p] * 5 + [_sz, _p]),
 }
 
 _lib = None

@@ -47,6 +47,7 @@ SOURCES = [
     "finalmlp.hip",
     "fpmc.hip",
     "slrc.hip",
+    "cfkg.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

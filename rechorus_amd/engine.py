@@ -3361,3 +3361,129 @@ class SlrcTrainer:
         m, v = self._mv("global_alpha")
         dense_update(self.P["global_alpha"], reduce_sum(gagrad), self.hyper, m=m, v=v)
         return loss
+
+
+# ---- CFKG: translation distance on one entity table, fused margin-hinge step (models/general/CFKG.py:57-76) -----------------------
+
+def cfkg_check_shape(d, n_cand=1, n_rel=1):
+    """rc_cfkg_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate, 1..8 relations; raises ValueError
+    with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_cfkg_check_shape(int(d), int(n_cand), int(n_rel)) != _lib.RC_OK:
+        raise ValueError("CFKG on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def cfkg_fwd_bwd_rows_per_block(d):
+    """the rows one workgroup of rc_cfkg_fwd_bwd takes at emb_size d (host logic); the launch geometry changes at its multiples"""
+    return int(_lib.load().rc_cfkg_fwd_bwd_rows_per_block(int(d)))
+
+
+def _cfkg_shapes(E, R, head, tail, rel):
+    d = E.shape[1]
+    if R.dim() != 2 or R.shape[1] != d:
+        raise ValueError("CFKG: e_embeddings and r_embeddings need the same emb_size")
+    if head.dim() != 2 or tail.shape != head.shape or rel.shape != head.shape:
+        raise ValueError(f"CFKG: head_id, tail_id and relation_id must share one [B, C] shape; got {tuple(head.shape)}, "
+                         f"{tuple(tail.shape)}, {tuple(rel.shape)}")
+    return head.shape[0], head.shape[1], d
+
+
+def _cfkg_front_args(E, R, head, tail, rel):
+    f32, i64 = torch.float32, torch.int64
+    return (_ptr(E, f32, "E"), _ptr(R, f32, "R"), _ptr(head, i64, "head_id"), _ptr(tail, i64, "tail_id"), _ptr(rel, i64, "relation_id"))
+
+
+def cfkg_scores(E, R, head, tail, rel):
+    """pred[b, c] = -|E[head[b, c]] + R[rel[b, c]] - E[tail[b, c]]|^2 for any [B, C] id triple (rc_cfkg_scores)"""
+    B, Cn, d = _cfkg_shapes(E, R, head, tail, rel)
+    pred = torch.empty((B, Cn), dtype=torch.float32, device=E.device)
+    _lib.call("rc_cfkg_scores", *_cfkg_front_args(E, R, head, tail, rel), B, Cn, d, E.shape[0], R.shape[0],
+              _ptr(pred, torch.float32, "pred"), _stream())
+    return pred
+
+
+def cfkg_scores_grads(E, R, head, tail, rel, gpred):
+    """rc_cfkg_scores_bwd: for a given gpred [B, C] the head rows' gradient G [B * C, d] = -2 gpred (E[head] + R[rel] - E[tail]);
+    the tail rows' is -G, the relation rows' is G"""
+    B, Cn, d = _cfkg_shapes(E, R, head, tail, rel)
+    G = torch.empty((B * Cn, d), dtype=torch.float32, device=E.device)
+    _lib.call("rc_cfkg_scores_bwd", *_cfkg_front_args(E, R, head, tail, rel), _ptr(gpred, torch.float32, "gpred"), B, Cn, d, E.shape[0],
+              R.shape[0], _ptr(G, torch.float32, "G"), _stream())
+    return G
+
+
+def cfkg_fwd_bwd(E, R, h, t, hn, tn, r, margin=0.0, inv_b=None, want_pred=True):
+    """rc_cfkg_fwd_bwd: the quadruple feed's scores, MarginRankingLoss(margin) and backward in one launch + the relation reduce.
+    h, t, hn, tn: int64 [B] row indices of E; r: int64 [B].
+    Returns (pred [B, 4] | None, loss_vec [B], grows [B, 4, d] (rows of h, t, hn, tn), GR [n_rel, d])."""
+    B, d, n_rel = h.shape[0], E.shape[1], R.shape[0]
+    if R.shape[1] != d:
+        raise ValueError("CFKG: e_embeddings and r_embeddings need the same emb_size")
+    if any(x.shape != (B,) for x in (t, hn, tn, r)):
+        raise ValueError("CFKG: h, t, hn, tn and r must all be [B]")
+    cfkg_check_shape(d, 4, n_rel)
+    if inv_b is None:
+        inv_b = 1.0 / B
+    dev, f32, i64 = E.device, torch.float32, torch.int64
+    pred = torch.empty((B, 4), dtype=f32, device=dev) if want_pred else None
+    loss_vec = torch.empty(B, dtype=f32, device=dev)
+    grows = torch.empty((B, 4, d), dtype=f32, device=dev)
+    GR = torch.empty((n_rel, d), dtype=f32, device=dev)
+    ws = workspace(_lib.load().rc_cfkg_fwd_bwd_workspace_bytes(B, d, n_rel), dev, "cfkg_front")
+    _lib.call("rc_cfkg_fwd_bwd", _ptr(E, f32, "E"), _ptr(R, f32, "R"), _ptr(h, i64, "h"), _ptr(t, i64, "t"), _ptr(hn, i64, "hn"),
+              _ptr(tn, i64, "tn"), _ptr(r, i64, "r"), B, d, E.shape[0], n_rel, float(margin), float(inv_b),
+              _ptr(loss_vec, f32, "loss_vec"), _ptr(pred, f32, "pred", True), _ptr(grows, f32, "grows"), _ptr(GR, f32, "GR"),
+              *_ws_args(ws))
+    return pred, loss_vec, grows, GR
+
+
+class CfkgTrainer:
+    """CFKG training on the device tables E [n_users + n_entities, d] and R [n_relations, d] (e_embeddings, r_embeddings of
+    models/general/CFKG.py:50-55).
+
+    One `step(head, tail, rel)` = one iteration of BaseRunner.fit's batch loop (helpers/BaseRunner.py:193-206) on the [B, 4] training
+    feed: rc_cfkg_fwd_bwd -> one rc_sort_ids over the 4 B keys (h, t, h', t') -> one rc_segmented_update of E from the gradient rows
+    -> rc_dense_update of R.  The two tables follow different semantics, on purpose: E is updated ROW-WISE (only rows of the batch
+    move, and only their optimizer state; weight decay reaches only them -- the semantics of BprmfTrainer), and the joint sort is
+    what makes an entity that is a head in one row and a tail in another (or in the same row) see ONE summed gradient.  R has at
+    most 8 rows and essentially every batch touches all of them, so it is updated DENSELY from GR and follows torch.optim exactly
+    (weight decay and Adam's moment decay on every row, every step)."""
+
+    def __init__(self, E, R, margin=0.0, opt="SGD", lr=1e-3, l2=0.0, beta1=0.9, beta2=0.999, eps=None):
+        if opt not in ("SGD", "Adam", "Adagrad"):
+            raise ValueError(f"CfkgTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        self.E, self.R, self.margin = E, R, float(margin)
+        self.d = E.shape[1]
+        cfkg_check_shape(self.d, 4, R.shape[0])
+        self.opt = opt
+        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
+        self.state = {name: new_opt_state(t, opt) for name, t in (("E", E), ("R", R))}
+
+    def _mv(self, name):
+        return self.state[name].get("m"), self.state[name].get("v")
+
+    def step(self, head, tail, rel, inv_b=None):
+        """one training step on head_id / tail_id / relation_id [B, 4]; returns the device loss tensor (shape [1], no sync)"""
+        if head.dim() != 2 or head.shape[1] != 4 or tail.shape != head.shape or rel.shape != head.shape:
+            raise ValueError(f"CfkgTrainer: the training feed is head_id, tail_id, relation_id [B, 4]; got {tuple(head.shape)}, "
+                             f"{tuple(tail.shape)}, {tuple(rel.shape)}")
+        B = head.shape[0]
+        if inv_b is None:
+            inv_b = 1.0 / B
+        # (h, t, h', t') per row, in the order of the gradient rows: the sort's occurrence o = 4 b + j is row o of grows
+        dev, i64 = self.E.device, torch.int64
+        ids = torch.empty((B, 4), dtype=i64, device=dev)
+        torch.stack((head[:, 0], tail[:, 0], head[:, 3], tail[:, 2]), dim=1, out=ids)
+        cols = torch.empty((4, B), dtype=i64, device=dev)
+        cols.copy_(ids.t())
+        r = torch.empty(B, dtype=i64, device=dev)
+        r.copy_(rel[:, 0])
+        self.hyper.step += 1
+        _, loss_vec, grows, GR = cfkg_fwd_bwd(self.E, self.R, cols[0], cols[1], cols[2], cols[3], r, self.margin, inv_b, want_pred=False)
+        loss = reduce_sum(loss_vec, inv_b)
+        keys, perm = sort_ids(ids, self.E.shape[0])
+        m, v = self._mv("E")
+        segmented_update(keys, perm, grows.view(4 * B, self.d), hyper=self.hyper, W=self.E, m=m, v=v)
+        m, v = self._mv("R")
+        dense_update(self.R, GR, self.hyper, m=m, v=v)
+        return loss

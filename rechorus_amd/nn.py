@@ -189,6 +189,37 @@ def slrc_scores(params, uid, iid, intervals):
     return _SlrcScoreFn.apply(uid.contiguous(), iid.contiguous(), intervals.contiguous(), *params)
 
 
+class _CfkgScoreFn(torch.autograd.Function):
+    """prediction[b,c] = -|E[head[b,c]] + R[rel[b,c]] - E[tail[b,c]]|^2  (models/general/CFKG.py:57-68), dense gradients for E, R."""
+
+    @staticmethod
+    def forward(ctx, E, R, head, tail, rel):
+        ctx.save_for_backward(E, R, head, tail, rel)
+        return engine.cfkg_scores(E.detach(), R.detach(), head, tail, rel)
+
+    @staticmethod
+    def backward(ctx, gpred):
+        E, R, head, tail, rel = (t.detach() for t in ctx.saved_tensors)
+        n = head.numel()
+        # one row per (b, c): the head's gradient; the tail's is its negative, the relation's equals it
+        G = engine.cfkg_scores_grads(E, R, head, tail, rel, gpred.contiguous())
+        # E serves heads and tails alike: ONE sort over both id lists, occurrence o and o + n both read row o of G (coef +1 / -1)
+        keys, perm = engine.sort_ids(torch.cat((head.reshape(-1), tail.reshape(-1))), E.shape[0])
+        coef = torch.ones(2 * n, dtype=torch.float32, device=G.device)
+        coef[n:] = -1.0
+        src_index = torch.arange(n, dtype=torch.int64, device=G.device).repeat(2)
+        GE = torch.zeros_like(E)
+        engine.segmented_update(keys, perm, G, coef=coef, src_index=src_index, dense_grad=GE)
+        GR = engine.embedding_dense_backward(G, rel, R.shape[0], route="sort")
+        return GE, GR, None, None, None
+
+
+def cfkg_scores(E, R, head, tail, rel):
+    """CFKG's translation-distance head as one autograd node: dense gradients for the entity and the relation table from an
+    arbitrary loss on the scores"""
+    return _CfkgScoreFn.apply(E, R, head.contiguous(), tail.contiguous(), rel.contiguous())
+
+
 def table_rows(W, ids):
     """W[ids] with an autograd that sums the rows' gradients into a dense [n_rows, d] tensor (HipEmbedding's lookup on a table
     that is not a module's Parameter, e.g. LightGCN's propagated tables)"""

@@ -273,10 +273,11 @@ class BaseRunner(object):
                 losses.append(step.run(batch))
                 self._after_step(model)
                 continue
-            item_ids = batch['item_id']
             indices = None
             if not equivariant:
-                # shuffle candidate columns so a model cannot learn "column 0 is the target"
+                # shuffle candidate columns so a model cannot learn "column 0 is the target" (a feed without `item_id` --
+                # CFKG's head / tail / relation triple -- belongs to a model that declares itself equivariant)
+                item_ids = batch['item_id']
                 indices = torch.argsort(torch.rand(*item_ids.shape), dim=-1).to(item_ids.device)
                 batch['item_id'] = torch.gather(item_ids, 1, indices)
             model.optimizer.zero_grad()

@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.join(ROOT, "rechorus_amd", "rechorus"))
 PUBLISHED = {"BPRMF": (0.3549, 0.2486, 2.5), "NeuMF": (0.3237, 0.2221, 3.4), "SASRec": (0.3917, 0.2942, 5.5),
              "LightGCN": (0.3705, 0.2564, 6.1), "DirectAU": (0.3911, 0.2779, 3.3), "ComiRec": (0.3753, 0.2675, 4.5), "BUIR": (0.3701, 0.2567, 3.3),
              "FPMC": (0.3594, 0.2785, 3.4),      # (FPMC: not in the default --models list; Topk_Amazon.sh:18, README.md:52)
-             "SLRCPlus": (0.4376, 0.3263, 4.3)}  # (SLRCPlus: not in the default list either; needs item_meta.csv; README.md:62)
+             "SLRCPlus": (0.4376, 0.3263, 4.3),  # (SLRCPlus: not in the default list either; needs item_meta.csv; README.md:62)
+             "CFKG": (0.4199, 0.2984, 8.7)}      # (CFKG: not in the default list either; needs item_meta.csv; README.md:61)
 FLAGS = {
     "BPRMF": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-6"],
     "NeuMF": ["--emb_size", "64", "--layers", "[64]", "--lr", "5e-4", "--l2", "1e-7", "--dropout", "0.2"],
@@ -30,6 +31,7 @@ FLAGS = {
     "BUIR": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-6"],
     "FPMC": ["--emb_size", "64", "--lr", "1e-3", "--l2", "1e-6", "--history_max", "20"],
     "SLRCPlus": ["--emb_size", "64", "--lr", "5e-4", "--l2", "1e-5", "--history_max", "20"],
+    "CFKG": ["--emb_size", "64", "--margin", "1", "--include_attr", "1", "--lr", "1e-4", "--l2", "1e-6"],
 }
 
 
