@@ -1354,6 +1354,35 @@ enum rc_status rc_cfkg_fwd_bwd(const float* E, const float* R, const int64_t* h,
                                const int64_t* tn, const int64_t* r, int B, int d, int64_t n_rows, int n_rel, float margin, float inv_b,
                                float* loss_vec, float* pred, float* grows, float* GR, void* ws, size_t ws_bytes, rc_stream_t stream);
 
+/* ---- DIN target attention (csrc/din.hip; reference models/context_seq/DIN.py:63-95) ----------------------------------------------
+ * Instance n = b C + c attends over the history of batch row b: q [N, H] (N = B C), keys [B, L, H], lengths [B] (int64):
+ *   s[n, l] = att_mlp(cat[q_n, k_bl, q_n - k_bl, q_n * k_bl]),  w[n, l] = (l < min(len_b, L) ? s[n, l] : 0) / sqrt(H),
+ *   out[n] = sum_l w[n, l] k_bl                      (no softmax; positions l >= len_b are never read; len_b = 0 gives a zero row)
+ * att_mlp (utils/layers.py MLP_Block): n_layers hidden layers Linear(A_{j-1} -> A_j) -> Sigmoid -> Dropout(drop_p), A_0 = 4 H,
+ * A_j = widths[j], then Linear(A_last -> 1).  params is ONE fp32 buffer in definition order
+ *   [W_1 (A_1 x 4H) | b_1 | W_2 (A_2 x A_1) | b_2 | W_3 | b_3 | w_out (A_last) | b_out],   rc_din_param_count floats,
+ * and dparams has the same layout.  The first layer is evaluated folded, z_1 = (Wq + Wd) q + (Wk - Wd) k + Wp (q * k) + b_1 with
+ * W_1 = [Wq | Wk | Wd | Wp]: no [N, L, 4H] or [N, L, A] tensor exists; the summation order differs from the concatenated form.
+ * Dropout: rc_linear_fwd's rule with row m = n L + l, column = hidden unit, site = site0 + layer (0-based).
+ * Envelope (rc_din_check_shape, the one statement of it): H a multiple of 4 in [4, 512]; 1 <= L <= 64; 1 to 3 hidden layers, each a
+ * multiple of 16 in [16, 256], their SUM at most 256 (a tile keeps every layer's activations in LDS); 0 <= drop_p < 1.  Any B, C >= 1. */
+enum rc_status rc_din_check_shape(int H, int L, int n_layers, const int* widths, float drop_p);
+size_t rc_din_param_count(int H, int n_layers, const int* widths);
+/* out: row stride ld_out floats (>= H, a multiple of 4; out 16-byte aligned) so that it can land inside a concatenated input;
+ * att [N, L] (may be NULL): the masked, scaled weights w.                                                                          */
+enum rc_status rc_din_attention_fwd(const float* q, const float* keys, const int64_t* lengths, const float* params, int64_t B, int C,
+                                    int L, int H, int n_layers, const int* widths, float drop_p, const uint64_t* seed_dev,
+                                    uint32_t site0, float* out, int64_t ld_out, float* att, rc_stream_t stream);
+/* given d_out [N, H]: dq [N, H], dkeys [B, L, H] (summed over a row's C candidates; 0 at l >= len_b), dparams; everything is
+ * recomputed from q, keys and params (same seed and site0 as the forward).  No float atomics: a workgroup owns whole batch rows and
+ * accumulates the parameter gradients in its own slice of ws, the slices are summed in workgroup order: two runs are bit-equal.
+ * ws: 16-byte aligned, rc_din_attention_bwd_workspace_bytes(B, H, n_layers, widths) bytes.                                          */
+size_t rc_din_attention_bwd_workspace_bytes(int64_t B, int H, int n_layers, const int* widths);
+enum rc_status rc_din_attention_bwd(const float* q, const float* keys, const int64_t* lengths, const float* params,
+                                    const float* d_out, int64_t B, int C, int L, int H, int n_layers, const int* widths, float drop_p,
+                                    const uint64_t* seed_dev, uint32_t site0, float* dq, float* dkeys, float* dparams, void* ws,
+                                    size_t ws_bytes, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

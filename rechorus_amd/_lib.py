@@ -95,6 +95,7 @@ _sz = C.c_size_t
 _hp = C.POINTER(OptHyper)
 _gp = C.POINTER(LgcnGraph)
 _dbl = C.c_double
+_ip = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); must list every symbol include/rechorus_hip.h declares
 SIGNATURES = {
@@ -285,6 +286,11 @@ SIGNATURES = {
     "rc_cfkg_scores_bwd": (_i, [_p] * 6 + [_i, _i, _i, _i64, _i, _p, _p]),
     "rc_cfkg_fwd_bwd_workspace_bytes": (_sz, [_i64, _i, _i]),
     "rc_cfkg_fwd_bwd": (_i, [_p] * 7 + [_i, _i, _i64, _i, _f, _f] + [_p] * 5 + [_sz, _p]),
+    "rc_din_check_shape": (_i, [_i, _i, _i, _ip, _f]),
+    "rc_din_param_count": (_sz, [_i, _i, _ip]),
+    "rc_din_attention_fwd": (_i, [_p] * 4 + [_i64, _i, _i, _i, _i, _ip, _f, _p, C.c_uint32, _p, _i64, _p, _p]),
+    "rc_din_attention_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _ip]),
+    "rc_din_attention_bwd": (_i, [_p] * 5 + [_i64, _i, _i, _i, _i, _ip, _f, _p, C.c_uint32] + [_p] * 4 + [_sz, _p]),
 }
 
 _lib = None

@@ -48,6 +48,7 @@ SOURCES = [
     "fpmc.hip",
     "slrc.hip",
     "cfkg.hip",
+    "din.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -3487,3 +3487,70 @@ class CfkgTrainer:
         m, v = self._mv("R")
         dense_update(self.R, GR, self.hyper, m=m, v=v)
         return loss
+
+
+# ---- DIN: target attention over the history (models/context_seq/DIN.py:63-95; csrc/din.hip) --------------------------------------
+
+def _din_widths(widths):
+    widths = [int(w) for w in widths]
+    return len(widths), (C.c_int * max(len(widths), 1))(*widths)
+
+
+def din_check_shape(H, L, widths, drop_p=0.0):
+    """rc_din_check_shape (host logic), the one statement of the envelope: H a multiple of 4 in [4, 512], 1 <= L <= 64, 1 to 3 hidden
+    widths, each a multiple of 16 in [16, 256] and at most 256 in all, 0 <= drop_p < 1; raises ValueError with the library's reason"""
+    lib = _lib.load()
+    n, arr = _din_widths(widths)
+    if lib.rc_din_check_shape(int(H), int(L), n, arr, C.c_float(float(drop_p))) != _lib.RC_OK:
+        raise ValueError("DIN attention on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def din_param_count(H, widths):
+    """floats of the attention MLP's parameters in definition order [W_1 | b_1 | W_2 | b_2 | W_3 | b_3 | w_out | b_out]"""
+    n, arr = _din_widths(widths)
+    return int(_lib.load().rc_din_param_count(int(H), n, arr))
+
+
+def _din_shapes(q, keys, lengths, params, n_cand, widths):
+    if keys.dim() != 3 or q.dim() != 2 or q.shape[1] != keys.shape[2] or q.shape[0] != keys.shape[0] * n_cand:
+        raise ValueError(f"DIN attention: q [B * C, H] and keys [B, L, H] do not fit: {tuple(q.shape)}, {tuple(keys.shape)}, C={n_cand}")
+    B, L, H = keys.shape
+    if lengths.shape != (B,):
+        raise ValueError(f"DIN attention: lengths must be [B], got {tuple(lengths.shape)}")
+    din_check_shape(H, L, widths)
+    if params.dim() != 1 or params.numel() != din_param_count(H, widths):
+        raise ValueError(f"DIN attention: params must hold {din_param_count(H, widths)} floats, got {tuple(params.shape)}")
+    return B, L, H
+
+
+def din_attention_fwd(q, keys, lengths, params, n_cand, widths, drop_p=0.0, seed=None, site0=0, out=None, want_att=False):
+    """rc_din_attention_fwd: out[n] = sum_l w[n, l] keys[b, l] with the masked, scaled attention weights w of DIN.attention.
+    q [B * C, H], keys [B, L, H], lengths int64 [B], params: the attention MLP flat in definition order.
+    out: None (a fresh [N, H]) or a 2-D view with unit column stride whose row stride is a multiple of 4 (a slice of a wider buffer).
+    Returns (out, att [N, L] | None)."""
+    B, L, H = _din_shapes(q, keys, lengths, params, n_cand, widths)
+    f32, N = torch.float32, q.shape[0]
+    if out is None:
+        out = torch.empty((N, H), dtype=f32, device=q.device)
+    if out.dtype != f32 or not out.is_cuda or out.shape != (N, H) or out.stride(1) != 1:
+        raise ValueError("DIN attention: out must be a float32 [N, H] GPU view with unit column stride")
+    att = torch.empty((N, L), dtype=f32, device=q.device) if want_att else None
+    n, arr = _din_widths(widths)
+    _lib.call("rc_din_attention_fwd", _ptr(q, f32, "q"), _ptr(keys, f32, "keys"), _ptr(lengths, torch.int64, "lengths"),
+              _ptr(params, f32, "params"), B, int(n_cand), L, H, n, arr, *_drop_args(drop_p, seed), C.c_uint32(int(site0)),
+              C.c_void_p(out.data_ptr()), out.stride(0), _ptr(att, f32, "att", True), _stream())
+    return out, att
+
+
+def din_attention_bwd(q, keys, lengths, params, d_out, n_cand, widths, drop_p=0.0, seed=None, site0=0):
+    """rc_din_attention_bwd: (dq [N, H], dkeys [B, L, H], dparams) for a given d_out [N, H]; everything recomputed from the inputs
+    with the forward's seed and site0.  No float atomics: two runs are bit-equal."""
+    B, L, H = _din_shapes(q, keys, lengths, params, n_cand, widths)
+    f32, dev = torch.float32, q.device
+    dq, dkeys, dparams = torch.empty_like(q), torch.empty_like(keys), torch.empty_like(params)
+    n, arr = _din_widths(widths)
+    ws = workspace(_lib.load().rc_din_attention_bwd_workspace_bytes(B, H, n, arr), dev, "din_bwd")
+    _lib.call("rc_din_attention_bwd", _ptr(q, f32, "q"), _ptr(keys, f32, "keys"), _ptr(lengths, torch.int64, "lengths"),
+              _ptr(params, f32, "params"), _ptr(d_out, f32, "d_out"), B, int(n_cand), L, H, n, arr, *_drop_args(drop_p, seed),
+              C.c_uint32(int(site0)), _ptr(dq, f32, "dq"), _ptr(dkeys, f32, "dkeys"), _ptr(dparams, f32, "dparams"), *_ws_args(ws))
+    return dq, dkeys, dparams

@@ -220,6 +220,41 @@ def cfkg_scores(E, R, head, tail, rel):
     return _CfkgScoreFn.apply(E, R, head.contiguous(), tail.contiguous(), rel.contiguous())
 
 
+class _DinAttentionFn(torch.autograd.Function):
+    """DIN.attention (models/context_seq/DIN.py:63-95) for instance n = b C + c over the history of row b, as ONE node: the forward
+    keeps q, keys and the flat parameters; the backward recomputes everything from them (same dropout seed and site)."""
+
+    @staticmethod
+    def forward(ctx, q, keys, lengths, flat, n_cand, widths, drop_p, seed, site0):
+        q, keys, flat = q.detach().contiguous(), keys.detach().contiguous(), flat.detach().contiguous()
+        # the seed's VALUE at the forward: the caller may bump the device counter before the backward recomputes the mask
+        seed = seed.clone() if (drop_p and seed is not None) else None
+        ctx.save_for_backward(q, keys, lengths, flat, seed)
+        ctx.args = (n_cand, widths, drop_p, site0)
+        out, att = engine.din_attention_fwd(q, keys, lengths, flat, n_cand, widths, drop_p, seed, site0, want_att=True)
+        ctx.mark_non_differentiable(att)
+        return out, att
+
+    @staticmethod
+    def backward(ctx, d_out, _d_att):
+        q, keys, lengths, flat, seed = ctx.saved_tensors
+        n_cand, widths, drop_p, site0 = ctx.args
+        dq, dkeys, dflat = engine.din_attention_bwd(q, keys, lengths, flat, d_out.contiguous(), n_cand, widths, drop_p, seed, site0)
+        return dq, dkeys, None, dflat, None, None, None, None, None
+
+
+def din_attention(q, keys, lengths, n_cand, params, drop_p=0.0, seed=None, site0=0):
+    """DIN's target attention as one autograd node.  q [B * n_cand, H], keys [B, L, H], lengths int64 [B];
+    params = [(W_1, b_1), ..., (W_k, b_k), (w_out, b_out)]: the Linear layers of att_mlp_layers in order (Sigmoid and Dropout(drop_p)
+    behind every hidden one).  Returns (out [N, H], att [N, L]): the weighted key sum and the masked, scaled weights (the reference's
+    return_seq_weight; no gradient flows through att).  drop_p > 0 (training): `seed` int64 [1] on the device, layers use sites
+    site0, site0 + 1, ...  The parameters travel as one flat buffer (a torch.cat of a few thousand floats, whose autograd hands every
+    layer its slice of the flat gradient); nothing of N * L rows exists outside the kernels."""
+    widths = tuple(int(W.shape[0]) for W, _ in params[:-1])
+    flat = torch.cat([t.reshape(-1) for pair in params for t in pair])
+    return _DinAttentionFn.apply(q, keys, lengths.contiguous(), flat, int(n_cand), widths, float(drop_p), seed if drop_p else None, int(site0))
+
+
 def table_rows(W, ids):
     """W[ids] with an autograd that sums the rows' gradients into a dense [n_rows, d] tensor (HipEmbedding's lookup on a table
     that is not a module's Parameter, e.g. LightGCN's propagated tables)"""

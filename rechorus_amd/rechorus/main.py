@@ -28,7 +28,7 @@ for p in (HERE, ROOT):
 
 from utils import utils  # noqa: E402
 
-MODEL_PACKAGES = ('models.general', 'models.sequential', 'models.context')
+MODEL_PACKAGES = ('models.general', 'models.sequential', 'models.context', 'models.context_seq')
 
 
 def parse_global_args(parser):

@@ -3,13 +3,14 @@ ContextModel (top-k ranking with BPR or BCE loss) and ContextCTRModel (labelled 
 Both add the corpus' user / item / situation features to every feed dict; the model sees them
 as extra int (or float) tensors keyed by feature name next to 'user_id' / 'item_id'.
 
-The history-aware ContextSeq* bases (reference :91-166, reader ContextSeqReader) are not part of
-this engine's path.
+ContextSeqModel / ContextSeqCTRModel (reference :89-166, reader helpers.ContextSeqReader) add the user's history to the
+feed: `history_item_id`, `history_<item feature>`, with --add_historical_situations 1 also `history_<situation feature>`, and
+`lengths`; histories are cut to the last --history_max interactions and instances without history are dropped.
 """
 import numpy as np
 import torch
 
-from models.BaseModel import GeneralModel, CTRModel
+from models.BaseModel import GeneralModel, CTRModel, SequentialModel
 from rechorus_amd import nn as hnn
 
 
@@ -75,3 +76,76 @@ class ContextCTRModel(CTRModel):
         def _get_feed_dict(self, index):
             feed = super()._get_feed_dict(index)
             return get_context_feature(feed, index, self.corpus, self.data)
+
+
+def _seq_flags(parser):
+    parser.add_argument('--history_max', type=int, default=20, help='Maximum length of history.')
+    parser.add_argument('--add_historical_situations', type=int, default=0,
+                        help='Whether to add historical situation context as sequence.')
+    return parser
+
+
+def _history_context(feed, model, corpus, user_seq):
+    """the history's item features per position, its situation features where the model asks for them, and the reference's key
+    `history_item_id` for the item ids (:117-123, :159-165)"""
+    items = feed.pop('history_items')
+    for c in corpus.item_feature_names:
+        feed['history_' + c] = np.array([corpus.item_features[i][c] for i in items])
+    if model.add_historical_situations:
+        for k, c in enumerate(corpus.situation_feature_names):
+            feed['history_' + c] = np.array([inter[-1][k] for inter in user_seq])
+    feed['history_item_id'] = items
+    return feed
+
+
+def _cut_history(model, corpus, user_id, position):
+    seq = corpus.user_his[user_id][:position]
+    return seq[-model.history_max:] if model.history_max > 0 else seq
+
+
+class ContextSeqModel(ContextModel):
+    reader = 'ContextSeqReader'
+
+    @staticmethod
+    def parse_model_args(parser):
+        return ContextModel.parse_model_args(_seq_flags(parser))
+
+    def __init__(self, args, corpus):
+        super().__init__(args, corpus)
+        self.history_max = args.history_max
+        self.add_historical_situations = args.add_historical_situations
+
+    class Dataset(SequentialModel.Dataset):
+        def _get_feed_dict(self, index):
+            feed = super()._get_feed_dict(index)      # user, candidates, history_items / history_times / lengths
+            seq = _cut_history(self.model, self.corpus, feed['user_id'], self.data['position'][index])
+            feed = get_context_feature(feed, index, self.corpus, self.data)
+            return _history_context(feed, self.model, self.corpus, seq)
+
+
+class ContextSeqCTRModel(ContextCTRModel):
+    reader = 'ContextSeqReader'
+
+    @staticmethod
+    def parse_model_args(parser):
+        return ContextCTRModel.parse_model_args(_seq_flags(parser))
+
+    def __init__(self, args, corpus):
+        super().__init__(args, corpus)
+        self.history_max = args.history_max
+        self.add_historical_situations = args.add_historical_situations
+
+    class Dataset(ContextCTRModel.Dataset):
+        def __init__(self, model, corpus, phase):
+            super().__init__(model, corpus, phase)
+            keep = np.array(self.data['position']) > 0      # the history must not be empty
+            for col in self.data:
+                self.data[col] = np.array(self.data[col])[keep]
+
+        def _get_feed_dict(self, index):
+            feed = super()._get_feed_dict(index)
+            seq = _cut_history(self.model, self.corpus, feed['user_id'], self.data['position'][index])
+            feed['history_items'] = np.array([x[0] for x in seq])
+            feed['history_times'] = np.array([x[1] for x in seq])
+            feed['lengths'] = len(seq)
+            return _history_context(feed, self.model, self.corpus, seq)
