@@ -1383,6 +1383,39 @@ enum rc_status rc_din_attention_bwd(const float* q, const float* keys, const int
                                     const uint64_t* seed_dev, uint32_t site0, float* dq, float* dkeys, float* dparams, void* ws,
                                     size_t ws_bytes, rc_stream_t stream);
 
+/* ---- KDA relational dynamic aggregation (csrc/kda.hip; reference models/sequential/KDA.py:265-303) --------------------------------
+ * fp32 rows already gathered, 16-byte aligned: seq [B, L, V] (history), target [B, C, V], value [B, C, R, V], rel [R, V]; hist [B, L]
+ * int64 (position l of row b is valid iff hist[b, l] > 0; invalid positions may sit anywhere), delta_t [B, L] fp32, freq_real /
+ * freq_imag [R, F].  Per (b, c, r):
+ *   ri = (rel[r] + value[b, c, r]) * target[b, c]   (include_val == 0: ri = rel[r] * target[b, c], value is not read and may be NULL)
+ *   a[l] = <seq[b, l], ri>,  p = softmax of a over the valid l (the maximum subtracted is the one over the valid l of this (b, c, r);
+ *          the reference subtracts the global maximum, KDA.py:296, which for finite inputs gives the same p)
+ *   decay[b, l, r] = clamp((1 / (2 * 2F)) sum_{k < 2F} (cos(w_k) xr[r, k] - sin(w_k) xi[r, k]), 0, 1),  w_k = 2 pi f_k delta_t[b, l],
+ *          f = concat(linspace(0, 1, F) / 2, -linspace(0, 1, F) / 2), xr = [real, real], xi = [imag, -imag]        (KDA.py:276-285, :299)
+ *   context[b, c, r] = sum_l p[l] decay[b, l, r] seq[b, l]                                                          (KDA.py:300-302)
+ * The decay is computed once per batch row; no tensor larger than the [B, C, R, V] output exists (the reference materialises two
+ * [B, C, L, R, V] products).  A row WITHOUT any valid position gives a zero context and zero gradients (the reference: NaN).
+ * sin / cos are the accurate ones (arguments reach about 100 rad).
+ * Envelope (rc_kda_check_shape, the one statement of it): V in {16, 32, 64, 128}, 1 <= L <= 64, 1 <= R <= 8, 2 <= F <= 129;
+ * any B, C >= 1.                                                                                                                    */
+enum rc_status rc_kda_check_shape(int V, int L, int R, int F);
+/* RelationalDynamicAggregation.forward (KDA.py:287-303): context [B, C, R, V], one launch */
+enum rc_status rc_kda_aggregate_fwd(const float* seq, const int64_t* hist, const float* delta_t, const float* target,
+                                    const float* value, const float* rel, const float* freq_real, const float* freq_imag, int64_t B,
+                                    int C, int L, int R, int V, int F, int include_val, float* context, rc_stream_t stream);
+/* the backward of KDA.py:276-303 for a given d_context [B, C, R, V]: dseq [B, L, V] (through the score and through the sum, summed
+ * over C and R), dtarget [B, C, V], dvalue [B, C, R, V] (include_val only, else not written and may be NULL), drel [R, V],
+ * dfreq_real / dfreq_imag [R, F]; the clamp's gradient passes where 0 <= x <= 1.  Everything is recomputed from the inputs, nothing
+ * of size B C L R is kept.  No atomics: a workgroup owns whole batch rows and accumulates drel / dfreq_* in its own slice of ws, the
+ * slices are summed in workgroup order: two runs are bit-equal.
+ * ws: 16-byte aligned, rc_kda_aggregate_bwd_workspace_bytes(B, R, V, F) bytes.                                                      */
+size_t rc_kda_aggregate_bwd_workspace_bytes(int64_t B, int R, int V, int F);
+enum rc_status rc_kda_aggregate_bwd(const float* seq, const int64_t* hist, const float* delta_t, const float* target,
+                                    const float* value, const float* rel, const float* freq_real, const float* freq_imag,
+                                    const float* d_context, int64_t B, int C, int L, int R, int V, int F, int include_val, float* dseq,
+                                    float* dtarget, float* dvalue, float* drel, float* dfreq_real, float* dfreq_imag, void* ws,
+                                    size_t ws_bytes, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

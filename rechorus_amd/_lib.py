@@ -291,6 +291,10 @@ SIGNATURES = {
     "rc_din_attention_fwd": (_i, [_p] * 4 + [_i64, _i, _i, _i, _i, _ip, _f, _p, C.c_uint32, _p, _i64, _p, _p]),
     "rc_din_attention_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _ip]),
     "rc_din_attention_bwd": (_i, [_p] * 5 + [_i64, _i, _i, _i, _i, _ip, _f, _p, C.c_uint32] + [_p] * 4 + [_sz, _p]),
+    "rc_kda_check_shape": (_i, [_i, _i, _i, _i]),
+    "rc_kda_aggregate_fwd": (_i, [_p] * 8 + [_i64, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "rc_kda_aggregate_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_kda_aggregate_bwd": (_i, [_p] * 9 + [_i64, _i, _i, _i, _i, _i, _i] + [_p] * 7 + [_sz, _p]),
 }
 
 _lib = None

@@ -49,6 +49,7 @@ SOURCES = [
     "slrc.hip",
     "cfkg.hip",
     "din.hip",
+    "kda.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -3554,3 +3554,73 @@ def din_attention_bwd(q, keys, lengths, params, d_out, n_cand, widths, drop_p=0.
               _ptr(params, f32, "params"), _ptr(d_out, f32, "d_out"), B, int(n_cand), L, H, n, arr, *_drop_args(drop_p, seed),
               C.c_uint32(int(site0)), _ptr(dq, f32, "dq"), _ptr(dkeys, f32, "dkeys"), _ptr(dparams, f32, "dparams"), *_ws_args(ws))
     return dq, dkeys, dparams
+
+
+# ---- KDA: relational dynamic aggregation (models/sequential/KDA.py:265-303; csrc/kda.hip) ---------------------------------------------
+
+def kda_check_shape(V, L, R, F):
+    """rc_kda_check_shape (host logic), the one statement of the envelope: V in {16, 32, 64, 128}, 1 <= L <= 64, 1 <= R <= 8,
+    2 <= F <= 129; raises ValueError with the library's reason"""
+    lib = _lib.load()
+    if lib.rc_kda_check_shape(int(V), int(L), int(R), int(F)) != _lib.RC_OK:
+        raise ValueError("KDA aggregation on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def _kda_shapes(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val):
+    if seq.dim() != 3 or target.dim() != 3 or target.shape[0] != seq.shape[0] or target.shape[2] != seq.shape[2]:
+        raise ValueError(f"KDA aggregation: seq [B, L, V] and target [B, C, V] do not fit: {tuple(seq.shape)}, {tuple(target.shape)}")
+    (B, L, V), Cn = seq.shape, target.shape[1]
+    if rel.dim() != 2 or rel.shape[1] != V:
+        raise ValueError(f"KDA aggregation: rel must be [R, {V}], got {tuple(rel.shape)}")
+    R = rel.shape[0]
+    if freq_real.dim() != 2 or freq_real.shape[0] != R or freq_imag.shape != freq_real.shape:
+        raise ValueError(f"KDA aggregation: freq_real and freq_imag must both be [{R}, F], got {tuple(freq_real.shape)}, "
+                         f"{tuple(freq_imag.shape)}")
+    F = freq_real.shape[1]
+    if hist.shape != (B, L) or delta_t.shape != (B, L):
+        raise ValueError(f"KDA aggregation: hist and delta_t must be [{B}, {L}], got {tuple(hist.shape)}, {tuple(delta_t.shape)}")
+    if include_val and (value is None or value.shape != (B, Cn, R, V)):
+        raise ValueError(f"KDA aggregation: value must be [{B}, {Cn}, {R}, {V}], got {None if value is None else tuple(value.shape)}")
+    if Cn < 1:
+        raise ValueError("KDA aggregation: need at least one candidate")
+    kda_check_shape(V, L, R, F)
+    return B, Cn, L, R, V, F
+
+
+def _kda_inputs(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val):
+    f32 = torch.float32
+    return (_ptr(seq, f32, "seq"), _ptr(hist, torch.int64, "hist"), _ptr(delta_t, f32, "delta_t"), _ptr(target, f32, "target"),
+            _ptr(value if include_val else None, f32, "value", True), _ptr(rel, f32, "rel"), _ptr(freq_real, f32, "freq_real"),
+            _ptr(freq_imag, f32, "freq_imag"))
+
+
+def kda_aggregate_fwd(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val=True):
+    """rc_kda_aggregate_fwd: context [B, C, R, V] = sum_l softmax_l(<seq[b, l], ri>)[l] decay[b, l, r] seq[b, l] over the valid l
+    (hist > 0), ri = (rel[r] + value[b, c, r]) * target[b, c] (include_val) or rel[r] * target[b, c]; one launch.  A row without a
+    valid position gives zeros."""
+    B, Cn, L, R, V, F = _kda_shapes(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val)
+    ctx = torch.empty((B, Cn, R, V), dtype=torch.float32, device=seq.device)
+    if B:
+        _lib.call("rc_kda_aggregate_fwd", *_kda_inputs(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val),
+                  B, Cn, L, R, V, F, int(bool(include_val)), _ptr(ctx, torch.float32, "context"), _stream())
+    return ctx
+
+
+def kda_aggregate_bwd(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, d_context, include_val=True):
+    """rc_kda_aggregate_bwd: (dseq, dtarget, dvalue | None, drel, dfreq_real, dfreq_imag) for a given d_context [B, C, R, V];
+    everything recomputed from the inputs.  No atomics: two runs are bit-equal."""
+    B, Cn, L, R, V, F = _kda_shapes(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val)
+    f32, dev = torch.float32, seq.device
+    if d_context.shape != (B, Cn, R, V):
+        raise ValueError(f"KDA aggregation: d_context must be [{B}, {Cn}, {R}, {V}], got {tuple(d_context.shape)}")
+    dseq, dtarget = torch.empty_like(seq), torch.empty_like(target)
+    dvalue = torch.empty((B, Cn, R, V), dtype=f32, device=dev) if include_val else None
+    drel, dfr, dfi = torch.empty_like(rel), torch.empty_like(freq_real), torch.empty_like(freq_imag)
+    if not B:
+        return dseq, dtarget, dvalue, drel.zero_(), dfr.zero_(), dfi.zero_()
+    ws = workspace(_lib.load().rc_kda_aggregate_bwd_workspace_bytes(B, R, V, F), dev, "kda_bwd")
+    _lib.call("rc_kda_aggregate_bwd", *_kda_inputs(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val),
+              _ptr(d_context, f32, "d_context"), B, Cn, L, R, V, F, int(bool(include_val)), _ptr(dseq, f32, "dseq"),
+              _ptr(dtarget, f32, "dtarget"), _ptr(dvalue, f32, "dvalue", True), _ptr(drel, f32, "drel"), _ptr(dfr, f32, "dfreq_real"),
+              _ptr(dfi, f32, "dfreq_imag"), *_ws_args(ws))
+    return dseq, dtarget, dvalue, drel, dfr, dfi

@@ -255,6 +255,34 @@ def din_attention(q, keys, lengths, n_cand, params, drop_p=0.0, seed=None, site0
     return _DinAttentionFn.apply(q, keys, lengths.contiguous(), flat, int(n_cand), widths, float(drop_p), seed if drop_p else None, int(site0))
 
 
+class _KdaAggregateFn(torch.autograd.Function):
+    """RelationalDynamicAggregation.forward (models/sequential/KDA.py:265-303) as ONE node: the forward keeps its inputs, the backward
+    recomputes everything from them (nothing of size B C L R is kept)."""
+
+    @staticmethod
+    def forward(ctx, seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val):
+        seq, target, rel = seq.detach().contiguous(), target.detach().contiguous(), rel.detach().contiguous()
+        value = value.detach().contiguous() if include_val else None
+        freq_real, freq_imag = freq_real.detach().contiguous(), freq_imag.detach().contiguous()
+        ctx.include_val = include_val
+        ctx.save_for_backward(seq, hist, delta_t, target, value, rel, freq_real, freq_imag)
+        return engine.kda_aggregate_fwd(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val)
+
+    @staticmethod
+    def backward(ctx, d_context):
+        dseq, dtarget, dvalue, drel, dfr, dfi = engine.kda_aggregate_bwd(*ctx.saved_tensors, d_context.contiguous(), ctx.include_val)
+        return dseq, None, None, dtarget, dvalue, drel, dfr, dfi, None
+
+
+def kda_aggregate(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val=True):
+    """KDA's relational dynamic aggregation as one autograd node.  seq [B, L, V] history rows, hist int64 [B, L] (valid iff > 0, anywhere
+    in the row), delta_t fp32 [B, L], target [B, C, V], value [B, C, R, V] (read only with include_val; may be None without), rel [R, V],
+    freq_real / freq_imag [R, F].  Returns context [B, C, R, V]; gradients flow to seq, target, value, rel and both frequency tables.
+    A row without a valid position gives a zero context and zero gradients."""
+    return _KdaAggregateFn.apply(seq, hist.contiguous(), delta_t.float().contiguous(), target, value if include_val else None, rel,
+                                 freq_real, freq_imag, bool(include_val))
+
+
 def table_rows(W, ids):
     """W[ids] with an autograd that sums the rows' gradients into a dense [n_rows, d] tensor (HipEmbedding's lookup on a table
     that is not a module's Parameter, e.g. LightGCN's propagated tables)"""
