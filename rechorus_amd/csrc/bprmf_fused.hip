@@ -13,8 +13,9 @@
 // lives in one wave's VGPRs (100 VGPRs/lane), so the backward pass (user-row gradient
 // sum_c g_c * I_c, which needs every row again after the softmax over all K negatives is
 // known) re-reads nothing from HBM, and the only cross-lane traffic is DPP row reductions +
-// a few ds_bpermute across the GS groups.  The only LDS use is a strip of C floats per tuple that
-// transposes the scores so that the loss is evaluated one lane per candidate (fused_body.hpp).
+// a few ds_bpermute across the GS groups.  LDS holds a strip of C floats per tuple that transposes the
+// scores so that the loss is evaluated one lane per candidate, and (one tuple per wave, C <= 128) a strip
+// of the tuple's ids, read once from memory and handed to the lane-groups (fused_body.hpp).
 // Small C packs several tuples per wave (C=2: two 32-lane tuples).
 //
 // Singleton rows (MODE != MODE_NONE).  An item row that occurs exactly once in the batch is

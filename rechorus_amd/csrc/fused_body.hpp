@@ -49,56 +49,102 @@ template <int CPL_, int MODE_>
 constexpr int fused_min_waves() {
   return (MODE_ == MODE_ADAM || MODE_ == MODE_ADAGRAD) ? (CPL_ >= 20 ? 2 : 3) : (CPL_ >= 26 ? 2 : (CPL_ >= 20 ? 3 : 4));
 }
-// The body of the fused kernel for workgroup `block` of NT threads (the stand-alone kernel: NT = kBlock and its own
-// workgroup index; the small-batch step, small_step.hip, runs it in the upper part of a merged grid).  ub: optional
+// A wave's work on one tuple comes in parts.  fused_load_ids reads the tuple's ids; fused_request issues every load of the
+// tuple from those ids (the user row, the CPL candidate rows of each lane-group, the bitmap words or flag bytes): ONE
+// memory round trip.  fused_scores (scores -> strip) and fused_finish (loss -> gpred / loss_vec -> backward -> singleton
+// write-back -> ugrad) are everything behind it.  bprmf_fwd_bwd_body runs the parts once per tuple.
+template <int D, int GS, int CPL>
+struct FusedGeom {
+  static constexpr int LPR = D / 4;
+  static constexpr int S = LPR * GS;
+  static_assert(S <= 64 && (64 % S) == 0, "tuple must fit a wave");
+  static constexpr int TPW = 64 / S;          // tuples per wave
+  static constexpr int SLOTS = GS * CPL;      // strip length (>= C)
+  static constexpr int NPL = (SLOTS + S - 1) / S;  // candidates per lane in the loss phase
+  // the tuple's ids are read once, coalesced: two registers per lane (candidates lane, lane + 64), handed to the lane-groups
+  // through an LDS strip of SLOTS ids; otherwise every lane-group loads its CPL ids from memory itself.  C <= SLOTS, and the
+  // dispatch picks SLOTS <= 128 exactly when C <= 128.
+  static constexpr bool COAL = S == 64 && SLOTS <= 128;
+  static constexpr int ID_SLOTS = COAL ? SLOTS : 1;  // int64 per tuple in LDS
+};
+
+// the ids of one tuple as its wave holds them
+struct TupleIds {
+  int64_t u;       // uid[t]
+  int64_t ia, ib;  // COAL only: iid[t, lane] and iid[t, lane + 64], clamped to candidate 0 past C (ib unused when SLOTS <= 64)
+};
+
+template <int D, int GS, int CPL>
+__device__ __forceinline__ TupleIds fused_load_ids(const int64_t* __restrict__ uid, const int64_t* __restrict__ iid, int64_t t,
+                                                   int C, int lane) {
+  using G = FusedGeom<D, GS, CPL>;
+  TupleIds k;
+  k.u = uid[t];
+  k.ia = k.ib = 0;
+  if (G::COAL) {
+    const int64_t* ids = iid + t * C;
+    const int c0 = lane, c1 = lane + 64;
+    k.ia = ids[c0 < C ? c0 : 0];
+    if (G::SLOTS > 64) k.ib = ids[c1 < C ? c1 : 0];
+  }
+  return k;
+}
+
+// COAL: hand the wave's id registers to the lane-groups.  id_strip[c] = id of candidate c (candidate 0 past C); a
+// lane-group reads its slot j as id_strip[j * GS + grp], also inside a divergent branch (the write-back).  A shuffle would
+// do for the gather, but the write-back's shuffles have to stand ahead of its branches, where the compiler hoists all CPL
+// of them above the row registers (scratch at <64, 4, 25, SGD>).
+template <int SLOTS>
+__device__ __forceinline__ void fused_stage_ids(const TupleIds& ti, int lane, int64_t* id_strip) {
+  if (lane < SLOTS) id_strip[lane] = ti.ia;
+  if (SLOTS > 64 && lane + 64 < SLOTS) id_strip[lane + 64] = ti.ib;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// what fused_request leaves in registers for fused_finish
+template <int CPL>
+struct FusedRows {
+  float4 u4;
+  float4 r[CPL];
+  unsigned smask;  // bit j: candidate slot j of this group is a singleton row
+};
+
+// Issue the loads of tuple t (tv: the tuple exists; t is clamped otherwise); COAL: ti is staged in id_strip.  ub: optional
 // [B, D] snapshot of the batch's user rows (the small-batch step updates U and I in ONE later launch, so the item side
 // must not read U any more).
-template <int D, int GS, int CPL, int MODE, int NT>
-__device__ __forceinline__ void bprmf_fwd_bwd_body(
-    const float* __restrict__ U, const float* I,
-    const int64_t* __restrict__ uid, const int64_t* __restrict__ iid, int B, int C,
-    float inv_b, float* __restrict__ pred, float* __restrict__ loss_vec,
-    float* __restrict__ gpred, float* __restrict__ ugrad, const FusedUpd& upd, int64_t block, float* __restrict__ ub) {
-  constexpr int LPR = D / 4;
-  constexpr int S = LPR * GS;
-  static_assert(S <= 64 && (64 % S) == 0, "tuple must fit a wave");
-  constexpr int TPW = 64 / S;          // tuples per wave
-  constexpr int SLOTS = GS * CPL;      // strip length (>= C)
-  constexpr int NPL = (SLOTS + S - 1) / S;  // candidates per lane in the loss phase
-  __shared__ float strip_mem[(NT / 64) * TPW * SLOTS];
-
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = block * (NT / 64) + (threadIdx.x >> 6);
-  const int64_t t_raw = wave * TPW + lane / S;
-  const bool tv = t_raw < B;
-  const int64_t t = tv ? t_raw : (int64_t)B - 1;  // clamp: every lane stays in the shuffles
+template <int D, int GS, int CPL, int MODE>
+__device__ __forceinline__ void fused_request(
+    const float* __restrict__ U, const float* I, const int64_t* __restrict__ iid, int C, const FusedUpd& upd,
+    float* __restrict__ ub, const TupleIds& ti, int64_t t, bool tv, int lane, const int64_t* id_strip, FusedRows<CPL>& f) {
+  using G = FusedGeom<D, GS, CPL>;
+  constexpr int LPR = G::LPR, S = G::S;
   const int sub = lane % S;
   const int grp = sub / LPR;
   const int l = sub % LPR;
-  float* strip = strip_mem + ((threadIdx.x >> 6) * TPW + lane / S) * SLOTS;
+  float4 (&r)[CPL] = f.r;
 
   // ---- gather: user row, then this group's CPL candidate rows, all loads in flight
-  const int64_t u = uid[t];
-  const float4 u4 = reinterpret_cast<const float4*>(U + u * D)[l];
+  const float4 u4 = reinterpret_cast<const float4*>(U + ti.u * D)[l];
   if (ub != nullptr && tv && grp == 0) reinterpret_cast<float4*>(ub + t * D)[l] = u4;
+  f.u4 = u4;
   const int64_t* ids = iid + t * C;
-  float4 r[CPL];
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
     const int c = j * GS + grp;
-    const int64_t id = ids[c < C ? c : 0];  // slots past C re-read candidate 0; masked below
+    const int64_t id = G::COAL ? id_strip[c] : ids[c < C ? c : 0];  // slots past C re-read candidate 0; masked below
     r[j] = load_stream4(reinterpret_cast<const float4*>(I + id * D) + l);
   }
   unsigned smask = 0;  // bit j: candidate slot j of this group is a singleton row
   if (MODE != MODE_NONE && upd.multi != nullptr) {
     // bucket plan: the singleton information is a bitmap over item ids (1.25 MB at 10 M rows: L2-resident).  Lane i
-    // looks up candidates i, i + 64, ... of its tuple (the id loads are coalesced and hit the lines the row gathers
-    // above brought in), a ballot turns the bits into wave-uniform masks, and every lane-group picks its candidates'
-    // bits out of them -- no per-position flag array exists in HBM any more.
-    if (S == 64 && C <= 128) {
+    // looks up candidates i and i + 64 of its tuple (the two id registers it holds), a ballot turns the bits into
+    // wave-uniform masks, and every lane-group picks its candidates' bits out of them -- no per-position flag array
+    // exists in HBM any more.
+    if (G::COAL) {
       const int c0 = lane, c1 = lane + 64;
-      const int64_t ia = ids[c0 < C ? c0 : 0];
-      const int64_t ib = ids[c1 < C ? c1 : 0];
+      const int64_t ia = ti.ia, ib = ti.ib;
       const uint32_t wa = upd.multi[ia >> 5];
       const uint32_t wb = C > 64 ? upd.multi[ib >> 5] : 0u;
       const uint64_t m_lo = __ballot(c0 < C && ((wa >> (ia & 31)) & 1u));
@@ -137,8 +183,19 @@ __device__ __forceinline__ void bprmf_fwd_bwd_body(
       }
     }
   }
+  f.smask = smask;
+}
 
-  // ---- scores -> strip
+// scores -> strip (this tuple's SLOTS floats of LDS): the first use of the rows
+template <int D, int GS, int CPL>
+__device__ __forceinline__ void fused_scores(int lane, float* strip, const FusedRows<CPL>& f) {
+  using G = FusedGeom<D, GS, CPL>;
+  constexpr int LPR = G::LPR;
+  const int sub = lane % G::S;
+  const int grp = sub / LPR;
+  const int l = sub % LPR;
+  const float4 u4 = f.u4;
+  const float4 (&r)[CPL] = f.r;
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
     const float pj = row_allreduce_sum<LPR>(dot4(u4, r[j]));
@@ -147,6 +204,23 @@ __device__ __forceinline__ void bprmf_fwd_bwd_body(
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Everything behind the scores of one tuple (wave barriers only).
+template <int D, int GS, int CPL, int MODE>
+__device__ __forceinline__ void fused_finish(
+    const int64_t* __restrict__ iid, int C, float inv_b, float* __restrict__ pred, float* __restrict__ loss_vec,
+    float* __restrict__ gpred, float* __restrict__ ugrad, const FusedUpd& upd, int64_t t, bool tv, int lane, float* strip,
+    const int64_t* id_strip, const FusedRows<CPL>& f) {
+  using G = FusedGeom<D, GS, CPL>;
+  constexpr int LPR = G::LPR, S = G::S, SLOTS = G::SLOTS, NPL = G::NPL;
+  const int sub = lane % S;
+  const int grp = sub / LPR;
+  const int l = sub % LPR;
+  const float4 u4 = f.u4;
+  const float4 (&r)[CPL] = f.r;
+  const unsigned smask = f.smask;
+  const int64_t* ids = G::COAL ? id_strip : iid + t * C;  // ids[c], c < C
 
   // ---- loss, one lane per candidate: softmax over the negatives, P = sum w * sigmoid(pos - neg)
   float pc[NPL];
@@ -206,7 +280,6 @@ __device__ __forceinline__ void bprmf_fwd_bwd_body(
   float gs[CPL];  // stateful optimizers only
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
-    const int c = j * GS + grp;
     const float g = strip[grp * CPL + j];  // broadcast read, 0 on slots past C
     acc.x = fmaf(g, r[j].x, acc.x);
     acc.y = fmaf(g, r[j].y, acc.y);
@@ -266,6 +339,34 @@ __device__ __forceinline__ void bprmf_fwd_bwd_body(
       }
     }
   }
+}
+
+// The body of the fused kernel for workgroup `block` of NT threads (the stand-alone kernel: NT = kBlock and its own
+// workgroup index; the small-batch step, small_step.hip, runs it in the upper part of a merged grid).
+template <int D, int GS, int CPL, int MODE, int NT>
+__device__ __forceinline__ void bprmf_fwd_bwd_body(
+    const float* __restrict__ U, const float* I,
+    const int64_t* __restrict__ uid, const int64_t* __restrict__ iid, int B, int C,
+    float inv_b, float* __restrict__ pred, float* __restrict__ loss_vec,
+    float* __restrict__ gpred, float* __restrict__ ugrad, const FusedUpd& upd, int64_t block, float* __restrict__ ub) {
+  using G = FusedGeom<D, GS, CPL>;
+  __shared__ float strip_mem[(NT / 64) * G::TPW * G::SLOTS];
+
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = block * (NT / 64) + (threadIdx.x >> 6);
+  const int64_t t_raw = wave * G::TPW + lane / G::S;
+  const bool tv = t_raw < B;
+  const int64_t t = tv ? t_raw : (int64_t)B - 1;  // clamp: every lane stays in the shuffles
+  __shared__ int64_t id_mem[(NT / 64) * G::ID_SLOTS];  // COAL: one tuple per wave
+  float* strip = strip_mem + ((threadIdx.x >> 6) * G::TPW + lane / G::S) * G::SLOTS;
+  int64_t* id_strip = id_mem + (threadIdx.x >> 6) * G::ID_SLOTS;
+
+  const TupleIds ti = fused_load_ids<D, GS, CPL>(uid, iid, t, C, lane);
+  if (G::COAL) fused_stage_ids<G::SLOTS>(ti, lane, id_strip);
+  FusedRows<CPL> f;
+  fused_request<D, GS, CPL, MODE>(U, I, iid, C, upd, ub, ti, t, tv, lane, id_strip, f);
+  fused_scores<D, GS, CPL>(lane, strip, f);
+  fused_finish<D, GS, CPL, MODE>(iid, C, inv_b, pred, loss_vec, gpred, ugrad, upd, t, tv, lane, strip, id_strip, f);
 }
 
 }  // namespace rc
