@@ -1416,6 +1416,77 @@ enum rc_status rc_kda_aggregate_bwd(const float* seq, const int64_t* hist, const
                                     float* dtarget, float* dvalue, float* drel, float* dfreq_real, float* dfreq_imag, void* ws,
                                     size_t ws_bytes, rc_stream_t stream);
 
+/* ---- Chorus, stage 2 (csrc/chorus.hip; reference models/sequential/Chorus.py:100-153) ----------------------------------------------
+ * fp32 tables in the reference's layout: U [n_users, d], I [n_items, d], Rel [R, d] (r_embeddings) and w [d] (prediction.weight)
+ * row-major and 16-byte aligned, d in {16, 32, 64, 128}; betas, sigmas, mus [n_cat, R] (1 <= R <= 8 = item relations + 1; read as
+ * scalars); user_bias [n_users], item_bias [n_items].  uid [B], iid [B, C], cid [B, C] int64 (cid < n_cat); intervals [B, C, R] fp32,
+ * -1 where the relation has no history event; kinds: a HOST array of R ints, passed to the kernels by value (0: exponential -- relation
+ * 0 and any column naming neither word; 1: 'complement'; 2: 'substitute').  With k = cid[b, c], t_r = intervals[b, c, r],
+ * on = (t_r >= 0), dt = on ? t_r : 0, beta = clamp(betas[k, r] + 1, 1e-10, 10), sigma likewise, mu = mus[k, r] + 1 and
+ * n(x; m, s) = exp(-(x - m)^2 / (2 s^2) - log s - log sqrt(2 pi)):
+ *   kappa = exp(log beta - beta dt)  |  n(dt; 0, beta)  |  n(dt; mu, sigma) - n(dt; 0, beta)          (Chorus.py:100-120)
+ *   decay_r = on * clamp(kappa, -1, 1),  S = sum_r decay_r                                                (Chorus.py:132-137)
+ *   pred = (1 + S) <u', I[i]> + sum_r decay_r <u', Rel[r]>  (+ user_bias[u] + item_bias[i]),  u' = U[u], or w o U[u] when w != NULL
+ * -- the FACTORED form of Chorus.py:140-152: the R products with Rel are formed once per tuple, so the summation order differs from
+ * the reference's sum over d of u' o z.  w == NULL selects the BPR head (the biases are required), w != NULL the GMF head (the biases
+ * are not read and may be NULL).  Both clamps pass the gradient on the closed interval.  No floating-point atomics, every sum in a
+ * fixed order: results are bit-identical from run to run.                                                                          */
+
+/* RC_OK, or RC_ERR_INVALID_ARG with the reason in rc_last_error_string: d outside {16, 32, 64, 128}, C < 1, R outside 1..8 -- the one
+ * statement of the envelope */
+enum rc_status rc_chorus_check_shape(int d, int C, int R);
+/* the tuples one workgroup of rc_chorus_fwd_bwd / rc_chorus_scores_bwd takes (16: four per wave, in turn; the launch geometry and the
+ * number of [R + 1, d] partials change at its multiples), and the sorted positions one workgroup of rc_chorus_category_update sums
+ * (the piece size, 1,024).  There is one path for every C: no register / streaming switch.  Host logic, nothing is launched.    */
+size_t rc_chorus_front_tuples_per_block(void);
+size_t rc_chorus_category_piece(void);
+/* Chorus.rec_forward (Chorus.py:122-153) for any C >= 1 (evaluation: C = 100, or C = n_items - 1 with --test_all): pred [B, C] */
+enum rc_status rc_chorus_scores(const float* U, const float* I, const float* Rel, const float* betas, const float* sigmas,
+                                const float* mus, const float* w, const float* user_bias, const float* item_bias, const int64_t* uid,
+                                const int64_t* iid, const int64_t* cid, const float* intervals, const int* kinds, int B, int C, int d,
+                                int R, float* pred, rc_stream_t stream);
+/* Chorus.rec_forward, GeneralModel.loss (Chorus.py:175-176 -> models/BaseModel.py:182-185; the arithmetic of rc_bpr_loss_fwd_bwd) and
+ * the backward in one launch plus a fixed-order reduce.  With g = gpred[b, c] = d(inv_b * sum loss_vec) / d pred:
+ *   pred [B, C] (optional, may be NULL), loss_vec [B], gpred [B, C],
+ *   coef [B, C] = g (1 + S)                     -- dI[i] += coef u': rc_segmented_update(coef, src = U or uprime, src_index = uid, div = C)
+ *   ugrad [B, d] = (w o) sum_c g z,   ubgrad [B] = sum_c g  (the per-tuple gradient of user_bias; gpred itself is item_bias's),
+ *   kgrad [B * C, 3 R]: row o = b C + c holds g (<u', I[i]> + <u', Rel[r]>) d decay_r / d (betas | sigmas | mus)[cid[o], 0..R), both
+ *     clamp gates and the mask applied (sigmas and mus: kind 2 only, 0 elsewhere),
+ *   GRel [R, d] = sum_{b, c} g decay_r u'  (dense, every row written),
+ *   GMF only: gw [d] = sum_{b, c} g U[u] o z  and  uprime [B, d] = w o U[u]  (not written and may be NULL for BPR).
+ * GRel and gw: register accumulators over a wave's tuples, the waves through LDS in wave order, one [R + 1, d] partial per workgroup
+ * in ws, summed in workgroup order.  ws: 16-byte aligned, rc_chorus_front_workspace_bytes(B, d, R) bytes.  Any C >= 2, any B >= 1. */
+size_t rc_chorus_front_workspace_bytes(int64_t B, int d, int R);
+enum rc_status rc_chorus_fwd_bwd(const float* U, const float* I, const float* Rel, const float* betas, const float* sigmas,
+                                 const float* mus, const float* w, const float* user_bias, const float* item_bias, const int64_t* uid,
+                                 const int64_t* iid, const int64_t* cid, const float* intervals, const int* kinds, int B, int C, int d,
+                                 int R, float inv_b, float* pred, float* loss_vec, float* gpred, float* coef, float* ugrad,
+                                 float* ubgrad, float* kgrad, float* GRel, float* gw, float* uprime, void* ws, size_t ws_bytes,
+                                 rc_stream_t stream);
+/* the backward of Chorus.py:122-153 for a GIVEN gpred [B, C] (the autograd node of the dense engine, whose loss is not this file's):
+ * coef, ugrad, ubgrad, kgrad, GRel, gw and uprime as rc_chorus_fwd_bwd leaves them; the same workspace.  Any C >= 1.               */
+enum rc_status rc_chorus_scores_bwd(const float* U, const float* I, const float* Rel, const float* betas, const float* sigmas,
+                                    const float* mus, const float* w, const int64_t* uid, const int64_t* iid, const int64_t* cid,
+                                    const float* intervals, const int* kinds, const float* gpred, int B, int C, int d, int R,
+                                    float* coef, float* ugrad, float* ubgrad, float* kgrad, float* GRel, float* gw, float* uprime,
+                                    void* ws, size_t ws_bytes, rc_stream_t stream);
+/* betas, sigmas and mus [n_cat, R] (the embeddings of Chorus.py:83-85) in one pass over the sorted category ids: keys / perm of
+ * rc_sort_ids over cid [B * C] (keys < n_cat), heads / n_heads of rc_segment_heads with only_multi = 0 (both required).  W, M, V and
+ * dense_grad are HOST arrays of three device pointers in the order betas, sigmas, mus -- the order of kgrad's column blocks.  For
+ * every distinct category k: g = the sum of kgrad[perm[j]] over its sorted positions j.  The list is cut every 1,024 positions
+ * (rc_chorus_category_piece); one workgroup sums one piece in ascending position, cutting at every change of category, and a second
+ * kernel adds the pieces of a category in piece order -- a category that owns the whole list (no category column: n_cat = 1) is
+ * spread over n_occ / 1,024 workgroups, and no segment is walked by one wave.  Then either row k of the three dense gradients is
+ * written (dense_grad given: all three pointers, or RC_ERR_INVALID_ARG; the caller zero-fills), or the optimizer `h` is applied to
+ * row k of each table (and of M / V) in place with the arithmetic of rc_segmented_update.  In that form W[1] and W[2] may be NULL:
+ * sigmas and mus have no gradient when no relation is of kind 2, and torch.optim leaves a parameter without one alone.
+ * ws: 256-byte aligned, rc_chorus_category_update_workspace_bytes(n_occ, n_cat, R) bytes.                                          */
+size_t rc_chorus_category_update_workspace_bytes(int64_t n_occ, int64_t n_cat, int R);
+enum rc_status rc_chorus_category_update(float* const* W, float* const* M, float* const* V, int64_t n_cat, int R, const uint32_t* keys,
+                                         const uint32_t* perm, int64_t n_occ, const float* kgrad, const rc_opt_hyper* h,
+                                         float* const* dense_grad, const uint32_t* heads, const uint32_t* n_heads, void* ws,
+                                         size_t ws_bytes, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,15 @@ SIGNATURES = {
     "rc_kda_aggregate_fwd": (_i, [_p] * 8 + [_i64, _i, _i, _i, _i, _i, _i, _p, _p]),
     "rc_kda_aggregate_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "rc_kda_aggregate_bwd": (_i, [_p] * 9 + [_i64, _i, _i, _i, _i, _i, _i] + [_p] * 7 + [_sz, _p]),
+    "rc_chorus_check_shape": (_i, [_i, _i, _i]),
+    "rc_chorus_front_tuples_per_block": (_sz, []),
+    "rc_chorus_category_piece": (_sz, []),
+    "rc_chorus_scores": (_i, [_p] * 13 + [_ip, _i, _i, _i, _i, _p, _p]),
+    "rc_chorus_front_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "rc_chorus_fwd_bwd": (_i, [_p] * 13 + [_ip, _i, _i, _i, _i, _f] + [_p] * 11 + [_sz, _p]),
+    "rc_chorus_scores_bwd": (_i, [_p] * 11 + [_ip, _p, _i, _i, _i, _i] + [_p] * 8 + [_sz, _p]),
+    "rc_chorus_category_update_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "rc_chorus_category_update": (_i, [_p] * 3 + [_i64, _i, _p, _p, _i64, _p, _hp, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -50,6 +50,7 @@ SOURCES = [
     "cfkg.hip",
     "din.hip",
     "kda.hip",
+    "chorus.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -3624,3 +3624,234 @@ def kda_aggregate_bwd(seq, hist, delta_t, target, value, rel, freq_real, freq_im
               _ptr(dtarget, f32, "dtarget"), _ptr(dvalue, f32, "dvalue", True), _ptr(drel, f32, "drel"), _ptr(dfr, f32, "dfreq_real"),
               _ptr(dfi, f32, "dfreq_imag"), *_ws_args(ws))
     return dseq, dtarget, dvalue, drel, dfr, dfi
+
+
+# ---- Chorus: knowledge- and time-aware item vectors, two stages (models/sequential/Chorus.py:100-177; csrc/chorus.hip) -------------
+
+CHORUS_PARAMS = ("U", "I", "Rel", "betas", "mus", "sigmas", "w", "user_bias", "item_bias")   # the reference's definition order
+CHORUS_CAT_TABLES = ("betas", "sigmas", "mus")   # the [3] arrays of rc_chorus_category_update and kgrad's column blocks
+CHORUS_KINDS = {"exponential": 0, "complement": 1, "substitute": 2}
+
+
+def chorus_kinds(item_relations):
+    """the temporal kernel of every relation (Chorus.py:106-118): relation 0 and a column naming neither word take the exponential
+    one, 'complement' is tested before 'substitute'"""
+    kinds = [0]
+    for name in item_relations:
+        kinds.append(1 if "complement" in name else (2 if "substitute" in name else 0))
+    return kinds
+
+
+def chorus_check_shape(d, n_cand=1, n_rel=1):
+    """rc_chorus_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate, 1..8 relations; raises ValueError
+    with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_chorus_check_shape(int(d), int(n_cand), int(n_rel)) != _lib.RC_OK:
+        raise ValueError("Chorus on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def chorus_front_tuples_per_block():
+    """the tuples one workgroup of rc_chorus_fwd_bwd takes (host logic); the launch geometry changes at its multiples"""
+    return int(_lib.load().rc_chorus_front_tuples_per_block())
+
+
+def chorus_category_piece():
+    """the sorted positions one workgroup of rc_chorus_category_update sums (host logic)"""
+    return int(_lib.load().rc_chorus_category_piece())
+
+
+def chorus_kg_feed(head_id, tail_id):
+    """Stage 1's feed (Chorus.py:216-219: head_id = (t, t, t', t), tail_id = (h, h, h, h'), which corrupts the HEAD slot in pair 1)
+    in the layout of rc_cfkg_fwd_bwd / CfkgTrainer (head = (a, a, a, a'), tail = (b, b, b', b), which corrupts the TAIL slot in
+    pair 1): the two pairs exchanged.  The per-row loss is unchanged; `pred` columns 2 and 3 come out swapped."""
+    a, b = head_id[:, 0], tail_id[:, 0]
+    return torch.stack((a, a, a, head_id[:, 2]), dim=1), torch.stack((b, b, tail_id[:, 3], b), dim=1)
+
+
+def _chorus_shapes(P, uid, iid, cid, intervals, kinds):
+    U, I, Rel, betas, mus, sigmas, w, ub, ib = P
+    d, n_users, n_items, R = U.shape[1], U.shape[0], I.shape[0], Rel.shape[0]
+    if I.shape[1] != d or Rel.shape[1] != d or w.numel() != d:
+        raise ValueError("Chorus: u_embeddings, i_embeddings, r_embeddings and prediction.weight need the same emb_size")
+    if ub.numel() != n_users or ib.numel() != n_items:
+        raise ValueError("Chorus: user_bias [n_users, 1] and item_bias [n_items, 1] are needed")
+    if betas.dim() != 2 or betas.shape[1] != R or sigmas.shape != betas.shape or mus.shape != betas.shape:
+        raise ValueError("Chorus: betas, mus and sigmas must all be [category_num, relation_num]")
+    if iid.dim() != 2 or uid.shape != (iid.shape[0],) or cid.shape != iid.shape or tuple(intervals.shape) != (*iid.shape, R):
+        raise ValueError(f"Chorus: need uid [B], iid [B, C], category_id [B, C], relational_interval [B, C, {R}]; got "
+                         f"{tuple(uid.shape)}, {tuple(iid.shape)}, {tuple(cid.shape)}, {tuple(intervals.shape)}")
+    if len(kinds) != R or any(k not in (0, 1, 2) for k in kinds):
+        raise ValueError(f"Chorus: kinds must hold {R} values of 0 / 1 / 2, got {list(kinds)}")
+    return iid.shape[0], iid.shape[1], d, R
+
+
+def _chorus_tables(P, gmf, with_bias=True):
+    """(U, I, Rel, betas, sigmas, mus, w | NULL [, user_bias, item_bias]) in the entry points' order"""
+    U, I, Rel, betas, mus, sigmas, w, ub, ib = P
+    f32 = torch.float32
+    out = (_ptr(U, f32, "U"), _ptr(I, f32, "I"), _ptr(Rel, f32, "Rel"), _ptr(betas, f32, "betas"), _ptr(sigmas, f32, "sigmas"),
+           _ptr(mus, f32, "mus"), _ptr(w if gmf else None, f32, "w", True))
+    if with_bias:
+        out += (_ptr(None if gmf else ub, f32, "user_bias", True), _ptr(None if gmf else ib, f32, "item_bias", True))
+    return out
+
+
+def _chorus_ids(uid, iid, cid, intervals, kinds):
+    i64 = torch.int64
+    return (_ptr(uid, i64, "uid"), _ptr(iid, i64, "iid"), _ptr(cid, i64, "category_id"),
+            _ptr(intervals, torch.float32, "relational_interval"), (C.c_int * len(kinds))(*[int(k) for k in kinds]))
+
+
+def chorus_scores(P, uid, iid, cid, intervals, kinds, gmf=False):
+    """Chorus's stage-2 prediction [B, C] for any C >= 1 (rc_chorus_scores); P: the nine parameter tensors in CHORUS_PARAMS order"""
+    B, Cn, d, R = _chorus_shapes(P, uid, iid, cid, intervals, kinds)
+    pred = torch.empty((B, Cn), dtype=torch.float32, device=iid.device)
+    _lib.call("rc_chorus_scores", *_chorus_tables(P, gmf), *_chorus_ids(uid, iid, cid, intervals, kinds), B, Cn, d, R,
+              _ptr(pred, torch.float32, "pred"), _stream())
+    return pred
+
+
+def _chorus_front_outputs(B, Cn, d, R, gmf, dev):
+    f32 = torch.float32
+    out = {"coef": torch.empty((B, Cn), dtype=f32, device=dev), "ugrad": torch.empty((B, d), dtype=f32, device=dev),
+           "ubgrad": torch.empty(B, dtype=f32, device=dev), "kgrad": torch.empty((B * Cn, 3 * R), dtype=f32, device=dev),
+           "GRel": torch.empty((R, d), dtype=f32, device=dev),
+           "gw": torch.empty(d, dtype=f32, device=dev) if gmf else None,
+           "uprime": torch.empty((B, d), dtype=f32, device=dev) if gmf else None}
+    args = tuple(_ptr(out[k], f32, k, k in ("gw", "uprime")) for k in ("coef", "ugrad", "ubgrad", "kgrad", "GRel", "gw", "uprime"))
+    return out, args
+
+
+def chorus_fwd_bwd(P, uid, iid, cid, intervals, kinds, gmf=False, inv_b=None, want_pred=True):
+    """rc_chorus_fwd_bwd: scores + GeneralModel.loss + backward in one launch, plus the fixed-order reduce of GRel / gw.
+    Returns a dict: pred | None, loss_vec [B], gpred [B, C], coef [B, C], ugrad [B, d], ubgrad [B], kgrad [B * C, 3 R] (betas | sigmas
+    | mus), GRel [R, d], and for GMF gw [d], uprime [B, d] (None for BPR)."""
+    B, Cn, d, R = _chorus_shapes(P, uid, iid, cid, intervals, kinds)
+    if inv_b is None:
+        inv_b = 1.0 / B
+    dev, f32 = iid.device, torch.float32
+    out, out_args = _chorus_front_outputs(B, Cn, d, R, gmf, dev)
+    out["pred"] = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
+    out["loss_vec"] = torch.empty(B, dtype=f32, device=dev)
+    out["gpred"] = torch.empty((B, Cn), dtype=f32, device=dev)
+    ws = workspace(_lib.load().rc_chorus_front_workspace_bytes(B, d, R), dev, "chorus_front")
+    _lib.call("rc_chorus_fwd_bwd", *_chorus_tables(P, gmf), *_chorus_ids(uid, iid, cid, intervals, kinds), B, Cn, d, R, float(inv_b),
+              _ptr(out["pred"], f32, "pred", True), _ptr(out["loss_vec"], f32, "loss_vec"), _ptr(out["gpred"], f32, "gpred"), *out_args,
+              *_ws_args(ws))
+    return out
+
+
+def chorus_scores_grads(P, uid, iid, cid, intervals, kinds, gpred, gmf=False):
+    """rc_chorus_scores_bwd: for a given gpred [B, C] the dict of chorus_fwd_bwd without pred, loss_vec and gpred"""
+    B, Cn, d, R = _chorus_shapes(P, uid, iid, cid, intervals, kinds)
+    if gpred.shape != (B, Cn):
+        raise ValueError(f"Chorus: gpred must be [{B}, {Cn}], got {tuple(gpred.shape)}")
+    dev = iid.device
+    out, out_args = _chorus_front_outputs(B, Cn, d, R, gmf, dev)
+    ws = workspace(_lib.load().rc_chorus_front_workspace_bytes(B, d, R), dev, "chorus_front")
+    ids = _chorus_ids(uid, iid, cid, intervals, kinds)
+    _lib.call("rc_chorus_scores_bwd", *_chorus_tables(P, gmf, with_bias=False), *ids, _ptr(gpred, torch.float32, "gpred"), B, Cn, d, R,
+              *out_args, *_ws_args(ws))
+    return out
+
+
+def _ptr_array3(tensors, name, allow_none=False):
+    """a host array of three device pointers (CHORUS_CAT_TABLES order), or NULL when `tensors` is None"""
+    if tensors is None:
+        return None
+    if len(tensors) != 3:
+        raise ValueError(f"{name}: three tensors are needed ({', '.join(CHORUS_CAT_TABLES)})")
+    return (C.c_void_p * 3)(*(_ptr(t, torch.float32, f"{name}[{k}]", allow_none) for t, k in zip(tensors, CHORUS_CAT_TABLES)))
+
+
+def chorus_category_update(keys, perm, heads, n_heads, kgrad, n_cat, hyper=None, W=None, m=None, v=None, dense_grad=None,
+                           workspace_buf=None):
+    """rc_chorus_category_update: one pass over the sorted category ids (keys / perm of sort_ids(cid), heads / n_heads of
+    segment_heads) that sums kgrad [n_occ, 3 R] per distinct category and either applies `hyper` to that row of the three tables W
+    (m, v: their states; CHORUS_CAT_TABLES order) in place or writes the three dense gradients"""
+    n_occ = keys.numel()
+    if kgrad.dim() != 2 or kgrad.shape[0] != n_occ or kgrad.shape[1] % 3:
+        raise ValueError(f"Chorus: kgrad must be [{n_occ}, 3 R], got {tuple(kgrad.shape)}")
+    R = kgrad.shape[1] // 3
+    for t in (W or []) + (dense_grad or []):
+        if t is not None and tuple(t.shape) != (int(n_cat), R):
+            raise ValueError(f"Chorus: every category table must be [{int(n_cat)}, {R}], got {tuple(t.shape)}")
+    f32, i32 = torch.float32, torch.int32
+    need = _lib.load().rc_chorus_category_update_workspace_bytes(n_occ, int(n_cat), R)
+    ws = workspace_buf if workspace_buf is not None else workspace(need, keys.device, "chorus_cat")
+    _lib.call("rc_chorus_category_update", _ptr_array3(W, "W", True), _ptr_array3(m, "m", True), _ptr_array3(v, "v", True), int(n_cat), R,
+              _ptr(keys, i32, "keys"), _ptr(perm, i32, "perm"), n_occ, _ptr(kgrad, f32, "kgrad"), _hyper_ref(hyper),
+              _ptr_array3(dense_grad, "dense_grad", True), _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
+
+
+class ChorusTrainer:
+    """Row-wise-optimizer training of Chorus's stage 2 on the nine device parameters (CHORUS_PARAMS order; Chorus.py:79-88).
+
+    One `step(uid, iid, cid, intervals)` = one iteration of BaseRunner.fit's batch loop (helpers/BaseRunner.py:193-206): three sorts
+    (candidates, categories, users) + the categories' head list -> rc_chorus_fwd_bwd -> rc_segmented_update on I (coef, the pre-step U
+    or uprime) -> rc_slrc_user_bias_update on item_bias (gpred is its per-occurrence gradient) -> rc_chorus_category_update ->
+    rc_dense_update on Rel (and on prediction.weight for GMF) -> the user side last: rc_segmented_update on U, rc_slrc_user_bias_update
+    on user_bias.  Three hyper records, as Chorus.customize_parameters groups the parameters (Chorus.py:179-194): (lr, l2) for U,
+    betas, mus, sigmas and prediction.weight; (lr_scale * lr, l2) for I and Rel; (lr, 0) for the two bias tables.  Only rows of the
+    batch move (and only their optimizer state); Rel and prediction.weight are dense and follow torch.optim exactly.  A parameter the
+    head does not read (the biases under GMF, prediction.weight under BPR, sigmas and mus without a 'substitute' relation) has no
+    gradient and is left alone, as torch.optim does."""
+
+    def __init__(self, *params, kinds, gmf=False, opt="SGD", lr=1e-3, l2=0.0, lr_scale=0.1, beta1=0.9, beta2=0.999, eps=None):
+        if opt not in ("SGD", "Adam", "Adagrad"):
+            raise ValueError(f"ChorusTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        if len(params) != len(CHORUS_PARAMS):
+            raise ValueError("ChorusTrainer: nine parameter tensors are needed: " + ", ".join(CHORUS_PARAMS))
+        self.P = dict(zip(CHORUS_PARAMS, params))
+        self.d, self.R, self.n_cat = self.P["U"].shape[1], self.P["Rel"].shape[0], self.P["betas"].shape[0]
+        chorus_check_shape(self.d, 1, self.R)
+        self.kinds, self.gmf, self.opt = [int(k) for k in kinds], bool(gmf), opt
+        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
+        self.hyper_kg = make_hyper(opt, lr_scale * lr, l2, beta1, beta2, eps, step=0)
+        self.hyper_bias = make_hyper(opt, lr, 0.0, beta1, beta2, eps, step=0)
+        self.state = {name: new_opt_state(t, opt) for name, t in self.P.items()}
+
+    def _mv(self, name):
+        return self.state[name].get("m"), self.state[name].get("v")
+
+    def step(self, uid, iid, cid, intervals, inv_b=None):
+        """one training step; returns the device loss tensor (shape [1], no sync)"""
+        P = [self.P[k] for k in CHORUS_PARAMS]
+        B, Cn, d, R = _chorus_shapes(P, uid, iid, cid, intervals, self.kinds)
+        if inv_b is None:
+            inv_b = 1.0 / B
+        U, I = self.P["U"], self.P["I"]
+        for h in (self.hyper, self.hyper_kg, self.hyper_bias):
+            h.step += 1
+        ikeys, iperm = sort_ids(iid, I.shape[0])
+        ckeys, cperm = sort_ids(cid, self.n_cat)
+        _, heads, n_heads = segment_heads(ckeys, cperm, want_single=False)
+        ukeys, uperm = sort_ids(uid, U.shape[0])
+        out = chorus_fwd_bwd(P, uid, iid, cid, intervals, self.kinds, self.gmf, inv_b, want_pred=False)
+        loss = reduce_sum(out["loss_vec"], inv_b)
+        m, v = self._mv("I")
+        if self.gmf:
+            segmented_update(ikeys, iperm, out["uprime"], hyper=self.hyper_kg, W=I, m=m, v=v, coef=out["coef"], div=Cn)
+        else:
+            segmented_update(ikeys, iperm, U, hyper=self.hyper_kg, W=I, m=m, v=v, coef=out["coef"], src_index=uid, div=Cn)
+            m, v = self._mv("item_bias")
+            slrc_user_bias_update(ikeys, iperm, out["gpred"], hyper=self.hyper_bias, user_bias=self.P["item_bias"], m=m, v=v)
+        mv = [self._mv(k) for k in CHORUS_CAT_TABLES]
+        # sigmas and mus are read by the 'substitute' kernel alone: without one they have no gradient and stay as they are
+        live = [True, 2 in self.kinds, 2 in self.kinds]
+        chorus_category_update(ckeys, cperm, heads, n_heads, out["kgrad"], self.n_cat, hyper=self.hyper,
+                               W=[self.P[k] if on else None for k, on in zip(CHORUS_CAT_TABLES, live)],
+                               m=[x[0] for x in mv] if mv[0][0] is not None else None,
+                               v=[x[1] for x in mv] if mv[0][1] is not None else None)
+        m, v = self._mv("Rel")
+        dense_update(self.P["Rel"], out["GRel"], self.hyper_kg, m=m, v=v)
+        if self.gmf:
+            m, v = self._mv("w")
+            dense_update(self.P["w"], out["gw"].view_as(self.P["w"]), self.hyper, m=m, v=v)
+        # the user side last: the item update above read the pre-step U
+        m, v = self._mv("U")
+        segmented_update(ukeys, uperm, out["ugrad"], hyper=self.hyper, W=U, m=m, v=v)
+        if not self.gmf:
+            m, v = self._mv("user_bias")
+            slrc_user_bias_update(ukeys, uperm, out["ubgrad"], hyper=self.hyper_bias, user_bias=self.P["user_bias"], m=m, v=v)
+        return loss

@@ -220,6 +220,57 @@ def cfkg_scores(E, R, head, tail, rel):
     return _CfkgScoreFn.apply(E, R, head.contiguous(), tail.contiguous(), rel.contiguous())
 
 
+class _ChorusScoreFn(torch.autograd.Function):
+    """Chorus's stage-2 prediction (models/sequential/Chorus.py:122-153) with dense gradients for its nine parameters; none for the
+    ids or the intervals.  The backward runs on the saved inputs through engine.chorus_scores_grads (rc_chorus_scores_bwd) and the
+    row updates' dense-gradient forms.  A parameter the head does not read (prediction.weight under BPR, the biases under GMF, sigmas
+    and mus without a 'substitute' relation) gets no gradient, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, uid, iid, cid, intervals, kinds, gmf, *params):
+        ctx.save_for_backward(uid, iid, cid, intervals, *params)
+        ctx.kinds, ctx.gmf = list(kinds), bool(gmf)
+        return engine.chorus_scores([p.detach() for p in params], uid, iid, cid, intervals, ctx.kinds, ctx.gmf)
+
+    @staticmethod
+    def backward(ctx, gpred):
+        uid, iid, cid, intervals, *params = (t.detach() for t in ctx.saved_tensors)
+        U, I, Rel, betas, mus, sigmas, w, ub, ib = params
+        gmf, Cn = ctx.gmf, iid.shape[1]
+        gpred = gpred.contiguous()
+        out = engine.chorus_scores_grads(params, uid, iid, cid, intervals, ctx.kinds, gpred, gmf)
+        ikeys, iperm = engine.sort_ids(iid, I.shape[0])
+        GI = torch.zeros_like(I)
+        if gmf:
+            engine.segmented_update(ikeys, iperm, out["uprime"], coef=out["coef"], div=Cn, dense_grad=GI)
+        else:
+            engine.segmented_update(ikeys, iperm, U, coef=out["coef"], src_index=uid, div=Cn, dense_grad=GI)
+        ckeys, cperm = engine.sort_ids(cid, betas.shape[0])
+        _, heads, n_heads = engine.segment_heads(ckeys, cperm, want_single=False)
+        Gb, Gs, Gm = torch.zeros_like(betas), torch.zeros_like(sigmas), torch.zeros_like(mus)
+        engine.chorus_category_update(ckeys, cperm, heads, n_heads, out["kgrad"], betas.shape[0], dense_grad=[Gb, Gs, Gm])
+        ukeys, uperm = engine.sort_ids(uid, U.shape[0])
+        GU = torch.zeros_like(U)
+        engine.segmented_update(ukeys, uperm, out["ugrad"], dense_grad=GU)
+        if 2 not in ctx.kinds:      # sigmas and mus are read by the 'substitute' kernel alone
+            Gs = Gm = None
+        Gw = Gub = Gib = None
+        if gmf:
+            Gw = out["gw"].view_as(w)
+        else:
+            Gub, Gib = torch.zeros_like(ub), torch.zeros_like(ib)
+            engine.slrc_user_bias_update(ukeys, uperm, out["ubgrad"], dense_grad=Gub)
+            engine.slrc_user_bias_update(ikeys, iperm, gpred, dense_grad=Gib)
+        return (None, None, None, None, None, None, GU, GI, out["GRel"], Gb, Gm, Gs, Gw, Gub, Gib)
+
+
+def chorus_scores(params, uid, iid, cid, intervals, kinds, gmf=False):
+    """Chorus's stage-2 head as one autograd node: dense gradients for the nine parameters (engine.CHORUS_PARAMS order) from an
+    arbitrary loss on the scores; kinds: engine.chorus_kinds(item_relations).  The stage-1 forward is cfkg_scores on (i_embeddings,
+    r_embeddings)."""
+    return _ChorusScoreFn.apply(uid.contiguous(), iid.contiguous(), cid.contiguous(), intervals.contiguous(), kinds, gmf, *params)
+
+
 class _DinAttentionFn(torch.autograd.Function):
     """DIN.attention (models/context_seq/DIN.py:63-95) for instance n = b C + c over the history of row b, as ONE node: the forward
     keeps q, keys and the flat parameters; the backward recomputes everything from them (same dropout seed and site)."""
