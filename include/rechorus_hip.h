@@ -1487,6 +1487,36 @@ enum rc_status rc_chorus_category_update(float* const* W, float* const* M, float
                                          float* const* dense_grad, const uint32_t* heads, const uint32_t* n_heads, void* ws,
                                          size_t ws_bytes, rc_stream_t stream);
 
+/* ---- DCNv2: the mixed (mixture of low-rank experts) cross layer (csrc/dcnv2.hip; reference models/context/DCNv2.py:96-144) ----------
+ * X0, Xl [N, D] (N = batch * candidates, D = fields * emb_size); U, V [E, D, r], C [E, r, r], bias [D] of ONE layer; the gate
+ * Wg [E, D], bg [E] (the reference builds one gating ModuleList for all layers, DCNv2.py:62).  Per row and expert e
+ *   t_e = tanh(V_e^T x_l),  s_e = tanh(C_e t_e),  y_e = U_e s_e + bias                                     (DCNv2.py:126-134)
+ *   g = softmax_e(Wg_e . x_l + bg_e),  x_next = x_l + x_0 * sum_e g_e y_e                                  (DCNv2.py:124, :135-141)
+ * All fp32, every tensor 16-byte aligned.  The three products run on the f32-input MFMA; no float atomics, reruns are bitwise
+ * identical.
+ * RC_OK when D % 4 == 0, 8 <= D <= 1024, low_rank % 4 == 0, 4 <= low_rank <= 128 and 1 <= expert_num <= 4, else RC_ERR_UNSUPPORTED
+ * with the reason in rc_last_error_string() (host logic, no GPU needed); the entry points below check the same envelope themselves,
+ * and 1 <= N <= 2^24.                                                                                                              */
+enum rc_status rc_dcnv2_check_shape(int D, int low_rank, int expert_num);
+/* one layer of cross_net_mix's loop (DCNv2.py:119-141) in ONE launch: X0 and Xl are read once, Xnext [N, D] is written once, nothing
+ * is kept for the backward pass.                                                                                                   */
+enum rc_status rc_dcnv2_mix_layer_fwd(const float* X0, const float* Xl, const float* U, const float* V, const float* C,
+                                      const float* bias, const float* Wg, const float* bg, int64_t N, int D, int low_rank,
+                                      int expert_num, float* Xnext, rc_stream_t stream);
+/* bytes of the caller workspace (256-byte aligned) of rc_dcnv2_mix_layer_bwd: one partial of every weight gradient per workgroup,
+ * at most min(256, 128 MB / bytes of one partial) of them, so the size does not grow with N past 256 row tiles; 0 outside the
+ * envelope                                                                                                                         */
+size_t rc_dcnv2_mix_layer_bwd_workspace_bytes(int64_t N, int D, int low_rank, int expert_num);
+/* autograd of DCNv2.py:119-141 for one layer from dXnext: t, s and g are recomputed.  dXl [N, D] = dXnext + sum_e V_e dp_e +
+ * sum_e dz_e Wg_e (the straight-through term, the V path, the gate path); dX0_part [N, D] = dXnext * sum_e g_e y_e, THIS layer's
+ * share of x_0's gradient (the caller sums the layers'); dU, dV [E, D, r], dC [E, r, r], dbias [D], dWg [E, D], dbg [E] over all rows.
+ * With expert_num == 1 the gate is identically 1 and dWg, dbg are exact zeros.  Two launches: the row-tile kernel and the
+ * fixed-order reduce of its per-workgroup partials.                                                                                */
+enum rc_status rc_dcnv2_mix_layer_bwd(const float* dXnext, const float* X0, const float* Xl, const float* U, const float* V,
+                                      const float* C, const float* bias, const float* Wg, const float* bg, int64_t N, int D,
+                                      int low_rank, int expert_num, void* workspace, size_t ws_bytes, float* dXl, float* dX0_part,
+                                      float* dU, float* dV, float* dC, float* dbias, float* dWg, float* dbg, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -304,6 +304,10 @@ SIGNATURES = {
     "rc_chorus_scores_bwd": (_i, [_p] * 11 + [_ip, _p, _i, _i, _i, _i] + [_p] * 8 + [_sz, _p]),
     "rc_chorus_category_update_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "rc_chorus_category_update": (_i, [_p] * 3 + [_i64, _i, _p, _p, _i64, _p, _hp, _p, _p, _p, _p, _sz, _p]),
+    "rc_dcnv2_check_shape": (_i, [_i, _i, _i]),
+    "rc_dcnv2_mix_layer_fwd": (_i, [_p] * 8 + [_i64, _i, _i, _i, _p, _p]),
+    "rc_dcnv2_mix_layer_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_dcnv2_mix_layer_bwd": (_i, [_p] * 9 + [_i64, _i, _i, _i, _p, _sz] + [_p] * 8 + [_p]),
 }
 
 _lib = None

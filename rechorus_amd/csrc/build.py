@@ -51,6 +51,7 @@ SOURCES = [
     "din.hip",
     "kda.hip",
     "chorus.hip",
+    "dcnv2.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

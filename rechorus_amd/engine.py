@@ -2912,6 +2912,83 @@ def autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, dY, heads, workspace=None):
     return dX, dWq, dWk, dWv, dWr, dbr
 
 
+# ---- DCNv2 mixed cross layer (models/context/DCNv2.py:96-144) -----------------------------------------------------------------------
+
+def dcnv2_check_shape(width, low_rank, expert_num):
+    """rc_dcnv2_check_shape (host logic): width = fields * emb_size a multiple of 4 in [8, 1024], low_rank a multiple of 4 in
+    [4, 128], expert_num in [1, 4]; raises ValueError with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_dcnv2_check_shape(int(width), int(low_rank), int(expert_num)) != _lib.RC_OK:
+        raise ValueError("DCNv2 on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class DCNv2Workspace:
+    """the scratch of rc_dcnv2_mix_layer_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
+    freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
+    that wrote it, so the layers of a stack share one workspace."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, n, width, low_rank, expert_num, device):
+        key = (int(n), int(width), int(low_rank), int(expert_num), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_dcnv2_mix_layer_bwd_workspace_bytes(*key[:4])
+            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return buf
+
+
+def _dcnv2_shapes(X0, Xl, U, V, Cw, bias, Wg, bg):
+    if Xl.dim() < 2 or Xl.numel() == 0 or X0.shape != Xl.shape:
+        raise ValueError(f"dcnv2_mix_layer: X0 and Xl must be [..., width] of one shape with at least one row, got "
+                         f"{tuple(X0.shape)} / {tuple(Xl.shape)}")
+    D = Xl.shape[-1]
+    N = Xl.numel() // D
+    if U.dim() != 3 or U.shape[1] != D:
+        raise ValueError(f"dcnv2_mix_layer: U must be [experts, {D}, low_rank], got {tuple(U.shape)}")
+    E, _, r = U.shape
+    dcnv2_check_shape(D, r, E)
+    for name, W, shape in (("V", V, (E, D, r)), ("C", Cw, (E, r, r)), ("Wg", Wg, (E, D)), ("bg", bg, (E,))):
+        if tuple(W.shape) != shape:
+            raise ValueError(f"dcnv2_mix_layer: {name} must be {list(shape)}, got {tuple(W.shape)}")
+    if bias.numel() != D:
+        raise ValueError(f"dcnv2_mix_layer: bias must hold {D} values, got {tuple(bias.shape)}")
+    return N, D, r, E
+
+
+def dcnv2_mix_layer_fwd(X0, Xl, U, V, Cw, bias, Wg, bg):
+    """rc_dcnv2_mix_layer_fwd: x_next [..., D] = x_l + x_0 * sum_e softmax_e(gate)_e (U_e tanh(C_e tanh(V_e^T x_l)) + bias), one launch"""
+    N, D, r, E = _dcnv2_shapes(X0, Xl, U, V, Cw, bias, Wg, bg)
+    f32 = torch.float32
+    Xnext = torch.empty(Xl.shape, dtype=f32, device=Xl.device)
+    _lib.call("rc_dcnv2_mix_layer_fwd", _ptr(X0, f32, "X0"), _ptr(Xl, f32, "Xl"), _ptr(U, f32, "U"), _ptr(V, f32, "V"), _ptr(Cw, f32, "C"),
+              _ptr(bias, f32, "bias"), _ptr(Wg, f32, "Wg"), _ptr(bg, f32, "bg"), N, D, r, E, _ptr(Xnext, f32, "Xnext"), _stream())
+    return Xnext
+
+
+def dcnv2_mix_layer_bwd(dXnext, X0, Xl, U, V, Cw, bias, Wg, bg, workspace=None):
+    """rc_dcnv2_mix_layer_bwd -> (dXl, dX0_part, dU, dV, dC, dbias, dWg, dbg): t, s and the gate are recomputed; two launches"""
+    N, D, r, E = _dcnv2_shapes(X0, Xl, U, V, Cw, bias, Wg, bg)
+    if dXnext.shape != Xl.shape:
+        raise ValueError(f"dcnv2_mix_layer_bwd: dXnext must be {tuple(Xl.shape)}, got {tuple(dXnext.shape)}")
+    dev, f32 = Xl.device, torch.float32
+    ws = (workspace if workspace is not None else DCNv2Workspace()).get(N, D, r, E, dev)
+    dXl = torch.empty(Xl.shape, dtype=f32, device=dev)
+    dX0 = torch.empty(Xl.shape, dtype=f32, device=dev)
+    dU = torch.empty((E, D, r), dtype=f32, device=dev)
+    dV = torch.empty((E, D, r), dtype=f32, device=dev)
+    dC = torch.empty((E, r, r), dtype=f32, device=dev)
+    dbias = torch.empty(tuple(bias.shape), dtype=f32, device=dev)
+    dWg = torch.empty((E, D), dtype=f32, device=dev)
+    dbg = torch.empty((E,), dtype=f32, device=dev)
+    _lib.call("rc_dcnv2_mix_layer_bwd", _ptr(dXnext, f32, "dXnext"), _ptr(X0, f32, "X0"), _ptr(Xl, f32, "Xl"), _ptr(U, f32, "U"),
+              _ptr(V, f32, "V"), _ptr(Cw, f32, "C"), _ptr(bias, f32, "bias"), _ptr(Wg, f32, "Wg"), _ptr(bg, f32, "bg"), N, D, r, E,
+              C.c_void_p(ws.data_ptr()), ws.numel(), _ptr(dXl, f32, "dXl"), _ptr(dX0, f32, "dX0_part"), _ptr(dU, f32, "dU"), _ptr(dV, f32, "dV"),
+              _ptr(dC, f32, "dC"), _ptr(dbias, f32, "dbias"), _ptr(dWg, f32, "dWg"), _ptr(dbg, f32, "dbg"), _stream())
+    return dXl, dX0, dU, dV, dC, dbias, dWg, dbg
+
+
 # ---- FinalMLP: feature gates + first stream layers, bilinear fusion (models/context/FinalMLP.py:141-249) -------------------------------
 
 def finalmlp_check_shape(n_fields, emb_size, gate_in_1, first_1, gate_in_2, first_2, x_dim, y_dim, num_heads, drop_p_1=0.0, drop_p_2=0.0):

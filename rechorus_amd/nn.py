@@ -504,6 +504,41 @@ def autoint_layer_eval(X, Wq, Wk, Wv, Wr, br, heads):
     return engine.autoint_layer_fwd(*[t.detach().contiguous() for t in (X, Wq, Wk, Wv, Wr, br)], int(heads))
 
 
+class _Dcnv2MixLayerFn(torch.autograd.Function):
+    """One mixed cross layer of DCNv2 (models/context/DCNv2.py:119-141) on rc_dcnv2_mix_layer_fwd / _bwd.  Saves its inputs only:
+    the backward recomputes both tanh stages and the gate.  No host synchronisation and no data-dependent allocation: capture-safe."""
+
+    @staticmethod
+    def forward(ctx, X0, Xl, U, V, C, bias, Wg, bg, workspace):
+        det = [t.detach().contiguous() for t in (X0, Xl, U, V, C, bias, Wg, bg)]
+        Xnext = engine.dcnv2_mix_layer_fwd(*det)
+        ctx.save_for_backward(*det)
+        ctx.workspace = workspace
+        return Xnext
+
+    @staticmethod
+    def backward(ctx, dXnext):
+        dXl, dX0, dU, dV, dC, dbias, dWg, dbg = engine.dcnv2_mix_layer_bwd(dXnext.contiguous(), *ctx.saved_tensors,
+                                                                           workspace=ctx.workspace)
+        return dX0, dXl, dU, dV, dC, dbias, dWg, dbg, None
+
+
+def dcnv2_mix_layer(X0, Xl, U, V, C, bias, Wg, bg, workspace=None):
+    """x_l + x_0 * sum_e softmax(gate)_e (U_e tanh(C_e tanh(V_e^T x_l)) + bias) (models/context/DCNv2.py:119-141): X0, Xl [..., D],
+    U, V [E, D, r], C [E, r, r], bias [D] or [D, 1], the gate Wg [E, D], bg [E] -> [..., D], as ONE autograd node (one forward launch,
+    one backward launch plus the fixed-order reduce).  X0's gradient is this layer's share; autograd sums the layers'.
+    workspace: the model's engine.DCNv2Workspace, reused step after step"""
+    return _Dcnv2MixLayerFn.apply(X0, Xl, U, V, C, bias, Wg, bg, workspace)
+
+
+def dcnv2_mix_layer_eval(X0, Xl, U, V, C, bias, Wg, bg):
+    """the same layer on the evaluation path: forward only, raises when autograd is recording"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (X0, Xl, U, V, C, bias, Wg, bg)):
+        raise RuntimeError("dcnv2_mix_layer_eval is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through dcnv2_mix_layer)")
+    return engine.dcnv2_mix_layer_fwd(*[t.detach().contiguous() for t in (X0, Xl, U, V, C, bias, Wg, bg)])
+
+
 class _FinalMlpGateFn(torch.autograd.Function):
     """FinalMLP's feature gates and the first layer of both streams (models/context/FinalMLP.py:188-221, :100-101) on
     rc_finalmlp_gate_fwd / _bwd.  Saves X, the gate inputs, the weights and A_1, A_2 (their own ReLU / dropout masks): the gates are
