@@ -1517,6 +1517,42 @@ enum rc_status rc_dcnv2_mix_layer_bwd(const float* dXnext, const float* X0, cons
                                       int low_rank, int expert_num, void* workspace, size_t ws_bytes, float* dXl, float* dX0_part,
                                       float* dU, float* dV, float* dC, float* dbias, float* dWg, float* dbg, rc_stream_t stream);
 
+/* ---- list encoder: one post-norm transformer encoder block over short candidate lists (csrc/listenc.hip; reference
+ * models/reranker/PRM.py:64,90-92: nn.TransformerEncoderLayer(d, heads, d_ff, dropout = 0) under a key-padding mask) ----------------
+ * X [B, n, d] list-major (the reference's [n, B, d] transpose is a view: lists are independent); pad uint8 [B, n], 1 = padded slot.
+ *   QKV = X Win^T + bin (Win [3d, d], q | k | v),  P_h = softmax_j(q_h . k_h / sqrt(d / heads)) over the keys with pad == 0,
+ *   A = concat_h(P_h V_h) Wo^T + bo,  X1 = LN1(X + A),  Y = LN2(X1 + relu(X1 W1^T + b1) W2^T + b2)       (LayerNorm eps 1e-5)
+ * Wo [d, d], W1 [d_ff, d], W2 [d, d_ff]; g1, be1, g2, be2 [d] are the LayerNorms' weight and bias.  Padded slots are masked as keys
+ * only; as queries they are rows like any other.  The mask is taken per slot (valid slots need not be a prefix); every list must have
+ * at least one valid key.  All fp32, every float tensor 16-byte aligned.  All six products run on the f32-input MFMA; no float
+ * atomics, reruns are bitwise identical.
+ * RC_OK when 1 <= n <= 64, d % 16 == 0, 16 <= d <= 128, heads divides d with (d / heads) % 4 == 0, d_ff % 16 == 0, 16 <= d_ff <= 256
+ * AND a list with the backward's intermediates fits the 160 KB LDS (with NP = n rounded up to 16:
+ * 4 NP (3 (d + 4) + max(5 d + 8, 2 d + d_ff + 12) + 2) + 256 (NP + 4) bytes: n <= 64 at d <= 48 and at d = 64 with d_ff <= 224; n <= 48 at d = 64 with d_ff >= 240 and at d = 80; n <= 32 at d >= 96), else
+ * RC_ERR_UNSUPPORTED with the reason in rc_last_error_string() (host logic, no GPU needed); the entry points below check the same
+ * envelope themselves, and 1 <= B <= 2^24.                                                                                          */
+enum rc_status rc_listenc_check_shape(int n, int d, int heads, int d_ff);
+/* one encoder block (PRM.py:64, :90-92) in ONE launch: a workgroup holds a list's rows and every intermediate in LDS; X is read once,
+ * Y [B, n, d] is written once (all n slots of every list), nothing is kept for the backward pass.                                   */
+enum rc_status rc_listenc_block_fwd(const float* X, const uint8_t* pad, const float* Win, const float* bin, const float* Wo,
+                                    const float* bo, const float* g1, const float* be1, const float* W1, const float* b1,
+                                    const float* W2, const float* b2, const float* g2, const float* be2, int64_t B, int n, int d,
+                                    int heads, int d_ff, float* Y, rc_stream_t stream);
+/* bytes of the caller workspace (256-byte aligned) of rc_listenc_block_bwd: one partial of every weight and bias gradient per
+ * workgroup, at most min(256, 128 MB / bytes of one partial) of them, so the size does not grow with B past 256 lists; 0 outside the
+ * envelope                                                                                                                          */
+size_t rc_listenc_block_bwd_workspace_bytes(int64_t B, int n, int d, int heads, int d_ff);
+/* autograd of the block (PRM.py:64, :90-92) from dY [B, n, d]: the block is recomputed from X.  dX [B, n, d] is written once; the
+ * twelve weight and bias gradients are summed over all lists.  dY on padded slots is used like any other row's.  Two launches: the
+ * list kernel (a workgroup walks its lists and writes its partial once at d = 64, d_ff = 128, where the weight-gradient tiles stay in
+ * registers; other shapes add into the partial per list) and the fixed-order reduce of the per-workgroup partials.                   */
+enum rc_status rc_listenc_block_bwd(const float* dY, const float* X, const uint8_t* pad, const float* Win, const float* bin,
+                                    const float* Wo, const float* bo, const float* g1, const float* be1, const float* W1,
+                                    const float* b1, const float* W2, const float* b2, const float* g2, const float* be2, int64_t B,
+                                    int n, int d, int heads, int d_ff, void* workspace, size_t ws_bytes, float* dX, float* dWin,
+                                    float* dbin, float* dWo, float* dbo, float* dg1, float* dbe1, float* dW1, float* db1, float* dW2,
+                                    float* db2, float* dg2, float* dbe2, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -308,6 +308,10 @@ SIGNATURES = {
     "rc_dcnv2_mix_layer_fwd": (_i, [_p] * 8 + [_i64, _i, _i, _i, _p, _p]),
     "rc_dcnv2_mix_layer_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "rc_dcnv2_mix_layer_bwd": (_i, [_p] * 9 + [_i64, _i, _i, _i, _p, _sz] + [_p] * 8 + [_p]),
+    "rc_listenc_check_shape": (_i, [_i, _i, _i, _i]),
+    "rc_listenc_block_fwd": (_i, [_p] * 14 + [_i64, _i, _i, _i, _i, _p, _p]),
+    "rc_listenc_block_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "rc_listenc_block_bwd": (_i, [_p] * 15 + [_i64, _i, _i, _i, _i, _p, _sz] + [_p] * 13 + [_p]),
 }
 
 _lib = None

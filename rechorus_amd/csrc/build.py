@@ -52,6 +52,7 @@ SOURCES = [
     "kda.hip",
     "chorus.hip",
     "dcnv2.hip",
+    "listenc.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

@@ -2989,6 +2989,83 @@ def dcnv2_mix_layer_bwd(dXnext, X0, Xl, U, V, Cw, bias, Wg, bg, workspace=None):
     return dXl, dX0, dU, dV, dC, dbias, dWg, dbg
 
 
+# ---- list encoder block (models/reranker/PRM.py:64,90-92: nn.TransformerEncoderLayer under a key-padding mask) -------------------------
+
+LISTENC_WEIGHTS = ("Win", "bin", "Wo", "bo", "g1", "be1", "W1", "b1", "W2", "b2", "g2", "be2")
+
+
+def listenc_check_shape(n, d, heads, d_ff):
+    """rc_listenc_check_shape (host logic): 1 <= n <= 64, d a multiple of 16 in [16, 128], heads a divisor of d with d / heads a
+    multiple of 4, d_ff a multiple of 16 in [16, 256], and a list with the backward's intermediates within the LDS; raises ValueError
+    with the library's reason otherwise"""
+    lib = _lib.load()
+    if lib.rc_listenc_check_shape(int(n), int(d), int(heads), int(d_ff)) != _lib.RC_OK:
+        raise ValueError("list encoder on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+class ListEncWorkspace:
+    """the scratch of rc_listenc_block_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
+    freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
+    that wrote it, so the blocks of a stack share one workspace."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, B, n, d, heads, d_ff, device):
+        key = (int(B), int(n), int(d), int(heads), int(d_ff), torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = _lib.load().rc_listenc_block_bwd_workspace_bytes(*key[:5])
+            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return buf
+
+
+def _listenc_shapes(X, pad, weights, heads):
+    if X.dim() != 3 or X.numel() == 0:
+        raise ValueError(f"list_encoder_block: X must be [lists, slots, width] with at least one list, got {tuple(X.shape)}")
+    B, n, d = X.shape
+    if tuple(pad.shape) != (B, n):
+        raise ValueError(f"list_encoder_block: pad must be [{B}, {n}], got {tuple(pad.shape)}")
+    if len(weights) != len(LISTENC_WEIGHTS):
+        raise ValueError(f"list_encoder_block: twelve weights are needed ({', '.join(LISTENC_WEIGHTS)})")
+    W1 = weights[6]
+    if W1.dim() != 2 or W1.shape[1] != d:
+        raise ValueError(f"list_encoder_block: W1 must be [d_ff, {d}], got {tuple(W1.shape)}")
+    dff = W1.shape[0]
+    listenc_check_shape(n, d, heads, dff)
+    shapes = ((3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,), (dff, d), (dff,), (d, dff), (d,), (d,), (d,))
+    for name, W, shape in zip(LISTENC_WEIGHTS, weights, shapes):
+        if tuple(W.shape) != shape:
+            raise ValueError(f"list_encoder_block: {name} must be {list(shape)}, got {tuple(W.shape)}")
+    return B, n, d, dff
+
+
+def listenc_block_fwd(X, pad, weights, heads):
+    """rc_listenc_block_fwd: Y [B, n, d] = LN2(X1 + relu(X1 W1^T + b1) W2^T + b2), X1 = LN1(X + MHA(X; pad)), one launch.
+    pad uint8 [B, n], 1 = padded slot (masked as a key); weights in LISTENC_WEIGHTS order"""
+    B, n, d, dff = _listenc_shapes(X, pad, weights, heads)
+    f32 = torch.float32
+    Y = torch.empty(X.shape, dtype=f32, device=X.device)
+    _lib.call("rc_listenc_block_fwd", _ptr(X, f32, "X"), _ptr(pad, torch.uint8, "pad"),
+              *[_ptr(W, f32, k) for k, W in zip(LISTENC_WEIGHTS, weights)], B, n, d, int(heads), dff, _ptr(Y, f32, "Y"), _stream())
+    return Y
+
+
+def listenc_block_bwd(dY, X, pad, weights, heads, workspace=None):
+    """rc_listenc_block_bwd -> (dX, [the twelve gradients in LISTENC_WEIGHTS order]): the block is recomputed from X; two launches"""
+    B, n, d, dff = _listenc_shapes(X, pad, weights, heads)
+    if dY.shape != X.shape:
+        raise ValueError(f"listenc_block_bwd: dY must be {tuple(X.shape)}, got {tuple(dY.shape)}")
+    dev, f32 = X.device, torch.float32
+    ws = (workspace if workspace is not None else ListEncWorkspace()).get(B, n, d, heads, dff, dev)
+    dX = torch.empty(X.shape, dtype=f32, device=dev)
+    grads = [torch.empty(tuple(W.shape), dtype=f32, device=dev) for W in weights]
+    _lib.call("rc_listenc_block_bwd", _ptr(dY, f32, "dY"), _ptr(X, f32, "X"), _ptr(pad, torch.uint8, "pad"),
+              *[_ptr(W, f32, k) for k, W in zip(LISTENC_WEIGHTS, weights)], B, n, d, int(heads), dff, C.c_void_p(ws.data_ptr()), ws.numel(),
+              _ptr(dX, f32, "dX"), *[_ptr(G, f32, "d" + k) for k, G in zip(LISTENC_WEIGHTS, grads)], _stream())
+    return dX, grads
+
+
 # ---- FinalMLP: feature gates + first stream layers, bilinear fusion (models/context/FinalMLP.py:141-249) -------------------------------
 
 def finalmlp_check_shape(n_fields, emb_size, gate_in_1, first_1, gate_in_2, first_2, x_dim, y_dim, num_heads, drop_p_1=0.0, drop_p_2=0.0):

@@ -539,6 +539,45 @@ def dcnv2_mix_layer_eval(X0, Xl, U, V, C, bias, Wg, bg):
     return engine.dcnv2_mix_layer_fwd(*[t.detach().contiguous() for t in (X0, Xl, U, V, C, bias, Wg, bg)])
 
 
+class _ListEncoderBlockFn(torch.autograd.Function):
+    """One post-norm encoder block over candidate lists (models/reranker/PRM.py:64,90-92) on rc_listenc_block_fwd / _bwd.  Saves X,
+    the mask and the weights only: the backward recomputes the block.  No host synchronisation and no data-dependent allocation:
+    capture-safe."""
+
+    @staticmethod
+    def forward(ctx, X, pad, heads, workspace, *weights):
+        det = [t.detach().contiguous() for t in (X, *weights)]
+        pad = pad.detach().to(torch.uint8).contiguous()
+        Y = engine.listenc_block_fwd(det[0], pad, det[1:], heads)
+        ctx.save_for_backward(pad, *det)
+        ctx.heads, ctx.workspace = heads, workspace
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        pad, X, *weights = ctx.saved_tensors
+        dX, grads = engine.listenc_block_bwd(dY.contiguous(), X, pad, weights, ctx.heads, workspace=ctx.workspace)
+        return (dX, None, None, None, *grads)
+
+
+def list_encoder_block(X, pad, weights, heads, workspace=None):
+    """nn.TransformerEncoderLayer(d, heads, d_ff, dropout=0) (post-norm, ReLU, eps 1e-5) over lists X [B, n, d] under the key-padding
+    mask pad [B, n] (true / 1 = padded slot) (models/reranker/PRM.py:64,90-92) -> [B, n, d], as ONE autograd node (one forward launch,
+    one backward launch plus the fixed-order reduce).  weights: in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias,
+    norm1.weight, norm1.bias, linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm2.weight, norm2.bias
+    (engine.LISTENC_WEIGHTS order).  workspace: the model's engine.ListEncWorkspace, reused step after step"""
+    return _ListEncoderBlockFn.apply(X, pad, int(heads), workspace, *weights)
+
+
+def list_encoder_block_eval(X, pad, weights, heads):
+    """the same block on the evaluation path: forward only, raises when autograd is recording"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (X, *weights)):
+        raise RuntimeError("list_encoder_block_eval is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through list_encoder_block)")
+    return engine.listenc_block_fwd(X.detach().contiguous(), pad.detach().to(torch.uint8).contiguous(),
+                                    [t.detach().contiguous() for t in weights], int(heads))
+
+
 class _FinalMlpGateFn(torch.autograd.Function):
     """FinalMLP's feature gates and the first layer of both streams (models/context/FinalMLP.py:188-221, :100-101) on
     rc_finalmlp_gate_fwd / _bwd.  Saves X, the gate inputs, the weights and A_1, A_2 (their own ReLU / dropout masks): the gates are

@@ -28,7 +28,7 @@ for p in (HERE, ROOT):
 
 from utils import utils  # noqa: E402
 
-MODEL_PACKAGES = ('models.general', 'models.sequential', 'models.context', 'models.context_seq')
+MODEL_PACKAGES = ('models.general', 'models.sequential', 'models.context', 'models.context_seq', 'models.reranker')
 
 
 def parse_global_args(parser):
@@ -62,7 +62,8 @@ def find_class(kind, name):
             mod = importlib.import_module('{}.{}'.format(pkg, base))
         except ModuleNotFoundError:
             continue
-        return getattr(mod, base + mode)
+        if hasattr(mod, base + mode):
+            return getattr(mod, base + mode)
     raise ValueError('unknown model {!r} (looked in {})'.format(base + mode, MODEL_PACKAGES))
 
 

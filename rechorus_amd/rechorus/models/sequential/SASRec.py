@@ -25,6 +25,7 @@ from utils import layers
 
 class SASRecBase(object):
     candidate_permutation_equivariant = True  # every candidate is scored on its own
+    return_vectors = False  # forward also returns u_v / i_v (set per instance by the reranker base on its frozen ranker)
 
     @staticmethod
     def parse_model_args(parser):
@@ -92,7 +93,13 @@ class SASRecBase(object):
         his_vector = self._encode(feed_dict)
         rows = torch.arange(batch_size, device=i_ids.device)
         prediction = hnn.bprmf_scores(his_vector, self.i_embeddings.weight, rows, i_ids)
-        return {'prediction': prediction.view(batch_size, -1)}
+        out = {'prediction': prediction.view(batch_size, -1)}
+        if self.return_vectors:
+            # the reference's forward always hands back u_v / i_v (SASRec.py:82-85); only the rerankers built on a frozen base
+            # ranker read them (models/BaseRerankerModel.py sets the attribute on its ranker), so nobody else pays for the gather
+            out['u_v'] = his_vector[:, None, :].expand(-1, i_ids.shape[1], -1)
+            out['i_v'] = self.i_embeddings(i_ids)
+        return out
 
     # ---- large-table mode: row-wise update of the item table, dense step of everything small -----------
     def hip_rowwise_supported(self):
