@@ -100,6 +100,57 @@ def _hyper_ref(hyper):
     return C.byref(hyper) if hyper is not None else None
 
 
+def _check_shape(label, entry, *ints, extra=()):
+    """the body of every *_check_shape function: the library's host-side check `entry` on the integers (and whatever else `extra`
+    brings: floats, a host array); its refusal is raised as a ValueError that names the model and gives the library's reason"""
+    lib = _lib.load()
+    if getattr(lib, entry)(*(int(x) for x in ints), *extra) != _lib.RC_OK:
+        raise ValueError(label + " on the HIP engine: " + lib.rc_last_error_string().decode())
+
+
+def _step_outputs(B, Cn, dev, want_pred):
+    """(pred [B, C] | None, loss_vec [B], gpred [B, C]) of a fused front kernel, allocated in this order"""
+    f32 = torch.float32
+    pred = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
+    return pred, torch.empty(B, dtype=f32, device=dev), torch.empty((B, Cn), dtype=f32, device=dev)
+
+
+class _ShapeWorkspace:
+    """The scratch of one model's kernels: one uint8 buffer per (shape, device), allocated at the size the library's query gives
+    and never freed or replaced while the owner lives -- a captured hipGraph replays on its address.  A subclass is data:
+    _query   the library's size query
+    _shape   the names of get()'s shape arguments; get(*shape, device) takes them in this order
+    _order   the same names in the order the query takes them
+    _floor   the smallest allocation in bytes (256 where an empty workspace must still have an address)
+    `generation` counts the forwards that stamped the workspace (stamp(): DirectAU's and ContraRec's forward wrappers), so that a
+    backward can tell whether another forward has overwritten what it reads."""
+    _query, _shape, _order, _floor = None, (), None, 0
+
+    def __init__(self):
+        self._bufs = {}
+        self.generation = 0
+
+    def stamp(self):
+        self.generation += 1
+        return self.generation
+
+    def _buffer(self, query, key, args, device):
+        key += (torch.device(device),)
+        buf = self._bufs.get(key)
+        if buf is None:
+            nbytes = getattr(_lib.load(), query)(*args)
+            buf = self._bufs[key] = torch.empty(max(nbytes, self._floor), dtype=torch.uint8, device=device)
+        return buf
+
+    def get(self, *args, **kw):
+        names = self._shape + ("device",)
+        given = dict(zip(names, args), **kw)
+        if len(args) + len(kw) != len(names) or set(given) != set(names):
+            raise TypeError(f"{type(self).__name__}.get takes ({', '.join(names)})")
+        shape = {k: int(given[k]) for k in self._shape}
+        return self._buffer(self._query, tuple(shape.values()), [shape[k] for k in self._order or self._shape], given["device"])
+
+
 # ---- forward ---------------------------------------------------------------------------
 
 def gather_rows(W, ids):
@@ -177,9 +228,7 @@ def bprmf_fwd_bwd(U, I, uid, iid, inv_b=None, want_pred=True):
     if inv_b is None:
         inv_b = 1.0 / B
     dev = U.device
-    pred = torch.empty((B, Cn), dtype=torch.float32, device=dev) if want_pred else None
-    loss_vec = torch.empty(B, dtype=torch.float32, device=dev)
-    gpred = torch.empty((B, Cn), dtype=torch.float32, device=dev)
+    pred, loss_vec, gpred = _step_outputs(B, Cn, dev, want_pred)
     ugrad = torch.empty((B, d), dtype=torch.float32, device=dev)
     _lib.call("rc_bprmf_fwd_bwd", _ptr(U, torch.float32, "U"), _ptr(I, torch.float32, "I"),
               _ptr(uid, torch.int64, "uid"), _ptr(iid, torch.int64, "iid"), B, Cn, d, float(inv_b),
@@ -191,17 +240,21 @@ def bprmf_fwd_bwd(U, I, uid, iid, inv_b=None, want_pred=True):
 
 # ---- sort + segmented update --------------------------------------------------------------
 
-def sort_ids(ids, n_rows):
-    """Stable sort of a flat id list -> (keys uint32-as-int32 tensor, perm)."""
+def sort_ids(ids, n_rows, ids_b=None, key_base_b=0):
+    """Stable sort of a flat id list -> (keys uint32-as-int32 tensor, perm).
+    ids_b: a second list sorted jointly with the first -- its ids are keyed key_base_b + id, its occurrences numbered behind the
+    first list's, and n_rows bounds the joint keys."""
     ids_flat = ids.reshape(-1)
-    n = ids_flat.numel()
+    b_flat = ids_b.reshape(-1) if ids_b is not None else None
+    n_a, n_b = ids_flat.numel(), (b_flat.numel() if b_flat is not None else 0)
+    n = n_a + n_b
     dev = ids.device
     keys = torch.empty(n, dtype=torch.int32, device=dev)  # bit pattern is uint32
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     nbytes = _lib.load().rc_sort_workspace_bytes(n)
     ws = workspace(nbytes, dev, "sort")
-    _lib.call("rc_sort_ids", _ptr(ids_flat, torch.int64, "ids"), n, None, 0, 0, int(n_rows),
-              _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"),
+    _lib.call("rc_sort_ids", _ptr(ids_flat, torch.int64, "ids"), n_a, None if b_flat is None else _ptr(b_flat, torch.int64, "ids_b"), n_b,
+              int(key_base_b), int(n_rows), _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"),
               *_ws_args(ws))
     return keys, perm
 
@@ -410,9 +463,7 @@ def bprmf_fwd_bwd_update(U, I, uid, iid, single, hyper, mI=None, vI=None, inv_b=
         inv_b = 1.0 / B
     dev = U.device
     f32 = torch.float32
-    pred = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
-    loss_vec = torch.empty(B, dtype=f32, device=dev)
-    gpred = torch.empty((B, Cn), dtype=f32, device=dev)
+    pred, loss_vec, gpred = _step_outputs(B, Cn, dev, want_pred)
     ugrad = torch.empty((B, d), dtype=f32, device=dev)
     _lib.call("rc_bprmf_fwd_bwd_update", _ptr(U, f32, "U"), _ptr(I, f32, "I"),
               _ptr(mI, f32, "mI", True), _ptr(vI, f32, "vI", True),
@@ -426,17 +477,19 @@ def bprmf_fwd_bwd_update(U, I, uid, iid, single, hyper, mI=None, vI=None, inv_b=
 
 def segmented_update(keys, perm, src, hyper=None, W=None, m=None, v=None, coef=None,
                      src_index=None, div=1, dense_grad=None, skip_singletons=False, heads=None,
-                     n_heads=None, src2=None, n_split=None):
+                     n_heads=None, src2=None, n_split=None, key_base=0, occ_base=0):
     """rc_segmented_update: per distinct row r, grad_r = sum coef[o]*src[srow(o)], then either
     write dense_grad[r] or apply the optimizer to W[r] (and m, v) in place.
-    n_split (with src2): occurrences >= n_split take plain rows src2[o - n_split]."""
+    n_split (with src2): occurrences >= n_split take plain rows src2[o - n_split].
+    key_base, occ_base: keys / perm are a slice of a joint sort (sort_ids with a second list) -- what the slice's keys and
+    occurrence numbers start at."""
     n_occ = keys.numel()
     d = src.shape[-1]
     ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, d), keys.device, "seg")
-    # an omitted n_split: every occurrence takes `src`; a given one needs its src2.  (0, 0: key_base, occ_base)
+    # an omitted n_split: every occurrence takes `src`; a given one needs its src2
     _lib.call("rc_segmented_update", *_table_args(W, m, v), d, _ptr(keys, torch.int32, "keys"), _ptr(perm, torch.int32, "perm"), n_occ,
-              *_source_args(coef, src, src_index, div, src2, n_split, default=n_occ, need_src2=n_split is not None), 0, 0,
-              _hyper_ref(hyper), _ptr(dense_grad, torch.float32, "dense_grad", allow_none=True),
+              *_source_args(coef, src, src_index, div, src2, n_split, default=n_occ, need_src2=n_split is not None),
+              int(key_base), int(occ_base), _hyper_ref(hyper), _ptr(dense_grad, torch.float32, "dense_grad", allow_none=True),
               _ptr(heads, torch.int32, "heads", True), _ptr(n_heads, torch.int32, "n_heads", True),
               _lib.RC_SEG_SKIP_SINGLETONS if skip_singletons else 0, *_ws_args(ws))
 
@@ -2397,9 +2450,7 @@ def owner_backward(I, mI, vI, Uall, t32, rows, g, single, n_tuples, hyper):
 def lgcn_check_shape(d, n_layers, n_nodes=0, nnz=0):
     """rc_lgcn_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 0 <= n_layers <= 8, N < 2^31, nnz < 2^31; raises ValueError
     with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_lgcn_check_shape(int(d), int(n_layers), int(n_nodes), int(nnz)) != _lib.RC_OK:
-        raise ValueError("LightGCN on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("LightGCN", "rc_lgcn_check_shape", d, n_layers, n_nodes, nnz)
 
 
 def _lgcn_check(graph, d, n_layers):
@@ -2446,27 +2497,14 @@ def lgcn_propagate_bwd(graph, grad_user, grad_item, n_layers):
 def directau_check_shape(d, batch=1):
     """rc_directau_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 1 <= batch <= 2^20; raises ValueError with the library's
     reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_directau_check_shape(int(d), int(batch)) != _lib.RC_OK:
-        raise ValueError("DirectAU on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("DirectAU", "rc_directau_check_shape", d, batch)
 
 
-class DirectAUWorkspace:
+class DirectAUWorkspace(_ShapeWorkspace):
     """the scratch of rc_directau_fwd / _bwd, one buffer per (batch, d) that is never freed or moved while the owner lives: a
     captured training step replays on the same memory.  `generation` counts forwards, so that a backward can tell whether another
     forward has overwritten what it reads."""
-
-    def __init__(self):
-        self._bufs = {}
-        self.generation = 0
-
-    def get(self, batch, d, device):
-        key = (int(batch), int(d), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_directau_workspace_bytes(int(d), int(batch))
-            buf = self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return buf
+    _query, _shape, _order = "rc_directau_workspace_bytes", ("batch", "d"), ("d", "batch")
 
 
 def _dau_rows(name, t, batch, d):
@@ -2487,8 +2525,7 @@ def directau_fwd(user_e, item_e, gamma=1.0, sets=3, workspace=None, user_ids=Non
         if ids is not None and ids.numel() != B:
             raise ValueError(f"directau: {name} must hold {B} ids")
     ws = workspace if workspace is not None else DirectAUWorkspace()   # None: a private one, alive as long as the caller keeps it
-    buf = ws.get(B, d, user_e.device)
-    ws.generation += 1
+    buf, gen = ws.get(B, d, user_e.device), ws.stamp()
     out = torch.empty(4, dtype=torch.float32, device=user_e.device)
     pred = torch.empty((B, 1), dtype=torch.float32, device=user_e.device) if prediction else None
     uid = user_ids.reshape(-1).contiguous() if user_ids is not None else None
@@ -2497,7 +2534,7 @@ def directau_fwd(user_e, item_e, gamma=1.0, sets=3, workspace=None, user_ids=Non
               _ptr(item_e, torch.float32, "item_e"), _ptr(iid, torch.int64, "item_ids", allow_none=True), B, d, float(gamma),
               int(sets), C.c_void_p(buf.data_ptr()), buf.numel(), _ptr(pred, torch.float32, "prediction", allow_none=True),
               _ptr(out, torch.float32, "out"), _stream())
-    return out, pred, buf, ws.generation
+    return out, pred, buf, gen
 
 
 def directau_bwd(grad_out, batch, d, coef, buf, want_user=True, want_item=True):
@@ -2519,25 +2556,13 @@ def directau_bwd(grad_out, batch, d, coef, buf, want_user=True, want_item=True):
 def comirec_check_shape(d, attn_size, K, L):
     """rc_comirec_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 1 <= attn_size <= 64, 1 <= K <= 16, 1 <= L <= 256; raises
     ValueError with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_comirec_check_shape(int(d), int(attn_size), int(K), int(L)) != _lib.RC_OK:
-        raise ValueError("ComiRec on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("ComiRec", "rc_comirec_check_shape", d, attn_size, K, L)
 
 
-class ComiRecWorkspace:
+class ComiRecWorkspace(_ShapeWorkspace):
     """the scratch of rc_comirec_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
     freed or moved while the owner lives"""
-
-    def __init__(self):
-        self._bufs = {}
-
-    def get(self, d, attn_size, K, L, batch, device):
-        key = (int(d), int(attn_size), int(K), int(L), int(batch), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_comirec_workspace_bytes(int(d), int(attn_size), int(K), int(L), int(batch))
-            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return buf
+    _query, _shape, _floor = "rc_comirec_workspace_bytes", ("d", "attn_size", "K", "L", "batch"), 256
 
 
 def _comirec_shapes(item_emb, pos_emb, W1, b1, W2, b2, hist, lengths):
@@ -2617,9 +2642,7 @@ def comirec_score_max(interests, item_emb, iid):
 def contra_check_shape(d, batch=1):
     """rc_contra_check_shape (host logic): d % 4 == 0, 4 <= d <= 256, 1 <= batch <= 2^19; raises ValueError with the library's
     reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_contra_check_shape(int(d), int(batch)) != _lib.RC_OK:
-        raise ValueError("ContraRec on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("ContraRec", "rc_contra_check_shape", d, batch)
 
 
 def contra_layout(d, batch):
@@ -2645,21 +2668,10 @@ def contra_first_split_batch():
     return B
 
 
-class ContraWorkspace:
+class ContraWorkspace(_ShapeWorkspace):
     """the scratch of rc_contra_loss_fwd / _bwd, one buffer per (batch, d) that is never freed or moved while the owner lives.
     `generation` counts forwards, so that a backward can tell whether another forward has overwritten what it reads."""
-
-    def __init__(self):
-        self._bufs = {}
-        self.generation = 0
-
-    def get(self, batch, d, device):
-        key = (int(batch), int(d), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_contra_workspace_bytes(int(d), int(batch))
-            buf = self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return buf
+    _query, _shape, _order = "rc_contra_workspace_bytes", ("batch", "d"), ("d", "batch")
 
 
 def _contra_args(va, vb, labels):
@@ -2677,13 +2689,12 @@ def contra_loss_fwd(va, vb, labels, temperature, workspace=None):
     labels int64 [B] or None (InfoNCE)"""
     B, d = _contra_args(va, vb, labels)
     ws = workspace if workspace is not None else ContraWorkspace()
-    buf = ws.get(B, d, va.device)
-    ws.generation += 1
+    buf, gen = ws.get(B, d, va.device), ws.stamp()
     loss = torch.empty(1, dtype=torch.float32, device=va.device)
     _lib.call("rc_contra_loss_fwd", _ptr(va, torch.float32, "va"), _ptr(vb, torch.float32, "vb"),
               _ptr(labels, torch.int64, "labels", allow_none=True), B, d, float(temperature), C.c_void_p(buf.data_ptr()), buf.numel(),
               _ptr(loss, torch.float32, "loss"), _stream())
-    return loss, buf, ws.generation
+    return loss, buf, gen
 
 
 def contra_loss_bwd(grad_out, labels, batch, d, temperature, buf):
@@ -2727,29 +2738,15 @@ def seq_pos_grad_fwdpos(dX, lengths, B, L, n_pos):
 def buir_check_shape(d, batch=1):
     """rc_buir_check_shape (host logic): d % 16 == 0, 16 <= d <= 128, 1 <= batch <= 2^20; raises ValueError with the library's
     reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_buir_check_shape(int(d), int(batch)) != _lib.RC_OK:
-        raise ValueError("BUIR on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("BUIR", "rc_buir_check_shape", d, batch)
 
 
-class BuirWorkspace:
+class BuirWorkspace(_ShapeWorkspace):
     """the scratch of rc_buir_fwd / _bwd (the per-workgroup partials of loss, dW and db), one buffer per (batch, d) that is never
-    freed or moved while the owner lives: a captured training step replays on the same memory.  `generation` counts the launches
-    that wrote it.  Nothing in it outlives the call that wrote it (the backward pass recomputes the forward values from the
-    tables), so two pending losses may share one workspace."""
-
-    def __init__(self):
-        self._bufs = {}
-        self.generation = 0
-
-    def get(self, batch, d, device):
-        key = (int(batch), int(d), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_buir_workspace_bytes(int(d), int(batch))
-            buf = self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.generation += 1
-        return buf
+    freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
+    that wrote it (the backward pass recomputes the forward values from the tables), so two pending losses may share one
+    workspace."""
+    _query, _shape, _order = "rc_buir_workspace_bytes", ("batch", "d"), ("d", "batch")
 
 
 def _buir_shapes(user_online, user_target, item_online, item_target, W, b, uid, iid):
@@ -2848,26 +2845,14 @@ def ema_update(target_a, online_a, target_b, online_b, momentum):
 def autoint_check_shape(n_fields, d_in, attention_size, num_heads):
     """rc_autoint_check_shape (host logic): 2 <= fields <= 32, d_in % 4 == 0, 4 <= d_in <= 128, 4 <= attention_size <= 64, num_heads a
     divisor of attention_size; raises ValueError with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_autoint_check_shape(int(n_fields), int(d_in), int(attention_size), int(num_heads)) != _lib.RC_OK:
-        raise ValueError("AutoInt on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("AutoInt", "rc_autoint_check_shape", n_fields, d_in, attention_size, num_heads)
 
 
-class AutoIntWorkspace:
+class AutoIntWorkspace(_ShapeWorkspace):
     """the scratch of rc_autoint_layer_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
     freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
     that wrote it, so the layers of a stack share one workspace."""
-
-    def __init__(self):
-        self._bufs = {}
-
-    def get(self, n, n_fields, d_in, attention_size, num_heads, device):
-        key = (int(n), int(n_fields), int(d_in), int(attention_size), int(num_heads), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_autoint_workspace_bytes(*key[:5])
-            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return buf
+    _query, _shape, _floor = "rc_autoint_workspace_bytes", ("n", "n_fields", "d_in", "attention_size", "num_heads"), 256
 
 
 def _autoint_shapes(X, Wq, Wk, Wv, Wr, br, heads):
@@ -2917,26 +2902,14 @@ def autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, dY, heads, workspace=None):
 def dcnv2_check_shape(width, low_rank, expert_num):
     """rc_dcnv2_check_shape (host logic): width = fields * emb_size a multiple of 4 in [8, 1024], low_rank a multiple of 4 in
     [4, 128], expert_num in [1, 4]; raises ValueError with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_dcnv2_check_shape(int(width), int(low_rank), int(expert_num)) != _lib.RC_OK:
-        raise ValueError("DCNv2 on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("DCNv2", "rc_dcnv2_check_shape", width, low_rank, expert_num)
 
 
-class DCNv2Workspace:
+class DCNv2Workspace(_ShapeWorkspace):
     """the scratch of rc_dcnv2_mix_layer_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
     freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
     that wrote it, so the layers of a stack share one workspace."""
-
-    def __init__(self):
-        self._bufs = {}
-
-    def get(self, n, width, low_rank, expert_num, device):
-        key = (int(n), int(width), int(low_rank), int(expert_num), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_dcnv2_mix_layer_bwd_workspace_bytes(*key[:4])
-            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return buf
+    _query, _shape, _floor = "rc_dcnv2_mix_layer_bwd_workspace_bytes", ("n", "width", "low_rank", "expert_num"), 256
 
 
 def _dcnv2_shapes(X0, Xl, U, V, Cw, bias, Wg, bg):
@@ -2998,26 +2971,14 @@ def listenc_check_shape(n, d, heads, d_ff):
     """rc_listenc_check_shape (host logic): 1 <= n <= 64, d a multiple of 16 in [16, 128], heads a divisor of d with d / heads a
     multiple of 4, d_ff a multiple of 16 in [16, 256], and a list with the backward's intermediates within the LDS; raises ValueError
     with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_listenc_check_shape(int(n), int(d), int(heads), int(d_ff)) != _lib.RC_OK:
-        raise ValueError("list encoder on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("list encoder", "rc_listenc_check_shape", n, d, heads, d_ff)
 
 
-class ListEncWorkspace:
+class ListEncWorkspace(_ShapeWorkspace):
     """the scratch of rc_listenc_block_bwd (the per-workgroup partials of the weight gradients), one buffer per shape that is never
     freed or moved while the owner lives: a captured training step replays on the same memory.  Nothing in it outlives the call
     that wrote it, so the blocks of a stack share one workspace."""
-
-    def __init__(self):
-        self._bufs = {}
-
-    def get(self, B, n, d, heads, d_ff, device):
-        key = (int(B), int(n), int(d), int(heads), int(d_ff), torch.device(device))
-        buf = self._bufs.get(key)
-        if buf is None:
-            nbytes = _lib.load().rc_listenc_block_bwd_workspace_bytes(*key[:5])
-            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return buf
+    _query, _shape, _floor = "rc_listenc_block_bwd_workspace_bytes", ("B", "n", "d", "heads", "d_ff"), 256
 
 
 def _listenc_shapes(X, pad, weights, heads):
@@ -3072,10 +3033,8 @@ def finalmlp_check_shape(n_fields, emb_size, gate_in_1, first_1, gate_in_2, firs
     """rc_finalmlp_check_shape (host logic): 3 <= fields <= 32, emb_size % 4 == 0 in [4, 128], gate inputs / first-layer widths / stream
     outputs multiples of 4 in [4, 256], num_heads a divisor of both stream outputs, dropout in [0, 1), a 32-row tile within the LDS;
     raises ValueError with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_finalmlp_check_shape(int(n_fields), int(emb_size), int(gate_in_1), int(first_1), int(gate_in_2), int(first_2), int(x_dim),
-                                   int(y_dim), int(num_heads), float(drop_p_1), float(drop_p_2)) != _lib.RC_OK:
-        raise ValueError("FinalMLP on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("FinalMLP", "rc_finalmlp_check_shape", n_fields, emb_size, gate_in_1, first_1, gate_in_2, first_2, x_dim, y_dim, num_heads,
+                 extra=(float(drop_p_1), float(drop_p_2)))
 
 
 def finalmlp_fusion_check_shape(x_dim, y_dim, num_heads):
@@ -3086,21 +3045,15 @@ def finalmlp_fusion_check_shape(x_dim, y_dim, num_heads):
         raise ValueError("FinalMLP on the HIP engine: " + lib.rc_last_error_string().decode())
 
 
-class FinalMLPWorkspace:
+class FinalMLPWorkspace(_ShapeWorkspace):
     """the scratch of rc_finalmlp_gate_bwd and rc_finalmlp_fusion_bwd (per-workgroup partials, the per-slab shares of dZin), one buffer
     per call kind and shape that is never freed or moved while the owner lives: a captured training step replays on the same memory"""
-
-    def __init__(self):
-        self._bufs = {}
+    _query, _floor = {"gate": "rc_finalmlp_gate_workspace_bytes", "fusion": "rc_finalmlp_fusion_workspace_bytes"}, 256
 
     def get(self, kind, key, device):
-        key = (kind,) + tuple(int(k) for k in key) + (torch.device(device),)
-        buf = self._bufs.get(key)
-        if buf is None:
-            fn = {"gate": "rc_finalmlp_gate_workspace_bytes", "fusion": "rc_finalmlp_fusion_workspace_bytes"}[kind]
-            nbytes = getattr(_lib.load(), fn)(*key[1:-1])
-            buf = self._bufs[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return buf
+        """key: the arguments of the kind's size query"""
+        key = tuple(int(k) for k in key)
+        return self._buffer(self._query[kind], (kind,) + key, key, device)
 
 
 def _finalmlp_stream(X, n_cand, stream, which, need_seed=True):
@@ -3215,9 +3168,7 @@ def finalmlp_fusion_bwd(x, y, w_xy, w_x, w_y, dout, heads, workspace=None):
 def fpmc_check_shape(d, n_cand=1):
     """rc_fpmc_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate; raises ValueError with the library's
     reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_fpmc_check_shape(int(d), int(n_cand)) != _lib.RC_OK:
-        raise ValueError("FPMC on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("FPMC", "rc_fpmc_check_shape", d, n_cand)
 
 
 def fpmc_fwd_bwd_layout(d, n_cand):
@@ -3259,9 +3210,7 @@ def fpmc_fwd_bwd(UI, LI, IU, IL, uid, lid, iid, inv_b=None, want_pred=True):
     if inv_b is None:
         inv_b = 1.0 / B
     dev, f32 = UI.device, torch.float32
-    pred = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
-    loss_vec = torch.empty(B, dtype=f32, device=dev)
-    gpred = torch.empty((B, Cn), dtype=f32, device=dev)
+    pred, loss_vec, gpred = _step_outputs(B, Cn, dev, want_pred)
     ugrad = torch.empty((B, d), dtype=f32, device=dev)
     lgrad = torch.empty((B, d), dtype=f32, device=dev)
     _lib.call("rc_fpmc_fwd_bwd", *_fpmc_front_args(UI, LI, IU, IL, uid, lid, iid), B, Cn, d, float(inv_b),
@@ -3288,7 +3237,32 @@ def fpmc_item_update(keys, perm, heads, n_heads, gpred, UI, LI, uid, lid, hyper=
               _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
 
 
-class FpmcTrainer:
+class _RowwiseTrainer:
+    """What the row-wise trainers share: the optimizers their step covers, the hyper record `hyper` (step() counts its step), the
+    parameter tensors by name in `P` and the optimizer state of each in `state[name]` (new_opt_state)."""
+
+    def __init__(self, opt, lr, l2, beta1, beta2, eps):
+        if opt not in ("SGD", "Adam", "Adagrad"):
+            raise ValueError(f"{type(self).__name__}: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        self.opt = opt
+        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
+
+    def _new_state(self):
+        """fresh optimizer state for every tensor of P (after the subclass has checked the shapes: a refused one allocates nothing)"""
+        self.state = {name: new_opt_state(t, self.opt) for name, t in self.P.items()}
+
+    def _mv(self, name):
+        return self.state[name].get("m"), self.state[name].get("v")
+
+    def _tables(self, names):
+        """(W list, m list | None, v list | None) of the named tables, as the entry points with pointer arrays take them: an
+        optimizer without that state passes NULL for the whole array"""
+        mv = [self._mv(k) for k in names]
+        m, v = ([x[j] for x in mv] if mv[0][j] is not None else None for j in (0, 1))
+        return [self.P[k] for k in names], m, v
+
+
+class FpmcTrainer(_RowwiseTrainer):
     """Row-wise-optimizer FPMC training on the device tables UI [n_users, d], LI / IU / IL [n_items, d] (ui_embeddings, li_embeddings,
     iu_embeddings, il_embeddings of models/sequential/FPMC.py:36-39).
 
@@ -3297,52 +3271,36 @@ class FpmcTrainer:
     of the batch move (and only their optimizer state): the row-wise semantics of BprmfTrainer."""
 
     def __init__(self, UI, LI, IU, IL, opt="SGD", lr=1e-3, l2=0.0, beta1=0.9, beta2=0.999, eps=None):
-        if opt not in ("SGD", "Adam", "Adagrad"):
-            raise ValueError(f"FpmcTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        super().__init__(opt, lr, l2, beta1, beta2, eps)
         self.UI, self.LI, self.IU, self.IL = UI, LI, IU, IL
+        self.P = {"UI": UI, "LI": LI, "IU": IU, "IL": IL}
         self.d = UI.shape[1]
         fpmc_check_shape(self.d)
-        self.opt = opt
-        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
-        self.state = {name: new_opt_state(t, opt) for name, t in (("UI", UI), ("LI", LI), ("IU", IU), ("IL", IL))}
-
-    def _mv(self, name):
-        return self.state[name].get("m"), self.state[name].get("v")
-
-    def _query_update(self, W, name, keys, perm, grad, key_base, occ_base):
-        n_occ = keys.numel()
-        m, v = self._mv(name)
-        ws = workspace(_lib.load().rc_segmented_workspace_bytes(n_occ, self.d), keys.device, "seg")
-        # plain gradient rows, one per occurrence; keys / perm are a slice of the joint sort of users and last items
-        _lib.call("rc_segmented_update", *_table_args(W, m, v, need_W=True), self.d, _ptr(keys, torch.int32, "keys"),
-                  _ptr(perm, torch.int32, "perm"), n_occ, *_source_args(None, grad, None, 1, None, None, default=n_occ),
-                  int(key_base), int(occ_base), _hyper_ref(self.hyper), None, None, None, 0, *_ws_args(ws))
+        self._new_state()
 
     def step(self, uid, lid, iid, inv_b=None):
         """one training step; returns the device loss tensor (shape [1], no sync)"""
         B, Cn, d = _fpmc_shapes(self.UI, self.LI, self.IU, self.IL, uid, lid, iid)
         if inv_b is None:
             inv_b = 1.0 / B
-        dev = self.UI.device
         n_users, n_items = self.UI.shape[0], self.IU.shape[0]
         self.hyper.step += 1
         # candidates on their own; users + last items jointly (last items keyed behind the users)
         ikeys, iperm = sort_ids(iid, n_items)
         _, heads, n_heads = segment_heads(ikeys, iperm, want_single=False)
-        qkeys = torch.empty(2 * B, dtype=torch.int32, device=dev)
-        qperm = torch.empty(2 * B, dtype=torch.int32, device=dev)
-        ws = workspace(_lib.load().rc_sort_workspace_bytes(2 * B), dev, "sort")
-        _lib.call("rc_sort_ids", _ptr(uid, torch.int64, "uid"), B, _ptr(lid, torch.int64, "lid"), B, n_users, n_users + n_items,
-                  _ptr(qkeys, torch.int32, "keys"), _ptr(qperm, torch.int32, "perm"), *_ws_args(ws))
+        qkeys, qperm = sort_ids(uid, n_users + n_items, lid, n_users)
         _, loss_vec, gpred, ugrad, lgrad = fpmc_fwd_bwd(self.UI, self.LI, self.IU, self.IL, uid, lid, iid, inv_b, want_pred=False)
         loss = reduce_sum(loss_vec, inv_b)
         mIU, vIU = self._mv("IU")
         mIL, vIL = self._mv("IL")
         fpmc_item_update(ikeys, iperm, heads, n_heads, gpred, self.UI, self.LI, uid, lid, hyper=self.hyper, IU=self.IU, IL=self.IL,
                          m=(mIU, mIL), v=(vIU, vIL))
-        # the query side last: the item-side update above read the pre-step UI and LI
-        self._query_update(self.UI, "UI", qkeys[:B], qperm[:B], ugrad, 0, 0)
-        self._query_update(self.LI, "LI", qkeys[B:], qperm[B:], lgrad, n_users, B)
+        # the query side last: the item-side update above read the pre-step UI and LI.  Plain gradient rows, one per occurrence;
+        # each table takes its half of the joint sort, LI's keyed behind the users and numbered behind their occurrences
+        m, v = self._mv("UI")
+        segmented_update(qkeys[:B], qperm[:B], ugrad, hyper=self.hyper, W=self.UI, m=m, v=v)
+        m, v = self._mv("LI")
+        segmented_update(qkeys[B:], qperm[B:], lgrad, hyper=self.hyper, W=self.LI, m=m, v=v, key_base=n_users, occ_base=B)
         return loss
 
 
@@ -3355,9 +3313,7 @@ SLRC_ITEM_TABLES = ("I", "item_bias", "alphas", "pis", "betas", "sigmas", "mus")
 def slrc_check_shape(d, n_cand=1, n_rel=1):
     """rc_slrc_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate, 1..8 relations; raises ValueError
     with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_slrc_check_shape(int(d), int(n_cand), int(n_rel)) != _lib.RC_OK:
-        raise ValueError("SLRCPlus on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("SLRCPlus", "rc_slrc_check_shape", d, n_cand, n_rel)
 
 
 def slrc_fwd_bwd_layout(d, n_cand, n_rel=1):
@@ -3403,9 +3359,7 @@ def slrc_fwd_bwd(P, uid, iid, intervals, inv_b=None, want_pred=True):
     if inv_b is None:
         inv_b = 1.0 / B
     dev, f32 = iid.device, torch.float32
-    pred = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
-    loss_vec = torch.empty(B, dtype=f32, device=dev)
-    gpred = torch.empty((B, Cn), dtype=f32, device=dev)
+    pred, loss_vec, gpred = _step_outputs(B, Cn, dev, want_pred)
     ugrad = torch.empty((B, d), dtype=f32, device=dev)
     ubgrad = torch.empty(B, dtype=f32, device=dev)
     hgrad = torch.empty((B * Cn, 5 * R), dtype=f32, device=dev)
@@ -3429,13 +3383,17 @@ def slrc_excitation_grads(P, uid, iid, intervals, gpred):
     return hgrad, ubgrad, gagrad
 
 
-def _ptr_array7(tensors, name, allow_none=False):
-    """a host array of seven device pointers (SLRC_ITEM_TABLES order), or NULL when `tensors` is None"""
+_NUMBER_WORDS = {3: "three", 7: "seven"}      # the lengths of CHORUS_CAT_TABLES and SLRC_ITEM_TABLES
+
+
+def _ptr_array(tensors, names, what, allow_none=False):
+    """a host array of the device pointers of one float tensor per name (in the order of `names`), or NULL when `tensors` is None"""
     if tensors is None:
         return None
-    if len(tensors) != 7:
-        raise ValueError(f"{name}: seven tensors are needed ({', '.join(SLRC_ITEM_TABLES)})")
-    return (C.c_void_p * 7)(*(_ptr(t, torch.float32, f"{name}[{k}]", allow_none) for t, k in zip(tensors, SLRC_ITEM_TABLES)))
+    n = len(names)
+    if len(tensors) != n:
+        raise ValueError(f"{what}: {_NUMBER_WORDS[n]} tensors are needed ({', '.join(names)})")
+    return (C.c_void_p * n)(*(_ptr(t, torch.float32, f"{what}[{k}]", allow_none) for t, k in zip(tensors, names)))
 
 
 def slrc_item_update(keys, perm, heads, n_heads, gpred, hgrad, U, uid, hyper=None, W=None, m=None, v=None, dense_grad=None):
@@ -3449,9 +3407,10 @@ def slrc_item_update(keys, perm, heads, n_heads, gpred, hgrad, U, uid, hyper=Non
     R = hgrad.shape[-1] // 5
     f32, i32 = torch.float32, torch.int32
     ws = workspace(_lib.load().rc_slrc_item_update_workspace_bytes(n_occ, d), keys.device, "slrc_item")
-    _lib.call("rc_slrc_item_update", _ptr_array7(W, "W"), _ptr_array7(m, "m", True), _ptr_array7(v, "v", True), d, R,
+    T = SLRC_ITEM_TABLES
+    _lib.call("rc_slrc_item_update", _ptr_array(W, T, "W"), _ptr_array(m, T, "m", True), _ptr_array(v, T, "v", True), d, R,
               _ptr(keys, i32, "keys"), _ptr(perm, i32, "perm"), n_occ, _ptr(gpred, f32, "gpred"), _ptr(hgrad, f32, "hgrad"),
-              _ptr(U, f32, "U"), _ptr(uid, torch.int64, "uid"), Cn, _hyper_ref(hyper), _ptr_array7(dense_grad, "dense_grad"),
+              _ptr(U, f32, "U"), _ptr(uid, torch.int64, "uid"), Cn, _hyper_ref(hyper), _ptr_array(dense_grad, T, "dense_grad"),
               _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
 
 
@@ -3464,7 +3423,7 @@ def slrc_user_bias_update(keys, perm, ubgrad, hyper=None, user_bias=None, m=None
               _ptr(dense_grad, f32, "dense_grad", True), _stream())
 
 
-class SlrcTrainer:
+class SlrcTrainer(_RowwiseTrainer):
     """Row-wise-optimizer SLRC+ training on the ten device parameters (SLRC_PARAMS order; models/sequential/SLRCPlus.py:49-60).
 
     One `step(uid, iid, intervals)` = one iteration of BaseRunner.fit's batch loop (helpers/BaseRunner.py:193-206): two sorts + the
@@ -3473,19 +3432,13 @@ class SlrcTrainer:
     BprmfTrainer; the two bias tables take no weight decay, global_alpha (dense, one float) does."""
 
     def __init__(self, *params, opt="SGD", lr=1e-3, l2=0.0, beta1=0.9, beta2=0.999, eps=None):
-        if opt not in ("SGD", "Adam", "Adagrad"):
-            raise ValueError(f"SlrcTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        super().__init__(opt, lr, l2, beta1, beta2, eps)
         if len(params) != len(SLRC_PARAMS):
             raise ValueError("SlrcTrainer: ten parameter tensors are needed: " + ", ".join(SLRC_PARAMS))
         self.P = dict(zip(SLRC_PARAMS, params))
         self.d, self.R = self.P["U"].shape[1], self.P["alphas"].shape[1]
         slrc_check_shape(self.d, 1, self.R)
-        self.opt = opt
-        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
-        self.state = {name: new_opt_state(t, opt) for name, t in self.P.items()}
-
-    def _mv(self, name):
-        return self.state[name].get("m"), self.state[name].get("v")
+        self._new_state()
 
     def step(self, uid, iid, intervals, inv_b=None):
         """one training step; returns the device loss tensor (shape [1], no sync)"""
@@ -3500,16 +3453,11 @@ class SlrcTrainer:
         ukeys, uperm = sort_ids(uid, U.shape[0])
         _, loss_vec, gpred, ugrad, ubgrad, hgrad, gagrad = slrc_fwd_bwd(P, uid, iid, intervals, inv_b, want_pred=False)
         loss = reduce_sum(loss_vec, inv_b)
-        items = [self.P[k] for k in SLRC_ITEM_TABLES]
-        mv = [self._mv(k) for k in SLRC_ITEM_TABLES]
-        slrc_item_update(ikeys, iperm, heads, n_heads, gpred, hgrad, U, uid, hyper=self.hyper, W=items,
-                         m=[x[0] for x in mv] if mv[0][0] is not None else None, v=[x[1] for x in mv] if mv[0][1] is not None else None)
+        W, m, v = self._tables(SLRC_ITEM_TABLES)
+        slrc_item_update(ikeys, iperm, heads, n_heads, gpred, hgrad, U, uid, hyper=self.hyper, W=W, m=m, v=v)
         # the user side last: the item-side update above read the pre-step U
         m, v = self._mv("U")
-        ws = workspace(_lib.load().rc_segmented_workspace_bytes(B, d), U.device, "seg")
-        _lib.call("rc_segmented_update", *_table_args(U, m, v, need_W=True), d, _ptr(ukeys, torch.int32, "keys"),
-                  _ptr(uperm, torch.int32, "perm"), B, *_source_args(None, ugrad, None, 1, None, None, default=B), 0, 0,
-                  _hyper_ref(self.hyper), None, None, None, 0, *_ws_args(ws))
+        segmented_update(ukeys, uperm, ugrad, hyper=self.hyper, W=U, m=m, v=v)
         m, v = self._mv("user_bias")
         slrc_user_bias_update(ukeys, uperm, ubgrad, hyper=self.hyper, user_bias=self.P["user_bias"], m=m, v=v)
         m, v = self._mv("global_alpha")
@@ -3522,9 +3470,7 @@ class SlrcTrainer:
 def cfkg_check_shape(d, n_cand=1, n_rel=1):
     """rc_cfkg_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate, 1..8 relations; raises ValueError
     with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_cfkg_check_shape(int(d), int(n_cand), int(n_rel)) != _lib.RC_OK:
-        raise ValueError("CFKG on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("CFKG", "rc_cfkg_check_shape", d, n_cand, n_rel)
 
 
 def cfkg_fwd_bwd_rows_per_block(d):
@@ -3591,7 +3537,7 @@ def cfkg_fwd_bwd(E, R, h, t, hn, tn, r, margin=0.0, inv_b=None, want_pred=True):
     return pred, loss_vec, grows, GR
 
 
-class CfkgTrainer:
+class CfkgTrainer(_RowwiseTrainer):
     """CFKG training on the device tables E [n_users + n_entities, d] and R [n_relations, d] (e_embeddings, r_embeddings of
     models/general/CFKG.py:50-55).
 
@@ -3604,17 +3550,12 @@ class CfkgTrainer:
     (weight decay and Adam's moment decay on every row, every step)."""
 
     def __init__(self, E, R, margin=0.0, opt="SGD", lr=1e-3, l2=0.0, beta1=0.9, beta2=0.999, eps=None):
-        if opt not in ("SGD", "Adam", "Adagrad"):
-            raise ValueError(f"CfkgTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        super().__init__(opt, lr, l2, beta1, beta2, eps)
         self.E, self.R, self.margin = E, R, float(margin)
+        self.P = {"E": E, "R": R}
         self.d = E.shape[1]
         cfkg_check_shape(self.d, 4, R.shape[0])
-        self.opt = opt
-        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
-        self.state = {name: new_opt_state(t, opt) for name, t in (("E", E), ("R", R))}
-
-    def _mv(self, name):
-        return self.state[name].get("m"), self.state[name].get("v")
+        self._new_state()
 
     def step(self, head, tail, rel, inv_b=None):
         """one training step on head_id / tail_id / relation_id [B, 4]; returns the device loss tensor (shape [1], no sync)"""
@@ -3653,10 +3594,8 @@ def _din_widths(widths):
 def din_check_shape(H, L, widths, drop_p=0.0):
     """rc_din_check_shape (host logic), the one statement of the envelope: H a multiple of 4 in [4, 512], 1 <= L <= 64, 1 to 3 hidden
     widths, each a multiple of 16 in [16, 256] and at most 256 in all, 0 <= drop_p < 1; raises ValueError with the library's reason"""
-    lib = _lib.load()
     n, arr = _din_widths(widths)
-    if lib.rc_din_check_shape(int(H), int(L), n, arr, C.c_float(float(drop_p))) != _lib.RC_OK:
-        raise ValueError("DIN attention on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("DIN attention", "rc_din_check_shape", H, L, n, extra=(arr, C.c_float(float(drop_p))))
 
 
 def din_param_count(H, widths):
@@ -3715,9 +3654,7 @@ def din_attention_bwd(q, keys, lengths, params, d_out, n_cand, widths, drop_p=0.
 def kda_check_shape(V, L, R, F):
     """rc_kda_check_shape (host logic), the one statement of the envelope: V in {16, 32, 64, 128}, 1 <= L <= 64, 1 <= R <= 8,
     2 <= F <= 129; raises ValueError with the library's reason"""
-    lib = _lib.load()
-    if lib.rc_kda_check_shape(int(V), int(L), int(R), int(F)) != _lib.RC_OK:
-        raise ValueError("KDA aggregation on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("KDA aggregation", "rc_kda_check_shape", V, L, R, F)
 
 
 def _kda_shapes(seq, hist, delta_t, target, value, rel, freq_real, freq_imag, include_val):
@@ -3799,9 +3736,7 @@ def chorus_kinds(item_relations):
 def chorus_check_shape(d, n_cand=1, n_rel=1):
     """rc_chorus_check_shape (host logic): emb_size in {16, 32, 64, 128}, at least one candidate, 1..8 relations; raises ValueError
     with the library's reason otherwise"""
-    lib = _lib.load()
-    if lib.rc_chorus_check_shape(int(d), int(n_cand), int(n_rel)) != _lib.RC_OK:
-        raise ValueError("Chorus on the HIP engine: " + lib.rc_last_error_string().decode())
+    _check_shape("Chorus", "rc_chorus_check_shape", d, n_cand, n_rel)
 
 
 def chorus_front_tuples_per_block():
@@ -3885,9 +3820,7 @@ def chorus_fwd_bwd(P, uid, iid, cid, intervals, kinds, gmf=False, inv_b=None, wa
         inv_b = 1.0 / B
     dev, f32 = iid.device, torch.float32
     out, out_args = _chorus_front_outputs(B, Cn, d, R, gmf, dev)
-    out["pred"] = torch.empty((B, Cn), dtype=f32, device=dev) if want_pred else None
-    out["loss_vec"] = torch.empty(B, dtype=f32, device=dev)
-    out["gpred"] = torch.empty((B, Cn), dtype=f32, device=dev)
+    out["pred"], out["loss_vec"], out["gpred"] = _step_outputs(B, Cn, dev, want_pred)
     ws = workspace(_lib.load().rc_chorus_front_workspace_bytes(B, d, R), dev, "chorus_front")
     _lib.call("rc_chorus_fwd_bwd", *_chorus_tables(P, gmf), *_chorus_ids(uid, iid, cid, intervals, kinds), B, Cn, d, R, float(inv_b),
               _ptr(out["pred"], f32, "pred", True), _ptr(out["loss_vec"], f32, "loss_vec"), _ptr(out["gpred"], f32, "gpred"), *out_args,
@@ -3909,15 +3842,6 @@ def chorus_scores_grads(P, uid, iid, cid, intervals, kinds, gpred, gmf=False):
     return out
 
 
-def _ptr_array3(tensors, name, allow_none=False):
-    """a host array of three device pointers (CHORUS_CAT_TABLES order), or NULL when `tensors` is None"""
-    if tensors is None:
-        return None
-    if len(tensors) != 3:
-        raise ValueError(f"{name}: three tensors are needed ({', '.join(CHORUS_CAT_TABLES)})")
-    return (C.c_void_p * 3)(*(_ptr(t, torch.float32, f"{name}[{k}]", allow_none) for t, k in zip(tensors, CHORUS_CAT_TABLES)))
-
-
 def chorus_category_update(keys, perm, heads, n_heads, kgrad, n_cat, hyper=None, W=None, m=None, v=None, dense_grad=None,
                            workspace_buf=None):
     """rc_chorus_category_update: one pass over the sorted category ids (keys / perm of sort_ids(cid), heads / n_heads of
@@ -3933,12 +3857,13 @@ def chorus_category_update(keys, perm, heads, n_heads, kgrad, n_cat, hyper=None,
     f32, i32 = torch.float32, torch.int32
     need = _lib.load().rc_chorus_category_update_workspace_bytes(n_occ, int(n_cat), R)
     ws = workspace_buf if workspace_buf is not None else workspace(need, keys.device, "chorus_cat")
-    _lib.call("rc_chorus_category_update", _ptr_array3(W, "W", True), _ptr_array3(m, "m", True), _ptr_array3(v, "v", True), int(n_cat), R,
+    T = CHORUS_CAT_TABLES
+    _lib.call("rc_chorus_category_update", _ptr_array(W, T, "W", True), _ptr_array(m, T, "m", True), _ptr_array(v, T, "v", True), int(n_cat), R,
               _ptr(keys, i32, "keys"), _ptr(perm, i32, "perm"), n_occ, _ptr(kgrad, f32, "kgrad"), _hyper_ref(hyper),
-              _ptr_array3(dense_grad, "dense_grad", True), _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
+              _ptr_array(dense_grad, T, "dense_grad", True), _ptr(heads, i32, "heads"), _ptr(n_heads, i32, "n_heads"), *_ws_args(ws))
 
 
-class ChorusTrainer:
+class ChorusTrainer(_RowwiseTrainer):
     """Row-wise-optimizer training of Chorus's stage 2 on the nine device parameters (CHORUS_PARAMS order; Chorus.py:79-88).
 
     One `step(uid, iid, cid, intervals)` = one iteration of BaseRunner.fit's batch loop (helpers/BaseRunner.py:193-206): three sorts
@@ -3952,21 +3877,16 @@ class ChorusTrainer:
     gradient and is left alone, as torch.optim does."""
 
     def __init__(self, *params, kinds, gmf=False, opt="SGD", lr=1e-3, l2=0.0, lr_scale=0.1, beta1=0.9, beta2=0.999, eps=None):
-        if opt not in ("SGD", "Adam", "Adagrad"):
-            raise ValueError(f"ChorusTrainer: the row-wise step covers SGD, Adam and Adagrad, not {opt!r}")
+        super().__init__(opt, lr, l2, beta1, beta2, eps)
         if len(params) != len(CHORUS_PARAMS):
             raise ValueError("ChorusTrainer: nine parameter tensors are needed: " + ", ".join(CHORUS_PARAMS))
         self.P = dict(zip(CHORUS_PARAMS, params))
         self.d, self.R, self.n_cat = self.P["U"].shape[1], self.P["Rel"].shape[0], self.P["betas"].shape[0]
         chorus_check_shape(self.d, 1, self.R)
-        self.kinds, self.gmf, self.opt = [int(k) for k in kinds], bool(gmf), opt
-        self.hyper = make_hyper(opt, lr, l2, beta1, beta2, eps, step=0)
+        self.kinds, self.gmf = [int(k) for k in kinds], bool(gmf)
         self.hyper_kg = make_hyper(opt, lr_scale * lr, l2, beta1, beta2, eps, step=0)
         self.hyper_bias = make_hyper(opt, lr, 0.0, beta1, beta2, eps, step=0)
-        self.state = {name: new_opt_state(t, opt) for name, t in self.P.items()}
-
-    def _mv(self, name):
-        return self.state[name].get("m"), self.state[name].get("v")
+        self._new_state()
 
     def step(self, uid, iid, cid, intervals, inv_b=None):
         """one training step; returns the device loss tensor (shape [1], no sync)"""
@@ -3990,13 +3910,11 @@ class ChorusTrainer:
             segmented_update(ikeys, iperm, U, hyper=self.hyper_kg, W=I, m=m, v=v, coef=out["coef"], src_index=uid, div=Cn)
             m, v = self._mv("item_bias")
             slrc_user_bias_update(ikeys, iperm, out["gpred"], hyper=self.hyper_bias, user_bias=self.P["item_bias"], m=m, v=v)
-        mv = [self._mv(k) for k in CHORUS_CAT_TABLES]
+        W, m, v = self._tables(CHORUS_CAT_TABLES)
         # sigmas and mus are read by the 'substitute' kernel alone: without one they have no gradient and stay as they are
         live = [True, 2 in self.kinds, 2 in self.kinds]
         chorus_category_update(ckeys, cperm, heads, n_heads, out["kgrad"], self.n_cat, hyper=self.hyper,
-                               W=[self.P[k] if on else None for k, on in zip(CHORUS_CAT_TABLES, live)],
-                               m=[x[0] for x in mv] if mv[0][0] is not None else None,
-                               v=[x[1] for x in mv] if mv[0][1] is not None else None)
+                               W=[t if on else None for t, on in zip(W, live)], m=m, v=v)
         m, v = self._mv("Rel")
         dense_update(self.P["Rel"], out["GRel"], self.hyper_kg, m=m, v=v)
         if self.gmf:
