@@ -288,14 +288,15 @@ __device__ __forceinline__ void fused_finish(
     if (MODE == MODE_ADAM || MODE == MODE_ADAGRAD) gs[j] = g;  // row updates below
   }
   if (MODE == MODE_SGD) {
-    // single-occurrence rows: all write-backs of the wave in one burst after the accumulation
+    // single-occurrence rows: all write-backs of the wave in one burst after the accumulation; a row the update left
+    // bit-identical (r[j] is the row as it was read) is not written (opt_math.hpp, store_row4_changed)
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
       if (smask & (1u << j)) {  // whole lane-group takes the branch together
         const int64_t id = ids[j * GS + grp];
         const float g = strip[grp * CPL + j];
         const float4 gi = make_float4(g * u4.x, g * u4.y, g * u4.z, g * u4.w);
-        opt_row4<MODE>(upd.o, upd.I, upd.M, upd.V, (size_t)id * LPR + l, r[j], gi);
+        opt_row4_group<MODE, LPR>(upd.o, upd.I, upd.M, upd.V, (size_t)id * LPR + l, r[j], gi);
       }
     }
   }

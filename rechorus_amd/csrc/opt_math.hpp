@@ -100,6 +100,41 @@ __device__ __forceinline__ void store_row4(float4* p, const float4& x) {
   __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(p));
 }
 
+// Stateless SGD often returns the bits it was given: at a large batch lr * g is far below half an ulp of the weight, and
+// w = fmaf(-lr, g, w) rounds back to w in every element of the row.  Storing such a row moves bytes
+// the result does not need, so the SGD write-back of a row that an aligned group of LPR lanes holds (a float4 each) stores
+// it only if some lane's slice changed.  The comparison is on the bit patterns (-0.0 vs 0.0, NaN payloads and denormals
+// count as they are), and the store is the whole row or nothing: a partly written line costs more per byte than a row.
+// The vote is a wave ballot restricted to the group's own lanes, so it may stand in a divergent branch that whole
+// lane-groups take together: lanes outside the branch contribute no bits, lanes of other groups are masked off.
+// (1-D workgroups of whole waves, like every kernel of this library.)
+template <int LPR>
+__device__ __forceinline__ bool row_group_any(bool pred) {
+  static_assert(LPR >= 1 && LPR <= 64 && 64 % LPR == 0, "a row's lane-group must be an aligned part of a wave");
+  const uint64_t b = (uint64_t)__ballot(pred);
+  if (LPR == 64) return b != 0ull;
+  const unsigned first = (threadIdx.x & 63u) & ~(unsigned)(LPR - 1);   // the group's first lane
+  const uint32_t half = (first & 32u) ? (uint32_t)(b >> 32) : (uint32_t)b;
+  if (LPR == 32) return half != 0u;
+  return ((half >> (first & 31u)) & ((1u << (LPR & 31)) - 1u)) != 0u;
+}
+
+__device__ __forceinline__ bool bits_differ4(const float4& a, const float4& b) {
+  return (__float_as_uint(a.x) != __float_as_uint(b.x)) | (__float_as_uint(a.y) != __float_as_uint(b.y)) |
+         (__float_as_uint(a.z) != __float_as_uint(b.z)) | (__float_as_uint(a.w) != __float_as_uint(b.w));
+}
+
+// write-back of a row's new W slice (w0: the slice as it was read).  SGD: only if the row changed; every other mode stores
+// unconditionally (their state rows change with every step, and MODE_DENSE_GRAD's old row is not the row's history)
+template <int MODE, int LPR>
+__device__ __forceinline__ void store_row4_changed(float4* p, const float4& w, const float4& w0) {
+  if (MODE == MODE_SGD) {
+    if (row_group_any<LPR>(bits_differ4(w, w0))) store_row4(p, w);
+  } else {
+    store_row4(p, w);
+  }
+}
+
 // the optimizer on one float4 slice held in registers (state already loaded)
 template <int MODE>
 __device__ __forceinline__ void opt_apply4(const OptScalars& a, float4& w, float4& m, float4& v, const float4& g) {
@@ -121,6 +156,21 @@ __device__ __forceinline__ void opt_row4(const OptScalars& a, float* __restrict_
   store_row4(reinterpret_cast<float4*>(W) + idx4, w);
   if (mode_has_m(MODE)) store_row4(reinterpret_cast<float4*>(M) + idx4, m);
   if (mode_has_v(MODE)) store_row4(reinterpret_cast<float4*>(V) + idx4, v);
+}
+
+// opt_row4 where the whole row is held by an aligned group of LPR lanes that run this call together (slice idx4 of each
+// lane belongs to the same row; pair mode: to the same row of two tables): SGD leaves an unchanged row unwritten
+template <int MODE, int LPR>
+__device__ __forceinline__ void opt_row4_group(const OptScalars& a, float* __restrict__ W, float* __restrict__ M,
+                                               float* __restrict__ V, size_t idx4, float4 w, const float4& g) {
+  if (MODE == MODE_SGD) {
+    const float4 w0 = w;
+    float4 m = make_float4(0, 0, 0, 0), v = make_float4(0, 0, 0, 0);
+    opt_apply4<MODE>(a, w, m, v, g);
+    store_row4_changed<MODE, LPR>(reinterpret_cast<float4*>(W) + idx4, w, w0);
+  } else {
+    opt_row4<MODE>(a, W, M, V, idx4, w, g);
+  }
 }
 #endif
 

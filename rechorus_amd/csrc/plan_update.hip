@@ -169,7 +169,8 @@ __device__ __forceinline__ void plan_rows_body(const PlanUpdArgs& a, int side, b
       if (e[h].n > 1) padd4(acc[h], s1[h]);
       if (!MED)
         for (uint32_t k = kPlanBodyOcc; k < e[h].n; ++k) padd4(acc[h], plan_grad4<D>(sd.g, a.occ, e[h].start + k, l));
-      opt_row4<MODE>(a.o, tab[h].W, tab[h].M, tab[h].V, idx4[h], w[h], acc[h]);
+      // (pair mode: the vote runs over both tables' halves of the lane-group; an unchanged half is stored with a changed one)
+      opt_row4_group<MODE, LPR>(a.o, tab[h].W, tab[h].M, tab[h].V, idx4[h], w[h], acc[h]);
     }
   }
 }
@@ -302,8 +303,9 @@ __device__ __forceinline__ void plan_rows_indexed_body(const PlanUpdArgs& a, int
         //  where the plan lists the medium rows, MED, they are plan_medium_body's and this loop does not exist)
         if (!MED)
           for (uint32_t k = kIdxOcc; k < eh[h].n; ++k) padd4(acc, plan_grad4<D>(gr, a.occ, eh[h].start + k, l));
+        const float4 w0 = w[h];
         opt_apply4<MODE>(a.o, w[h], m[h], v[h], acc);
-        store_row4(reinterpret_cast<float4*>(sd.t.W) + idx4[h], w[h]);
+        store_row4_changed<MODE, LPR>(reinterpret_cast<float4*>(sd.t.W) + idx4[h], w[h], w0);   // SGD: only a row that changed
         if (mode_has_m(MODE)) store_row4(reinterpret_cast<float4*>(sd.t.M) + idx4[h], m[h]);
         if (mode_has_v(MODE)) store_row4(reinterpret_cast<float4*>(sd.t.V) + idx4[h], v[h]);
       }
@@ -400,7 +402,7 @@ __device__ __forceinline__ void plan_medium_body(const PlanUpdArgs& a, int side,
         else padd4(acc, t);
       }
     }
-    opt_row4<MODE>(a.o, sd.t.W, sd.t.M, sd.t.V, idx4, w, acc);
+    opt_row4_group<MODE, LPR>(a.o, sd.t.W, sd.t.M, sd.t.V, idx4, w, acc);
   }
 }
 
@@ -430,8 +432,14 @@ __device__ __forceinline__ void plan_chunk_body(const PlanUpdArgs& a, uint32_t f
 
 // MED (the BPRMF step: medium and hot rows listed by the plan, an indexed update side): a.blocks_med workgroups of medium
 // rows, then the hot rows' chunk workgroups, then the short rows
+// waves per SIMD the register allocation must allow.  The BPRMF step's SGD item update ran at five (96 VGPRs); the old
+// row kept beside the new one for the changed-row vote took it to 98 and four without this bound.  (d = 128 holds the
+// bound only with 8 bytes of scratch, so it is left at 98 registers and four waves; d = 16 had 98 and four before.)
+template <int D, int MODE, bool MED>
+constexpr int plan_rows_min_waves() { return (MED && MODE == MODE_SGD && (D == 32 || D == 64)) ? 5 : 1; }
+
 template <int D, int MODE, bool MED = false>
-__global__ __launch_bounds__(kBlock) void plan_rows_kernel(PlanUpdArgs a, uint32_t blocks_main, int update_side,
+__global__ __launch_bounds__(kBlock, (plan_rows_min_waves<D, MODE, MED>())) void plan_rows_kernel(PlanUpdArgs a, uint32_t blocks_main, int update_side,
                                                            int plan_other, uint32_t blocks_chunk) {
   __shared__ float4 part[kBlock];   // chunk workgroups only
   if constexpr (MED) {
@@ -543,7 +551,7 @@ __global__ __launch_bounds__(kBlock) void plan_final_kernel(PlanUpdArgs a, uint3
       if (g == 0) {
         size_t idx;
         const PlanTable t = plan_lane_table<D>(a.side[r.side], r.row, l, idx);
-        opt_row4<MODE>(a.o, t.W, t.M, t.V, idx, load_stream4(reinterpret_cast<const float4*>(t.W) + idx), part[threadIdx.x]);
+        opt_row4_group<MODE, LPR>(a.o, t.W, t.M, t.V, idx, load_stream4(reinterpret_cast<const float4*>(t.W) + idx), part[threadIdx.x]);
       }
       __syncthreads();
     }
