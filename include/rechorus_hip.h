@@ -1553,6 +1553,45 @@ enum rc_status rc_listenc_block_bwd(const float* dY, const float* X, const uint8
                                     float* dbin, float* dWo, float* dbo, float* dg1, float* dbe1, float* dW1, float* db1, float* dW2,
                                     float* db2, float* dg2, float* dbe2, rc_stream_t stream);
 
+/* ---- set attention: one post-norm multihead attention block whose query rows are not its key rows (csrc/setmab.hip; reference
+ * models/reranker/SetRank.py:29-56 `MAB`; two of them are one induced block, :67-80 `IMSAB`: h = MAB1(I, x, x; pad), x' = MAB2(x, h, h))
+ * Ks [B, nk, d] list-major; Qs [B, nq, d], or with shared_q != 0 ONE [nq, d] source for every list (the learned inducing points, which
+ * are every list's residual input as well); pad uint8 [B, nk], 1 = padded key, or NULL: no key is masked.
+ *   q = Qs Wq^T + bq, k = Ks Wk^T + bk, v = Ks Wv^T + bv (Win [3d, d] = Wq | Wk | Wv, bin [3d], as nn.MultiheadAttention packs them),
+ *   P_h = softmax_j(q_h . k_h / sqrt(d / heads)) over the keys j < nk with pad == 0,
+ *   A = concat_h(P_h V_h) Wo^T + bo,  X1 = LN1(Qs + A),  Y = LN2(X1 + relu(X1 W1^T + b1) W2^T + b2)       (LayerNorm eps 1e-5)
+ * Y [B, nq, d]; the weights are rc_listenc_block_fwd's.  Every list must have at least one valid key.  All fp32, every float tensor
+ * 16-byte aligned.  All products run on the f32-input MFMA; no float atomics, reruns are bitwise identical.
+ * RC_OK when 1 <= nq <= 64, 1 <= nk <= 64, d, heads and d_ff as rc_listenc_check_shape has them (d % 16 == 0, 16 <= d <= 128, heads
+ * divides d with (d / heads) % 4 == 0, d_ff % 16 == 0, 16 <= d_ff <= 256) AND both row sets with the backward's intermediates fit the
+ * 160 KB LDS (with NQP, NKP = nq, nk rounded up to 16:
+ * 4 (3 NQP (d + 4) + NKP (d + 4) + max(NQP (d + 4) + 2 NKP (2 d + 4), NQP (2 d + d_ff + 12)) + 64 (NKP + 4) + NKP + NQP) bytes: at
+ * d = 64, d_ff = 128 every (nq, nk) with nq, nk <= 64 but the one tile pair nq > 48 AND nk > 48, so (20, n) and (n, 20) hold for every
+ * n <= 64; at d = 128, d_ff = 256 nq, nk <= 32), else RC_ERR_UNSUPPORTED with the reason in rc_last_error_string() (host logic, no GPU
+ * needed); the entry points below check the same envelope themselves, and 1 <= B <= 2^24.                                           */
+enum rc_status rc_setmab_check_shape(int nq, int nk, int d, int heads, int d_ff);
+/* one block (SetRank.py:29-56; :72 and :76 with the two argument orders) in ONE launch: a workgroup holds a list's query-side and
+ * key-side rows and every intermediate in LDS.  With shared_q the workgroup projects q once, before the first list it walks.  Y is
+ * written once, nothing is kept for the backward pass.                                                                              */
+enum rc_status rc_setmab_fwd(const float* Qs, const float* Ks, const uint8_t* pad, const float* Win, const float* bin, const float* Wo,
+                             const float* bo, const float* g1, const float* be1, const float* W1, const float* b1, const float* W2,
+                             const float* b2, const float* g2, const float* be2, int64_t B, int nq, int nk, int d, int heads, int d_ff,
+                             int shared_q, float* Y, rc_stream_t stream);
+/* bytes of the caller workspace (256-byte aligned) of rc_setmab_bwd: one partial of every weight and bias gradient and of a shared
+ * dQs per workgroup, at most min(256, 128 MB / bytes of one partial) of them, so the size does not grow with B past 256 lists and does
+ * not depend on shared_q; 0 outside the envelope                                                                                    */
+size_t rc_setmab_bwd_workspace_bytes(int64_t B, int nq, int nk, int d, int heads, int d_ff);
+/* autograd of the block (SetRank.py:29-56) from dY [B, nq, d]: the block is recomputed from Qs and Ks.  dKs [B, nk, d] and dQs
+ * [B, nq, d] are written once; with shared_q dQs is [nq, d], the sum over all lists (SetRank.py:69's parameter I), and goes through the
+ * same per-workgroup partials and fixed-order reduce as the twelve weight and bias gradients.  Masked keys' rows of dKs are what the
+ * projections' backward leaves of zero dK, dV: exact zeros.  Two launches (three with shared_q): the list kernel and the reduces.   */
+enum rc_status rc_setmab_bwd(const float* dY, const float* Qs, const float* Ks, const uint8_t* pad, const float* Win, const float* bin,
+                             const float* Wo, const float* bo, const float* g1, const float* be1, const float* W1, const float* b1,
+                             const float* W2, const float* b2, const float* g2, const float* be2, int64_t B, int nq, int nk, int d,
+                             int heads, int d_ff, int shared_q, void* workspace, size_t ws_bytes, float* dQs, float* dKs, float* dWin,
+                             float* dbin, float* dWo, float* dbo, float* dg1, float* dbe1, float* dW1, float* db1, float* dW2,
+                             float* db2, float* dg2, float* dbe2, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

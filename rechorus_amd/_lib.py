@@ -312,6 +312,10 @@ SIGNATURES = {
     "rc_listenc_block_fwd": (_i, [_p] * 14 + [_i64, _i, _i, _i, _i, _p, _p]),
     "rc_listenc_block_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "rc_listenc_block_bwd": (_i, [_p] * 15 + [_i64, _i, _i, _i, _i, _p, _sz] + [_p] * 13 + [_p]),
+    "rc_setmab_check_shape": (_i, [_i, _i, _i, _i, _i]),
+    "rc_setmab_fwd": (_i, [_p] * 15 + [_i64, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "rc_setmab_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
+    "rc_setmab_bwd": (_i, [_p] * 16 + [_i64, _i, _i, _i, _i, _i, _i, _p, _sz] + [_p] * 14 + [_p]),
 }
 
 _lib = None

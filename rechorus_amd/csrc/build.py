@@ -53,6 +53,7 @@ SOURCES = [
     "chorus.hip",
     "dcnv2.hip",
     "listenc.hip",
+    "setmab.hip",
     "bench_mix.hip",
 ]
 # every header of this directory is a dependency of every object (a hand-kept list went stale once: sas_attn_reg.hpp /

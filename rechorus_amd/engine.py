@@ -3027,6 +3027,76 @@ def listenc_block_bwd(dY, X, pad, weights, heads, workspace=None):
     return dX, grads
 
 
+# ---- set attention block (models/reranker/SetRank.py:29-56 `MAB`: query rows that are not the key rows) -----------------------------
+
+def setmab_check_shape(nq, nk, d, heads, d_ff):
+    """rc_setmab_check_shape (host logic): 1 <= nq, nk <= 64, d, heads and d_ff as listenc_check_shape has them, and both row sets
+    with the backward's intermediates within the LDS; raises ValueError with the library's reason otherwise"""
+    _check_shape("set attention block", "rc_setmab_check_shape", nq, nk, d, heads, d_ff)
+
+
+class SetMabWorkspace(_ShapeWorkspace):
+    """the scratch of rc_setmab_bwd (the per-workgroup partials of the weight gradients and of a shared query source's gradient), one
+    buffer per shape that is never freed or moved while the owner lives: a captured training step replays on the same memory.
+    Nothing in it outlives the call that wrote it, so both blocks of every induced block of a stack share one workspace."""
+    _query, _shape, _floor = "rc_setmab_bwd_workspace_bytes", ("B", "nq", "nk", "d", "heads", "d_ff"), 256
+
+
+def _setmab_shapes(Qs, Ks, pad, weights, heads, shared_q):
+    if Ks.dim() != 3 or Ks.numel() == 0:
+        raise ValueError(f"set_attention_block: Ks must be [lists, key rows, width] with at least one list, got {tuple(Ks.shape)}")
+    B, nk, d = Ks.shape
+    if Qs.dim() != (2 if shared_q else 3) or Qs.numel() == 0 or Qs.shape[-1] != d or (not shared_q and Qs.shape[0] != B):
+        raise ValueError(f"set_attention_block: Qs must be {'[query rows, ' if shared_q else f'[{B}, query rows, '}{d}], "
+                         f"got {tuple(Qs.shape)} (shared_q={bool(shared_q)})")
+    nq = Qs.shape[-2]
+    if pad is not None and tuple(pad.shape) != (B, nk):
+        raise ValueError(f"set_attention_block: pad must be [{B}, {nk}] or None, got {tuple(pad.shape)}")
+    if len(weights) != len(LISTENC_WEIGHTS):
+        raise ValueError(f"set_attention_block: twelve weights are needed ({', '.join(LISTENC_WEIGHTS)})")
+    W1 = weights[6]
+    if W1.dim() != 2 or W1.shape[1] != d:
+        raise ValueError(f"set_attention_block: W1 must be [d_ff, {d}], got {tuple(W1.shape)}")
+    dff = W1.shape[0]
+    setmab_check_shape(nq, nk, d, heads, dff)
+    shapes = ((3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,), (dff, d), (dff,), (d, dff), (d,), (d,), (d,))
+    for name, W, shape in zip(LISTENC_WEIGHTS, weights, shapes):
+        if tuple(W.shape) != shape:
+            raise ValueError(f"set_attention_block: {name} must be {list(shape)}, got {tuple(W.shape)}")
+    return B, nq, nk, d, dff
+
+
+def setmab_fwd(Qs, Ks, pad, weights, heads, shared_q=False):
+    """rc_setmab_fwd: Y [B, nq, d] = LN2(X1 + relu(X1 W1^T + b1) W2^T + b2), X1 = LN1(Qs + MHA(Qs, Ks, Ks; pad)), one launch.
+    Qs [B, nq, d], or [nq, d] with shared_q (one query source for every list); pad uint8 [B, nk], 1 = padded key, or None;
+    weights in LISTENC_WEIGHTS order"""
+    B, nq, nk, d, dff = _setmab_shapes(Qs, Ks, pad, weights, heads, shared_q)
+    f32 = torch.float32
+    Y = torch.empty((B, nq, d), dtype=f32, device=Ks.device)
+    _lib.call("rc_setmab_fwd", _ptr(Qs, f32, "Qs"), _ptr(Ks, f32, "Ks"), _ptr(pad, torch.uint8, "pad", allow_none=True),
+              *[_ptr(W, f32, k) for k, W in zip(LISTENC_WEIGHTS, weights)], B, nq, nk, d, int(heads), dff, int(bool(shared_q)),
+              _ptr(Y, f32, "Y"), _stream())
+    return Y
+
+
+def setmab_bwd(dY, Qs, Ks, pad, weights, heads, shared_q=False, workspace=None):
+    """rc_setmab_bwd -> (dQs, dKs, [the twelve gradients in LISTENC_WEIGHTS order]): the block is recomputed from Qs and Ks; dQs has
+    Qs's shape (with shared_q: the sum over all lists); two launches, three with shared_q"""
+    B, nq, nk, d, dff = _setmab_shapes(Qs, Ks, pad, weights, heads, shared_q)
+    if tuple(dY.shape) != (B, nq, d):
+        raise ValueError(f"setmab_bwd: dY must be {(B, nq, d)}, got {tuple(dY.shape)}")
+    dev, f32 = Ks.device, torch.float32
+    ws = (workspace if workspace is not None else SetMabWorkspace()).get(B, nq, nk, d, heads, dff, dev)
+    dQs = torch.empty(Qs.shape, dtype=f32, device=dev)
+    dKs = torch.empty(Ks.shape, dtype=f32, device=dev)
+    grads = [torch.empty(tuple(W.shape), dtype=f32, device=dev) for W in weights]
+    _lib.call("rc_setmab_bwd", _ptr(dY, f32, "dY"), _ptr(Qs, f32, "Qs"), _ptr(Ks, f32, "Ks"), _ptr(pad, torch.uint8, "pad", allow_none=True),
+              *[_ptr(W, f32, k) for k, W in zip(LISTENC_WEIGHTS, weights)], B, nq, nk, d, int(heads), dff, int(bool(shared_q)),
+              C.c_void_p(ws.data_ptr()), ws.numel(), _ptr(dQs, f32, "dQs"), _ptr(dKs, f32, "dKs"),
+              *[_ptr(G, f32, "d" + k) for k, G in zip(LISTENC_WEIGHTS, grads)], _stream())
+    return dQs, dKs, grads
+
+
 # ---- FinalMLP: feature gates + first stream layers, bilinear fusion (models/context/FinalMLP.py:141-249) -------------------------------
 
 def finalmlp_check_shape(n_fields, emb_size, gate_in_1, first_1, gate_in_2, first_2, x_dim, y_dim, num_heads, drop_p_1=0.0, drop_p_2=0.0):

@@ -578,6 +578,60 @@ def list_encoder_block_eval(X, pad, weights, heads):
                                     [t.detach().contiguous() for t in weights], int(heads))
 
 
+class _SetAttentionBlockFn(torch.autograd.Function):
+    """One multihead attention block whose query rows are not its key rows (models/reranker/SetRank.py:29-56) on rc_setmab_fwd / _bwd.
+    Saves Qs, Ks, the mask and the weights only: the backward recomputes the block.  No host synchronisation and no data-dependent
+    allocation: capture-safe."""
+
+    @staticmethod
+    def forward(ctx, Qs, Ks, pad, heads, workspace, shared_q, *weights):
+        det = [t.detach().contiguous() for t in (Qs, Ks, *weights)]
+        pad = None if pad is None else pad.detach().to(torch.uint8).contiguous()
+        Y = engine.setmab_fwd(det[0], det[1], pad, det[2:], heads, shared_q)
+        ctx.save_for_backward(pad, *det)
+        ctx.heads, ctx.workspace, ctx.shared_q = heads, workspace, shared_q
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        pad, Qs, Ks, *weights = ctx.saved_tensors
+        dQs, dKs, grads = engine.setmab_bwd(dY.contiguous(), Qs, Ks, pad, weights, ctx.heads, ctx.shared_q, workspace=ctx.workspace)
+        return (dQs, dKs, None, None, None, None, *grads)
+
+
+def set_attention_block(Qs, Ks, pad, weights, heads, workspace=None, shared_q=False):
+    """SetRank's MAB (models/reranker/SetRank.py:29-56): LN2(X1 + rFF(X1)), X1 = LN1(Qs + MultiheadAttention(Qs, Ks, Ks)) under the
+    key-padding mask pad [B, nk] (true / 1 = padded key; None: no key is masked) -> [B, nq, d], as ONE autograd node (one forward
+    launch; the backward is one launch plus the fixed-order reduces).  Ks [B, nk, d]; Qs [B, nq, d], or with shared_q ONE [nq, d]
+    source for every list, whose gradient is the sum over the lists.  weights as list_encoder_block takes them
+    (engine.LISTENC_WEIGHTS order).  workspace: the model's engine.SetMabWorkspace, reused step after step"""
+    return _SetAttentionBlockFn.apply(Qs, Ks, pad, int(heads), workspace, bool(shared_q), *weights)
+
+
+def set_attention_block_eval(Qs, Ks, pad, weights, heads, shared_q=False):
+    """the same block on the evaluation path: forward only, raises when autograd is recording"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (Qs, Ks, *weights)):
+        raise RuntimeError("set_attention_block_eval is the evaluation path and has no backward: call it under torch.no_grad() "
+                           "(training goes through set_attention_block)")
+    return engine.setmab_fwd(Qs.detach().contiguous(), Ks.detach().contiguous(),
+                             None if pad is None else pad.detach().to(torch.uint8).contiguous(),
+                             [t.detach().contiguous() for t in weights], int(heads), bool(shared_q))
+
+
+def induced_set_block(x, pad, I, w1, w2, heads, workspace=None):
+    """SetRank's IMSAB (models/reranker/SetRank.py:67-80): h = MAB1(I, x, x) under the key-padding mask, x' = MAB2(x, h, h) without
+    one.  x [B, n, d], pad [B, n], I [m, d] the learned inducing points shared by every list, w1 / w2 the two blocks' twelve weights ->
+    [B, n, d].  Two set_attention_block nodes: h [B, m, d] passes between them as an ordinary tensor and autograd adds x's two
+    gradients (MAB1's keys, MAB2's queries)."""
+    h = set_attention_block(I, x, pad, w1, heads, workspace, shared_q=True)
+    return set_attention_block(x, h, None, w2, heads, workspace)
+
+
+def induced_set_block_eval(x, pad, I, w1, w2, heads):
+    """the same induced block on the evaluation path: forward only"""
+    return set_attention_block_eval(x, set_attention_block_eval(I, x, pad, w1, heads, shared_q=True), None, w2, heads)
+
+
 class _FinalMlpGateFn(torch.autograd.Function):
     """FinalMLP's feature gates and the first layer of both streams (models/context/FinalMLP.py:188-221, :100-101) on
     rc_finalmlp_gate_fwd / _bwd.  Saves X, the gate inputs, the weights and A_1, A_2 (their own ReLU / dropout masks): the gates are

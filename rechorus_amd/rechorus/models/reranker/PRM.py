@@ -12,7 +12,7 @@ plus a fixed-order reduce backward (rc_listenc_block_bwd), all products on the f
 Refused at construction, nothing rerouted: --dropout > 0, --tuneranker 1, evaluation list widths that differ from the training
 widths, a base ranker that returns no u_v / i_v, and a shape outside the kernels' envelope (train_max_pos_item + train_max_neg_item
 in [1, 64], num_hidden_unit a multiple of 16 in [16, 128] -- at 80 at most 48 slots, at 96, 112 and 128 at most 32 --, num_heads a divisor of it with
-num_hidden_unit / num_heads a multiple of 4).  SetRank and MIR have no model file here.
+num_hidden_unit / num_heads a multiple of 4).  SetRank is models/reranker/SetRank.py; MIR has no model file here.
 """
 from models.prm_model import PRMBase, PRMGeneral, PRMSequential   # the class bodies; see that module's docstring
 
